@@ -10,9 +10,14 @@ inputs per GPU, inputs and random-init weights resident in HBM before the timed 
 the batch is sharded by image (weak scaling: per-GPU batch fixed), and the FID-style feature block is all-gathered
 over RCCL on a side stream (3dgp_amd/distributed.py) -- the only collective on the path.
 
-Protocol: batch 16 per GPU (configs/scripts/inference.yaml:25) is the headline `value`; batch 4
-(training/base.yaml:5) is measured in the same process and reported under `other_batches`; defaults 10 warm-up + 50 timed
-steps.  Besides the contract fields the line carries
+Protocol: batch 16 per GPU (configs/scripts/inference.yaml:25) is the headline `value`; defaults 10 warm-up + 50
+timed steps.  A plain run sets up, warms up, times the K steps and prints the contract fields (metric, value, unit, ms_per_step,
+higher_is_better, dtype, ...) and nothing else.  `--dump-outputs DIR` writes the image of the last timed step to DIR/img.npy
+(float32; inputs and weights are seeded, so two builds can be compared output for output).
+
+`--full` adds everything else: batch 4 (training/base.yaml:5) measured in the same process under `other_batches`, the other launch mode,
+the FID-loop shapes, the host-side launch probes and the fields below (N > 1 runs the launch probe in a plain run too: its margin picks the
+headline's launch mode).  Besides the contract fields a `--full` line carries
   roofline     -- the dominant kernel (by HIP-event time measured here, on the launch stream, through the library's
                   per-kernel event hooks: start/stop events attached to each dispatch): algorithmic FLOP per launch / average launch
                   duration vs the fp32 MFMA peak; `traffic` (HBM bytes per launch), `hbm_gbs` (= traffic / the duration
@@ -260,10 +265,10 @@ def parity_statement(config):
     return st
 
 
-def timed_steps(step, barrier, steps, warmup, world, dev, finish=None, per_rank=None):
+def timed_steps(step, barrier, steps, warmup, world, dev, finish=None, per_rank=None, last=None):
     """W untimed steps, then exactly K steps between barrier + synchronize on both sides; max over ranks.  `per_rank` (a list) receives
     every rank's OWN time for the K steps -- stop-watch read after its own synchronize, BEFORE the closing barrier -- so that a straggler
-    shows in the line instead of hiding behind the maximum."""
+    shows in the line instead of hiding behind the maximum.  `last` (a list) receives what the last timed step returned."""
     for _ in range(warmup):
         step()
     barrier()
@@ -288,7 +293,26 @@ def timed_steps(step, barrier, steps, warmup, world, dev, finish=None, per_rank=
     elif per_rank is not None:
         per_rank[:] = [own]
     assert torch.isfinite(img).all()
+    if last is not None:
+        last[:] = [img]
     return elapsed
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write each array as out_dir/<name>.npy in float32.  If they hold more than `budget` bytes in all, each one is replaced by the same
+    fixed, seeded sample of its flattened elements (sorted indices, seed 0), sized to its share of the budget."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget:
+            keep = max(1, int(a.size * budget // total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def straggler_figures(per_rank_s, steps):
@@ -343,8 +367,12 @@ def parse_args(argv=None):
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=10)
+    ap.add_argument('--full', action='store_true', help='besides the headline: the other batch sizes and launch mode, per-kernel timing and roofline, '
+                                                         'FID-loop shapes, host-side launch probes, parity statement and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the image of the last timed step to DIR/img.npy (float32)')
     ap.add_argument('--batch', type=int, default=16, help='images per GPU per step of the headline value (16 = configs/scripts/inference.yaml:25)')
-    ap.add_argument('--other-batches', default='4', help='comma list of further per-GPU batch sizes measured in the same run (4 = training/base.yaml:5); "" = none')
+    ap.add_argument('--other-batches', default=None, help='comma list of further per-GPU batch sizes measured in the same run (default: 4 = training/base.yaml:5 '
+                                                           'with --full, none without); "" = none')
     ap.add_argument('--config', default='c3', choices=['c1', 'c2', 'c3', 'c4', 'c5'])
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cmax', type=int, default=0, help='override the backbone width (cbase = 64 x cmax): `--config c5 --cmax 1024` is the bf16 configuration as BASELINE.md section 3 sizes it')
@@ -370,6 +398,10 @@ def parse_args(argv=None):
                          "6 piece products, fp32 accumulation (fp32-grade results; reported with dtype 'bf16x3->f32' and never mixed with the default line)")
     args = ap.parse_args(argv)
     args.no_graph = not args.graph
+    if args.other_batches is None:
+        args.other_batches = '4' if args.full else ''
+    if not args.full and (args.fid_loop or args.other_batches.strip()):
+        ap.error('--fid-loop and --other-batches are measured with --full only')
     return args
 
 
@@ -397,6 +429,26 @@ def runs_cpu_baseline(args, world, rank):
     return world == 1 and rank == 0 and not args.no_cpu_baseline
 
 
+def headline_fields(args, cfg, G, world, elapsed):
+    """The contract fields of the line: the headline `value` (img/s over the K timed steps, all ranks), `ms_per_step`, what was run."""
+    names = dict(c1='BASELINE configs[0]: SDFood-like 64x64', c2='BASELINE configs[1]: Dogs 128x128', c3='BASELINE configs[2]: ImageNet 256x256',
+                 c4='BASELINE configs[3]: ImageNet 256x256', c5='BASELINE configs[4]: ImageNet 256x256')
+    return {
+        'metric': 'generator-forward img/s @256^2, 64 steps' if args.config in ('c3', 'c4') else (
+            'generator-forward img/s @256^2, 96 steps, bf16 blocks' if args.config == 'c5' else f'generator-forward img/s ({args.config})'),
+        'value': round(args.batch * world * args.steps / elapsed, 3), 'unit': 'img/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': round(elapsed / args.steps * 1e3, 3), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        'dtype': ('bf16 (backbone blocks >= %d^2: bf16 activations + weights, fp32 accumulate), f32 elsewhere' % cfg.fp16_resolution) if cfg.fp16_resolution
+                 else ('f32' if args.arith in ('f32', 'direct') else 'bf16x3->f32 (3x3 and x2 layers), f32 elsewhere'), 'data': 'synthetic',
+        'config': {'workload': f'{names[args.config]}, {cfg.num_ray_steps}(+{cfg.num_ray_steps}) ray steps, cmax {cfg.cmax}, '
+                               f'c_dim {cfg.c_dim}, tri-plane {cfg.tri_plane_res}^2 x {cfg.plane_channels}, full HIP path',
+                   'batch_per_gpu': args.batch, 'global_batch': args.batch * world, 'img_resolution': cfg.img_resolution,
+                   'num_ray_steps': cfg.num_ray_steps, 'depth_adaptor': bool(args.depth_adaptor), 'parallelism': f'dp{world} (batch-sharded, weights replicated)',
+                   'schedule': dict(chunk=G.synthesis.chunk, chunk_from=G.synthesis.chunk_from,
+                                    torgb_on_second_stream=bool(G.synthesis.tri_plane_decoder.overlap_torgb))},
+    }
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -407,7 +459,7 @@ def main():
     tdgp = importlib.import_module('3dgp_amd')
     D = tdgp.distributed
     rank, world, local_rank, dev, host = setup_rank(args, tdgp)
-    if not args.no_fid_loop:
+    if args.full and not args.no_fid_loop:
         args.fid_loop = True                # N > 1: it IS the multi-GPU workload; N == 1: the FID forward with and without the adaptors
     tdgp._lib.load()                       # the HIP library must be there: no fallback
     if args.arith == 'split':
@@ -475,7 +527,7 @@ def main():
     x = inputs(args.batch)
     # ---- host-side launch cost: is the eager forward launch-bound, alone and beside 7 busy sibling processes? ----
     host_probe = None
-    if not args.no_host_probe:
+    if not args.no_host_probe and (args.full or world > 1):         # N > 1: the margin decides the headline's launch mode
         eager = make_step(x, use_graph=False)
         for _ in range(3):
             eager()
@@ -517,8 +569,22 @@ def main():
                 host_probe['decision'] = 'margin < 2 on some rank: headline switched to HIP graph replay'
             else:
                 host_probe['decision'] = 'eager kept' if not args.graph else 'graph requested'
-    per_rank_s = []
-    elapsed = timed_steps(make_step(x), barrier, args.steps, args.warmup, world, dev, finish, per_rank=per_rank_s)
+    per_rank_s, last = [], []
+    elapsed = timed_steps(make_step(x), barrier, args.steps, args.warmup, world, dev, finish, per_rank=per_rank_s, last=last)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(img=last[0].detach().cpu().numpy()))
+    del last
+    head = dict(headline_fields(args, cfg, G, world, elapsed), launch='eager' if args.no_graph else
+                'hip graph replay (3dgp_amd/graphs.py: every kernel of the forward, one submission per step)', rccl_ranks_seen=ranks_seen,
+                per_rank_ms=straggler_figures(per_rank_s, args.steps)[0], straggler_ratio=straggler_figures(per_rank_s, args.steps)[1])
+    if not args.full:
+        if rank == 0:
+            if host_probe is not None:
+                head['host_launch'] = host_probe
+            print(json.dumps(head))
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
     # the other launch mode next to the headline (eager when the headline replays a graph, and the other way round)
     alt_elapsed = timed_steps(make_step(x, use_graph=args.no_graph), barrier, args.steps, args.warmup, world, dev, finish)
 
@@ -732,23 +798,8 @@ def main():
 
     if rank == 0:
         total_imgs = args.batch * world * args.steps
-        names = dict(c1='BASELINE configs[0]: SDFood-like 64x64', c2='BASELINE configs[1]: Dogs 128x128', c3='BASELINE configs[2]: ImageNet 256x256',
-                     c4='BASELINE configs[3]: ImageNet 256x256', c5='BASELINE configs[4]: ImageNet 256x256')
         out = {
-            'metric': 'generator-forward img/s @256^2, 64 steps' if args.config in ('c3', 'c4') else (
-                'generator-forward img/s @256^2, 96 steps, bf16 blocks' if args.config == 'c5' else f'generator-forward img/s ({args.config})'),
-            'value': round(total_imgs / elapsed, 3), 'unit': 'img/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': round(ms_step, 3), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': ('bf16 (backbone blocks >= %d^2: bf16 activations + weights, fp32 accumulate), f32 elsewhere' % cfg.fp16_resolution) if cfg.fp16_resolution
-                     else ('f32' if args.arith in ('f32', 'direct') else 'bf16x3->f32 (3x3 and x2 layers), f32 elsewhere'), 'data': 'synthetic',
-            'config': {'workload': f'{names[args.config]}, {cfg.num_ray_steps}(+{cfg.num_ray_steps}) ray steps, cmax {cfg.cmax}, '
-                                   f'c_dim {cfg.c_dim}, tri-plane {cfg.tri_plane_res}^2 x {cfg.plane_channels}, full HIP path',
-                       'batch_per_gpu': args.batch, 'global_batch': args.batch * world, 'img_resolution': cfg.img_resolution,
-                       'num_ray_steps': cfg.num_ray_steps, 'depth_adaptor': bool(args.depth_adaptor), 'parallelism': f'dp{world} (batch-sharded, weights replicated)',
-                       'schedule': dict(chunk=G.synthesis.chunk, chunk_from=G.synthesis.chunk_from, torgb_on_second_stream=bool(overlap_was))},
-            'launch': 'eager' if args.no_graph else 'hip graph replay (3dgp_amd/graphs.py: every kernel of the forward, one submission per step)',
-            ('graph_value' if args.no_graph else 'eager_value'): round(total_imgs / alt_elapsed, 3), 'fid_loop': fid_loop,
-            'rccl_ranks_seen': ranks_seen, 'per_rank_ms': straggler_figures(per_rank_s, args.steps)[0], 'straggler_ratio': straggler_figures(per_rank_s, args.steps)[1],
+            **head, ('graph_value' if args.no_graph else 'eager_value'): round(total_imgs / alt_elapsed, 3), 'fid_loop': fid_loop,
             'host': None if host is None else dict(rank0=host, omp_num_threads=os.environ.get('OMP_NUM_THREADS')), 'host_launch': host_probe,
             'parity_tolerance': parity_statement(args.config), 'roofline': roofline, 'whole_forward': whole, 'other_batches': others, 'kernels': kernels,
         }
