@@ -22,8 +22,14 @@
 
 namespace {
 
-constexpr int MAXS = 256;          // max samples per ray in one pass (2*S for the merged pass)
+constexpr int MAXS = 256;          // capacity of the short-ray kernels: samples per ray in one pass (2*S for the merged pass)
 constexpr int RAYS_PER_BLOCK = 4;
+// Long rays: the same one-wave-per-ray kernels instantiated at larger capacities, launched only above
+// the short kernels' thresholds.  A pass (coarse S, fine N, a pdf row of S - 2 <= 510 entries) holds at most MAXS_PASS samples: beyond 512
+// the pdf normaliser would reach a level of torch's cascade sum that torch_order_sum_lds does not restate.  A merged list holds at most
+// MAXS_LONG = 2 * MAXS_PASS.
+constexpr int MAXS_PASS = 512;
+constexpr int MAXS_LONG = 1024;
 
 // Per-wave LDS scratch.  MS = capacity in samples; the fused kernels pick 128 when the ray fits (4.1 KB per wave -> 8 waves
 // per SIMD instead of 4: these kernels are chains of dependent LDS / cross-lane steps, occupancy is what hides them).
@@ -38,6 +44,13 @@ struct alignas(16) WaveScratchT {
 };
 using WaveScratch = WaveScratchT<MAXS>;
 
+// The plain marcher reads only z / sig / w: its long form (MS = MAXS_LONG) keeps only those (12.3 KB per wave instead of 32.8 KB).
+template <int MS> struct alignas(16) MarchScratchT { float z[MS]; float sig[MS]; float w[MS + 4]; };
+template <> struct alignas(16) MarchScratchT<MAXS> : WaveScratch {};      // the short form keeps its layout
+// unify_samples ranks the depths only.
+template <int MS> struct alignas(16) UnifyScratchT { float z[MS]; };
+template <> struct alignas(16) UnifyScratchT<MAXS> : WaveScratch {};
+
 __device__ __forceinline__ void wave_sync() {
     // all LDS traffic of a wave is issued in order; this only stops the compiler from reordering across it
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -51,6 +64,13 @@ __device__ __forceinline__ float s2t(float s, float t_near, float t_far) { retur
 // tri_plane_renderer.py:355-387.
 // flags: bit0 use_inf_depth, bit1 last_back, bit3 relu clamp
 // ------------------------------------------------------------------------------------------------
+// LONGX: a list longer than MAXS (the long-ray kernels only).  alpha = 1 - exp(-delta sigma) cancels: with delta ~ 1 / S its relative
+// error is exp's ulp over delta sigma, and at 768 samples a 1-ulp expf left the image 2.6x further (mean) from the reference's float64
+// run than the reference's own fp32 run.  The long form rounds exp once from fp64 (the exactly rounded expf but for ~2^-29 of inputs).
+template <bool LONGX>
+__device__ __forceinline__ float exp_neg(float x) { return LONGX ? (float)exp(-(double)x) : expf(-x); }
+
+template <bool LONGX = false>
 __device__ void march_classical_lds(const float* z, const float* sig, float* w, int S, int flags, float cut_thr, float& final_T, float& wagg) {
     const int l = lane_id();
     double carry = 1.0;
@@ -69,7 +89,7 @@ __device__ void march_classical_lds(const float* z, const float* sig, float* w, 
                 const float delta = (i < S - 1) ? (z[i + 1] - z[i]) : ((flags & 1) ? 1e10f : 1e-3f);
                 float sp = (flags & 8) ? (sig[i] > 0.f ? sig[i] : 0.f) : softplus20f(sig[i]);
                 if (sp < cut_thr) sp = 0.f;
-                alpha[c] = 1.0f - expf(-(delta * sp));
+                alpha[c] = 1.0f - exp_neg<LONGX>(delta * sp);
                 fac[c] = (1.0f - alpha[c]) + 1e-10f;
             }
         }
@@ -89,7 +109,7 @@ __device__ void march_classical_lds(const float* z, const float* sig, float* w, 
             float delta = (i < S - 1) ? (z[i + 1] - z[i]) : ((flags & 1) ? 1e10f : 1e-3f);
             float sp = (flags & 8) ? (sig[i] > 0.f ? sig[i] : 0.f) : softplus20f(sig[i]);
             if (sp < cut_thr) sp = 0.f;                        // cut_quantile (:366-368); cut_thr = 0 never cuts (sp >= 0)
-            alpha = 1.0f - expf(-(delta * sp));
+            alpha = 1.0f - exp_neg<LONGX>(delta * sp);
             fac = (1.0f - alpha) + 1e-10f;
         }
         // transmittance = torch.cumprod on the CPU: prefixes accumulated in fp64, each rounded to fp32.  The fp64 DPP
@@ -112,6 +132,7 @@ __device__ void march_classical_lds(const float* z, const float* sig, float* w, 
 
 // mip marcher weights on LDS-resident data: M = S (inf depth) or S-1 mid-point samples.
 // tri_plane_renderer.py:305-334.
+template <bool LONGX = false>
 __device__ void march_mip_lds(const float* z, const float* sig, float* w, int S, int flags, float density_bias, float cut_thr, float& final_T,
                               float& wagg) {
     const int l = lane_id();
@@ -128,7 +149,7 @@ __device__ void march_mip_lds(const float* z, const float* sig, float* w, int S,
             float sp = softplus20f(smid + density_bias);
             if (sp < cut_thr) sp = 0.f;                        // cut_quantile (:324-326)
             float dd = sp * delta;
-            alpha = 1.0f - expf(-dd);
+            alpha = 1.0f - exp_neg<LONGX>(dd);
             fac = (1.0f - alpha) + 1e-10f;
         }
         const double incl64 = wave_scan_f64<true>((double)fac) * carry;        // fp64 prefixes rounded to fp32: see march_classical_lds
@@ -149,7 +170,8 @@ __device__ void march_mip_lds(const float* z, const float* sig, float* w, int S,
 // i.e. the searchsorted indices.  ATen's sum kernel (cpu/SumKernel.cpp, AVX2 dispatch: 8 fp32 lanes) cuts the row
 // into nv = n/8 vectors, adds them into 4 interleaved vector accumulators (acc[k] += V[4i+k]), the nv%4 left-over
 // vectors into accumulator 0, then acc0 += acc1, acc2, acc3, and finally a scalar takes the n%8 tail elements in
-// order followed by the 8 lanes of acc0 in order (no cascade level is reached below 512 elements; n <= 254 here).
+// order followed by the 8 lanes of acc0 in order (ATen's cascade_sum folds its accumulators every 16 groups of 4 x 8 lanes: the order
+// first changes at 18 groups = 576 elements; n <= MAXS_PASS - 2 = 510 here, checked on the host).
 // Rows shorter than 8 run the same scheme on scalars.  Lane (a = (l>>3)&3, col = l&7) plays lane col of accumulator a;
 // every lane returns the result.
 // ------------------------------------------------------------------------------------------------
@@ -193,12 +215,13 @@ __device__ void importance_lds(SC& sc, int S, int Wn, GetU getu, int N, int mip,
     const int l = lane_id();
     const float eps = 1e-5f;
     float* w = sc.w;
+    constexpr int CAP = sizeof(sc.z) / sizeof(float), NV = (CAP > MAXS ? CAP : MAXS) / 64;
     // smoothed / offset weights, in place (two passes through registers)
     if (mip) {
         // max_pool1d(2,1,pad 1) -> Wn+1, avg_pool1d(2,1) -> Wn, + 0.01
-        float nv[MAXS / 64];
+        float nv[NV];
 #pragma unroll
-        for (int c = 0; c < MAXS / 64; c++) {
+        for (int c = 0; c < NV; c++) {
             const int i = l + 64 * c;
             if (i < Wn) {
                 float a = (i - 1 >= 0) ? w[i - 1] : -INFINITY, b = w[i], d = (i + 1 < Wn) ? w[i + 1] : -INFINITY;
@@ -209,7 +232,7 @@ __device__ void importance_lds(SC& sc, int S, int Wn, GetU getu, int N, int mip,
         }
         wave_sync();
 #pragma unroll
-        for (int c = 0; c < MAXS / 64; c++) {
+        for (int c = 0; c < NV; c++) {
             const int i = l + 64 * c;
             if (i < Wn) w[i] = nv[c];
         }
@@ -298,20 +321,25 @@ __global__ __launch_bounds__(256) void density_activation_kernel(const float* __
         y[i] = relu ? (x[i] > 0.f ? x[i] : 0.f) : softplus20f(x[i] + bias);
 }
 
-// generic marcher: colours [rays,S,C], densities [rays,S], depths [rays,S]
+// generic marcher: colours [rays,S,C], densities [rays,S], depths [rays,S].  MS = MAXS, or MAXS_LONG for S > MAXS.
+template <int MS>
 __global__ __launch_bounds__(256) void ray_march_kernel(const float* __restrict__ colors, const float* __restrict__ dens,
                                                        const float* __restrict__ depths, float* __restrict__ rgb, float* __restrict__ depth_o,
                                                        float* __restrict__ weights, float* __restrict__ final_T, int64_t rays, int S, int C,
                                                        int marcher, int flags, float density_bias, float cut_thr) {
-    __shared__ WaveScratch scratch[RAYS_PER_BLOCK];
+    __shared__ MarchScratchT<MS> scratch[RAYS_PER_BLOCK];
     const int wv = threadIdx.x >> 6, l = lane_id();
     const int64_t r = (int64_t)blockIdx.x * RAYS_PER_BLOCK + wv;
     if (r >= rays) return;
-    WaveScratch& sc = scratch[wv];
+    MarchScratchT<MS>& sc = scratch[wv];
     for (int i = l; i < S; i += 64) { sc.z[i] = depths[r * S + i]; sc.sig[i] = dens[r * S + i]; }
     wave_sync();
     float fT, wagg;
     const int M = (marcher == 0) ? S : ((flags & 1) ? S : S - 1);
+    if (MS > MAXS && S > MAXS) {
+        if (marcher == 0) march_classical_lds<(MS > MAXS)>(sc.z, sc.sig, sc.w, S, flags, cut_thr, fT, wagg);
+        else march_mip_lds<(MS > MAXS)>(sc.z, sc.sig, sc.w, S, flags, density_bias, cut_thr, fT, wagg);
+    } else
     if (marcher == 0) march_classical_lds(sc.z, sc.sig, sc.w, S, flags, cut_thr, fT, wagg);
     else march_mip_lds(sc.z, sc.sig, sc.w, S, flags, density_bias, cut_thr, fT, wagg);
     if (weights) for (int i = l; i < M; i += 64) weights[r * M + i] = sc.w[i];
@@ -339,15 +367,16 @@ __global__ __launch_bounds__(256) void ray_march_kernel(const float* __restrict_
     if (l == 0) final_T[r] = fT;
 }
 
+template <int MS>
 __global__ __launch_bounds__(256) void sample_importance_kernel(const float* __restrict__ z, const float* __restrict__ weights,
                                                                const float* __restrict__ u, float* __restrict__ samples, int32_t* __restrict__ inds,
                                                                int32_t* __restrict__ below, int32_t* __restrict__ above, float* __restrict__ cdf_o,
                                                                int64_t rays, int S, int Wn, int N, int mip) {
-    __shared__ WaveScratch scratch[RAYS_PER_BLOCK];
+    __shared__ WaveScratchT<MS> scratch[RAYS_PER_BLOCK];
     const int wv = threadIdx.x >> 6, l = lane_id();
     const int64_t r = (int64_t)blockIdx.x * RAYS_PER_BLOCK + wv;
     if (r >= rays) return;
-    WaveScratch& sc = scratch[wv];
+    WaveScratchT<MS>& sc = scratch[wv];
     for (int i = l; i < S; i += 64) sc.z[i] = z[r * S + i];
     for (int i = l; i < Wn; i += 64) sc.w[i] = weights[r * Wn + i];
     wave_sync();
@@ -383,6 +412,54 @@ __device__ __forceinline__ void stable_ranks(const float* key, int M, int* rank 
     else if (M <= 128) stable_ranks_n<2>(key, M, rank);
     else if (M <= 192) stable_ranks_n<3>(key, M, rank);
     else stable_ranks_n<4>(key, M, rank);
+}
+
+// The same for the long lists (M <= MAXS_LONG): 8 or 16 value slots per lane.  O(M^2 / 64) per lane -- the fallback for lists that
+// are not ascending, and unify_samples' rank (not on the renderer's forward).
+template <int NR>
+__device__ __forceinline__ void stable_ranks_long(const float* key, int M, int (&rank)[NR]) {
+    static_assert(NR == MAXS_PASS / 64 || NR == MAXS_LONG / 64, "stable_ranks_long: 8 or 16 slots");
+#pragma unroll
+    for (int c = 0; c < NR; c++) rank[c] = 0;
+    if (M <= MAXS_PASS) stable_ranks_n<MAXS_PASS / 64>(key, M, rank);
+    else stable_ranks_n<NR>(key, M, rank);
+}
+
+// Bitonic sort of 64 * NS (key, index) pairs, NS per lane (element e = 64 c + lane), ascending by (key, index): the network of
+// wave_bitonic_sort2 below for any power-of-two NS.  Stages with j >= 64 are compare-exchanges between two slots of the same lane,
+// the others one pair of cross-lane permutes per slot.  Indices are unique, so the order is total and the result is the stable sort.
+// For 128 < N <= 512 fine samples (long rays): 45 stages at NS = 8, against 512 broadcasts x 8 slots of the brute-force rank.
+template <int NS, int CAP>
+__device__ __forceinline__ void wave_bitonic_sort_n(float (&key)[CAP], int (&idx)[CAP]) {
+    static_assert(NS <= CAP && (NS & (NS - 1)) == 0, "wave_bitonic_sort_n: NS a power of two within the arrays");
+    const int l = lane_id();
+#pragma unroll
+    for (int k = 2; k <= 64 * NS; k <<= 1) {
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            if (j >= 64) {
+                const int js = j >> 6;
+#pragma unroll
+                for (int c = 0; c < NS; c++) {
+                    if (c & js) continue;
+                    const int c2 = c | js;
+                    const bool asc = ((64 * c) & k) == 0;           // bits of e at or above 64 are the slot's; c and c2 agree on bit k
+                    const bool less2 = key[c2] < key[c] || (key[c2] == key[c] && idx[c2] < idx[c]);
+                    if (less2 == asc) { const float tk = key[c]; key[c] = key[c2]; key[c2] = tk; const int ti = idx[c]; idx[c] = idx[c2]; idx[c2] = ti; }
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < NS; c++) {
+                    const float pk = __shfl_xor(key[c], j, 64);
+                    const int pi = __shfl_xor(idx[c], j, 64);
+                    const bool asc = ((64 * c + l) & k) == 0;
+                    const bool keep_min = ((l & j) == 0) == asc;
+                    const bool partner_less = pk < key[c] || (pk == key[c] && pi < idx[c]);
+                    if (partner_less == keep_min) { key[c] = pk; idx[c] = pi; }
+                }
+            }
+        }
+    }
 }
 
 // Bitonic sort of one (key, index) pair per lane across the 64 lanes of a wave, ascending by (key, index): 21 compare-exchange
@@ -454,16 +531,32 @@ __global__ __launch_bounds__(256) void importance_from_coarse_kernel(const float
     for (int i = l; i < S; i += 64) { sc.z[i] = sdist[r * S + i]; sc.sig[i] = rgbs[(r * S + i) * 4 + 3]; }
     // the draws are not needed before the cdf exists: their loads go out now and land during the march
     float upre[MS / 64];
+    if constexpr (MS > MAXS) {      // long rays: the draws wait in LDS (sc.col[1]) -- a register array behind the non-inlined importance_lds would live in scratch
+        for (int i = l; i < N; i += 64) sc.col[1][i] = u_fine[r * N + i];
+    } else {
 #pragma unroll
     for (int c = 0; c < MS / 64; c++) upre[c] = (l + 64 * c < N) ? u_fine[r * N + l + 64 * c] : 0.f;
+    }
     wave_sync();
     TPH(0)
     float fT, wagg;
     int Wn = S;
+    if (MS > MAXS && S > MAXS) {    // the coarse list marched as tdgp_ray_march marches a list of that length
+        if (marcher == 0) march_classical_lds<(MS > MAXS)>(sc.z, sc.sig, sc.w, S, flags, cut_thr, fT, wagg);
+        else { march_mip_lds<(MS > MAXS)>(sc.z, sc.sig, sc.w, S, flags, density_bias, cut_thr, fT, wagg); Wn = (flags & 1) ? S : S - 1; }
+    } else
     if (marcher == 0) march_classical_lds(sc.z, sc.sig, sc.w, S, flags, cut_thr, fT, wagg);
     else { march_mip_lds(sc.z, sc.sig, sc.w, S, flags, density_bias, cut_thr, fT, wagg); Wn = (flags & 1) ? S : S - 1; }
     TPH(1)
     float* tkey = sc.col[0];
+    if constexpr (MS > MAXS)
+        // inlined here (the short forms inline it on their own): a call would pass the lambdas' captures through private scratch
+        [[clang::always_inline]] importance_lds(sc, S, Wn, [&](int j) { return sc.col[1][j]; }, N, marcher, [&](int j, float smp, int ind, int, int) {
+            tkey[j] = s2t(smp, t_near, t_far);
+            if (sfine) sfine[r * N + j] = smp;
+            if (inds) inds[r * N + j] = ind;
+        });
+    else
     importance_lds(sc, S, Wn, [&](int j) { float v = upre[0];
 #pragma unroll
                                           for (int c = 1; c < MS / 64; c++) v = (j >> 6) == c ? upre[c] : v;
@@ -558,6 +651,24 @@ __global__ __launch_bounds__(256) void importance_from_coarse_kernel(const float
         }
         return;
     }
+    if constexpr (MS > MAXS) {      // long rays, 128 < N <= MS: the bitonic network over 256 or 512 (t, draw index) pairs, NS per lane
+        constexpr int NSL = MS / 64;
+        float key[NSL];
+        int idx[NSL];
+#pragma unroll
+        for (int c = 0; c < NSL; c++) { const int e = l + 64 * c; key[c] = e < N ? tkey[e] : INFINITY; idx[c] = e; }    // padding sorts last (index >= N)
+        if (N <= 256) wave_bitonic_sort_n<4>(key, idx);
+        else wave_bitonic_sort_n<NSL>(key, idx);
+#pragma unroll
+        for (int c = 0; c < NSL; c++) {
+            const int pos = l + 64 * c;
+            if (pos < N) {
+                tfine[r * N + pos] = key[c];
+                if (fine_perm) fine_perm[r * N + pos] = idx[c];
+            }
+        }
+        return;
+    } else {
     int rank[MAXS / 64];
     stable_ranks(tkey, N, rank);
 #pragma unroll
@@ -568,24 +679,28 @@ __global__ __launch_bounds__(256) void importance_from_coarse_kernel(const float
             if (fine_perm) fine_perm[r * N + rank[c]] = j;
         }
     }
+    }
 }
 
+// MS = MAXS, or MAXS_LONG for S1 + S2 > MAXS (brute-force stable rank over 8 / 16 slots per lane: the staged path, not the renderer's forward).
+template <int MS>
 __global__ __launch_bounds__(256) void unify_kernel(const float* __restrict__ d1, const float* __restrict__ c1, const float* __restrict__ s1, int S1,
                                                    const float* __restrict__ d2, const float* __restrict__ c2, const float* __restrict__ s2, int S2,
                                                    float* __restrict__ d, float* __restrict__ c, float* __restrict__ s, int32_t* __restrict__ perm,
                                                    int64_t rays, int C) {
-    __shared__ WaveScratch scratch[RAYS_PER_BLOCK];
+    __shared__ UnifyScratchT<MS> scratch[RAYS_PER_BLOCK];
     const int wv = threadIdx.x >> 6, l = lane_id();
     const int64_t r = (int64_t)blockIdx.x * RAYS_PER_BLOCK + wv;
     if (r >= rays) return;
-    WaveScratch& sc = scratch[wv];
+    UnifyScratchT<MS>& sc = scratch[wv];
     const int M = S1 + S2;
     for (int i = l; i < M; i += 64) sc.z[i] = i < S1 ? d1[r * S1 + i] : d2[r * S2 + (i - S1)];
     wave_sync();
-    int rank[MAXS / 64];
-    stable_ranks(sc.z, M, rank);
+    int rank[MS / 64];
+    if constexpr (MS > MAXS) stable_ranks_long(sc.z, M, rank);
+    else stable_ranks(sc.z, M, rank);
 #pragma unroll
-    for (int cc = 0; cc < MAXS / 64; cc++) {
+    for (int cc = 0; cc < MS / 64; cc++) {
         const int i = l + 64 * cc;
         if (i >= M) continue;
         const int pos = rank[cc];
@@ -631,9 +746,11 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(const float* __res
     bool bad = false;
     for (int i = l; i < M; i += 64)
         if (i + 1 < M && i + 1 != S1 && sc.cdf[i + 1] < sc.cdf[i]) bad = true;
-    int rank[MAXS / 64];
+    constexpr int RK = (MS > MAXS ? MS : MAXS) / 64;
+    int rank[RK];
     if (__any(bad)) {
-        stable_ranks(sc.cdf, M, rank);
+        if constexpr (MS > MAXS) stable_ranks_long(sc.cdf, M, rank);
+        else stable_ranks(sc.cdf, M, rank);
     } else {
         // Ranks of a stable merge of two ascending lists (coarse wins ties).
         //   fine element j:    its own index + #coarse <= f_j  =: j + cnt_j     -- a binary search in the coarse list;
@@ -678,7 +795,7 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(const float* __res
         }
         wave_sync();
 #pragma unroll
-        for (int cc = 0; cc < MAXS / 64; cc++) rank[cc] = 0;
+        for (int cc = 0; cc < RK; cc++) rank[cc] = 0;
         int carry = 0;
 #pragma unroll
         for (int cc = 0; cc < NSL; cc++) {
@@ -707,6 +824,10 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(const float* __res
     TPH(2)
     float fT, wagg;
     const int Mm = (marcher == 0) ? M : ((flags & 1) ? M : M - 1);
+    if (MS > MAXS && M > MAXS) {
+        if (marcher == 0) march_classical_lds<(MS > MAXS)>(sc.z, sc.sig, sc.w, M, flags, cut_thr, fT, wagg);
+        else march_mip_lds<(MS > MAXS)>(sc.z, sc.sig, sc.w, M, flags, density_bias, cut_thr, fT, wagg);
+    } else
     if (marcher == 0) march_classical_lds(sc.z, sc.sig, sc.w, M, flags, cut_thr, fT, wagg);
     else march_mip_lds(sc.z, sc.sig, sc.w, M, flags, density_bias, cut_thr, fT, wagg);
     TPH(3)
@@ -780,13 +901,18 @@ TDGP_API int tdgp_density_activation(const float* sigma, float* out, int64_t n, 
 TDGP_API int tdgp_ray_march(const float* colors, const float* densities, const float* depths, float* rgb, float* depth, float* weights,
                             float* final_T, int64_t rays, int S, int C, int marcher, int flags, float density_bias, float cut_threshold, tdgp_stream_t stream) {
     TDGP_CHECK(colors && densities && depths && rgb && depth && final_T, TDGP_EINVAL, "ray_march: null pointer");
-    TDGP_CHECK(S >= 2 && S <= MAXS, TDGP_EUNSUPPORTED, "ray_march: S=%d outside [2,%d]", S, MAXS);
+    TDGP_CHECK(S >= 2 && S <= MAXS_LONG, TDGP_EUNSUPPORTED, "ray_march: S=%d outside [2,%d] (a merged list of at most %d + %d samples)", S, MAXS_LONG,
+               MAXS_PASS, MAXS_PASS);
     TDGP_CHECK(C >= 1 && C <= 8, TDGP_EUNSUPPORTED, "ray_march: C=%d outside [1,8]", C);
     TDGP_CHECK(marcher == 0 || marcher == 1, TDGP_EINVAL, "ray_march: unknown ray marcher %d", marcher);
     TDGP_FAULT_CHECK("ray_march");
     if (rays == 0) return TDGP_OK;
-    TDGP_LAUNCH("ray_march_kernel", ray_march_kernel, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, colors, densities, depths, rgb, depth, weights,
-                       final_T, rays, S, C, marcher, flags, density_bias, cut_threshold);
+    if (S <= MAXS)
+        TDGP_LAUNCH("ray_march_kernel", ray_march_kernel<MAXS>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, colors, densities, depths, rgb, depth, weights,
+                    final_T, rays, S, C, marcher, flags, density_bias, cut_threshold);
+    else
+        TDGP_LAUNCH("ray_march_kernel", ray_march_kernel<MAXS_LONG>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, colors, densities, depths, rgb, depth,
+                    weights, final_T, rays, S, C, marcher, flags, density_bias, cut_threshold);
     TDGP_LAUNCH_CHECK();
     return TDGP_OK;
 }
@@ -795,10 +921,15 @@ TDGP_API int tdgp_sample_importance(const float* z, const float* weights, const 
                                     int32_t* above, float* cdf, int64_t rays, int S, int Wn, int N, int marcher, tdgp_stream_t stream) {
     TDGP_CHECK(z && weights && u && samples, TDGP_EINVAL, "sample_importance: null pointer");
     TDGP_CHECK(!inds || (below && above), TDGP_EINVAL, "sample_importance: inds/below/above come together");
-    TDGP_CHECK(S >= 4 && S <= MAXS && Wn >= 3 && Wn <= S && N >= 1, TDGP_EUNSUPPORTED, "sample_importance: bad S=%d Wn=%d N=%d", S, Wn, N);
+    TDGP_CHECK(S >= 4 && S <= MAXS_PASS && Wn >= 3 && Wn <= S && N >= 1, TDGP_EUNSUPPORTED,
+               "sample_importance: bad S=%d Wn=%d N=%d (S at most %d: beyond it torch's sum order is not restated)", S, Wn, N, MAXS_PASS);
     if (rays == 0) return TDGP_OK;
-    TDGP_LAUNCH("sample_importance_kernel", sample_importance_kernel, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, z, weights, u, samples, inds, below,
-                       above, cdf, rays, S, Wn, N, marcher);
+    if (S <= MAXS)
+        TDGP_LAUNCH("sample_importance_kernel", sample_importance_kernel<MAXS>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, z, weights, u, samples, inds,
+                    below, above, cdf, rays, S, Wn, N, marcher);
+    else
+        TDGP_LAUNCH("sample_importance_kernel", sample_importance_kernel<MAXS_PASS>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, z, weights, u, samples,
+                    inds, below, above, cdf, rays, S, Wn, N, marcher);
     TDGP_LAUNCH_CHECK();
     return TDGP_OK;
 }
@@ -806,9 +937,13 @@ TDGP_API int tdgp_sample_importance(const float* z, const float* weights, const 
 TDGP_API int tdgp_unify_samples(const float* d1, const float* c1, const float* s1, int S1, const float* d2, const float* c2, const float* s2,
                                 int S2, float* d, float* c, float* s, int32_t* perm, int64_t rays, int C, tdgp_stream_t stream) {
     TDGP_CHECK(d1 && c1 && s1 && d2 && c2 && s2 && d && c && s, TDGP_EINVAL, "unify_samples: null pointer");
-    TDGP_CHECK(S1 >= 1 && S2 >= 1 && S1 + S2 <= MAXS, TDGP_EUNSUPPORTED, "unify_samples: S1+S2=%d > %d", S1 + S2, MAXS);
+    TDGP_CHECK(S1 >= 1 && S2 >= 1 && S1 + S2 <= MAXS_LONG, TDGP_EUNSUPPORTED, "unify_samples: S1+S2=%d > %d", S1 + S2, MAXS_LONG);
     if (rays == 0) return TDGP_OK;
-    TDGP_LAUNCH("unify_kernel", unify_kernel, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, d1, c1, s1, S1, d2, c2, s2, S2, d, c, s, perm, rays, C);
+    if (S1 + S2 <= MAXS)
+        TDGP_LAUNCH("unify_kernel", unify_kernel<MAXS>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, d1, c1, s1, S1, d2, c2, s2, S2, d, c, s, perm, rays, C);
+    else
+        TDGP_LAUNCH("unify_kernel", unify_kernel<MAXS_LONG>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, d1, c1, s1, S1, d2, c2, s2, S2, d, c, s, perm, rays,
+                    C);
     TDGP_LAUNCH_CHECK();
     return TDGP_OK;
 }
@@ -817,16 +952,19 @@ TDGP_API int tdgp_importance_from_coarse(const float* rgbs_coarse, const float* 
                                          float* sdist_fine, int32_t* inds, int32_t* fine_perm, int64_t rays, int S, int N, int marcher, int flags,
                                          float density_bias, float cut_threshold, float t_near, float t_far, tdgp_stream_t stream) {
     TDGP_CHECK(rgbs_coarse && sdist && u_fine && tdist_fine, TDGP_EINVAL, "importance_from_coarse: null pointer");
-    TDGP_CHECK(S >= 4 && S <= MAXS && N >= 1 && N <= MAXS, TDGP_EUNSUPPORTED, "importance_from_coarse: bad S=%d N=%d (both at most %d)", S, N, MAXS);
+    TDGP_CHECK(S >= 4 && S <= MAXS_PASS && N >= 1 && N <= MAXS_PASS, TDGP_EUNSUPPORTED, "importance_from_coarse: bad S=%d N=%d (both at most %d)", S, N, MAXS_PASS);
     TDGP_CHECK(marcher == 0 || marcher == 1, TDGP_EINVAL, "importance_from_coarse: unknown ray marcher %d", marcher);
     TDGP_FAULT_CHECK("importance_from_coarse");
     if (rays == 0) return TDGP_OK;
     if (S <= 128 && N <= 128)
         TDGP_LAUNCH("importance_from_coarse_kernel", importance_from_coarse_kernel<128>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, sdist,
                            u_fine, tdist_fine, sdist_fine, inds, fine_perm, rays, S, N, marcher, flags, density_bias, cut_threshold, t_near, t_far);
-    else
+    else if (S <= MAXS && N <= MAXS)
         TDGP_LAUNCH("importance_from_coarse_kernel", importance_from_coarse_kernel<MAXS>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, sdist,
                            u_fine, tdist_fine, sdist_fine, inds, fine_perm, rays, S, N, marcher, flags, density_bias, cut_threshold, t_near, t_far);
+    else                            // long rays: 16.4 KB of scratch per wave
+        TDGP_LAUNCH("importance_from_coarse_kernel", importance_from_coarse_kernel<MAXS_PASS>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse,
+                    sdist, u_fine, tdist_fine, sdist_fine, inds, fine_perm, rays, S, N, marcher, flags, density_bias, cut_threshold, t_near, t_far);
     TDGP_LAUNCH_CHECK();
     return TDGP_OK;
 }
@@ -835,7 +973,7 @@ TDGP_API int tdgp_merge_composite(const float* rgbs_coarse, const float* t_coars
                                   float* rgb, float* depth, float* wsum, float* final_T, int32_t* perm, const int32_t* fine_perm, int64_t rays,
                                   int marcher, int flags, float density_bias, float cut_threshold, tdgp_stream_t stream) {
     TDGP_CHECK(rgbs_coarse && t_coarse && rgbs_fine && t_fine && rgb && depth, TDGP_EINVAL, "merge_composite: null pointer");
-    TDGP_CHECK(S1 >= 1 && S2 >= 1 && S1 + S2 <= MAXS, TDGP_EUNSUPPORTED, "merge_composite: S1+S2=%d > %d", S1 + S2, MAXS);
+    TDGP_CHECK(S1 >= 1 && S2 >= 1 && S1 + S2 <= MAXS_LONG, TDGP_EUNSUPPORTED, "merge_composite: S1+S2=%d > %d", S1 + S2, MAXS_LONG);
     TDGP_CHECK(marcher == 0 || marcher == 1, TDGP_EINVAL, "merge_composite: unknown ray marcher %d", marcher);
     TDGP_FAULT_CHECK("merge_composite");
     if (rays == 0) return TDGP_OK;
@@ -845,9 +983,15 @@ TDGP_API int tdgp_merge_composite(const float* rgbs_coarse, const float* t_coars
     else if (S1 + S2 <= 192)        // BASELINE configs[4]: 96 + 96 samples -- three lane slots and 6.2 KB of scratch per wave instead of four and 8.2 KB
         TDGP_LAUNCH("merge_composite_kernel", merge_composite_kernel<192>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, t_coarse, S1,
                            rgbs_fine, t_fine, S2, rgb, depth, wsum, final_T, perm, fine_perm, rays, marcher, flags, density_bias, cut_threshold);
-    else
+    else if (S1 + S2 <= MAXS)
         TDGP_LAUNCH("merge_composite_kernel", merge_composite_kernel<MAXS>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, t_coarse, S1,
                            rgbs_fine, t_fine, S2, rgb, depth, wsum, final_T, perm, fine_perm, rays, marcher, flags, density_bias, cut_threshold);
+    else if (S1 + S2 <= MAXS_PASS)  // long rays up to 256 + 256: 16.4 KB of scratch per wave, twice the occupancy of the form below
+        TDGP_LAUNCH("merge_composite_kernel", merge_composite_kernel<MAXS_PASS>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, t_coarse, S1,
+                    rgbs_fine, t_fine, S2, rgb, depth, wsum, final_T, perm, fine_perm, rays, marcher, flags, density_bias, cut_threshold);
+    else                            // long rays: 32.8 KB of scratch per wave (last[] holds S1 + 1 <= MAXS_LONG entries)
+        TDGP_LAUNCH("merge_composite_kernel", merge_composite_kernel<MAXS_LONG>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, t_coarse, S1,
+                    rgbs_fine, t_fine, S2, rgb, depth, wsum, final_T, perm, fine_perm, rays, marcher, flags, density_bias, cut_threshold);
     TDGP_LAUNCH_CHECK();
     return TDGP_OK;
 }

@@ -549,6 +549,10 @@ class SynthesisBlocksSequence(torch.nn.Module):
             yield sl, wrap(img_c)
 
 
+# Points one tdgp_triplane_field call takes (csrc/field.hip: B * P <= INT32_MAX / 4): SynthesisNetwork.forward splits larger renders.
+FIELD_POINTS_MAX = (2 ** 31 - 1) // 4
+
+
 class SynthesisNetwork(torch.nn.Module):
     """networks_epigraf.py:134-261.  The depth / camera adaptors exist when the configuration carries them.  `.train()` switches
     to the training-mode forward (no autograd -- gradients are SURVEY.md 8f rank 4): rays at `train_resolution` (patch-wise
@@ -593,6 +597,46 @@ class SynthesisNetwork(torch.nn.Module):
                     white_back=cfg.white_back, max_batch_res=render_opts['max_batch_res'], cut_quantile=render_opts['cut_quantile'],
                     density_bias=render_opts['density_bias'])
 
+    def _render_within_field_bound(self, planes, ray_o, ray_d, opts, w):
+        """self.renderer on [B, R = h*w] rays, split where one call would exceed the field kernel's index bound (B * R * max(S, N) points,
+        csrc/field.hip: tdgp_triplane_field): by images first, then -- for an image too large for one call -- by runs of whole image rows
+        (the field kernel keeps walking 4x4-pixel tiles of each run).  Rays are independent: the result is the unsplit call's, bit for bit.
+        -> (rgb [B,R,C], depth [B,R,1])."""
+        B, R = ray_o.shape[:2]
+        per_ray = max(int(opts['num_proposal_steps']), int(opts['num_fine_steps']))
+        if B * R * per_ray <= FIELD_POINTS_MAX:
+            rgb, depth, _w, _T = self.renderer(planes, self.tri_plane_mlp, ray_o, ray_d, opts)
+            return rgb, depth
+        if float(opts.get('cut_quantile', 0.0)) > 0.0:
+            raise NotImplementedError(f'cut_quantile thresholds over one renderer call; {B} x {R} rays x {per_ray} samples exceed the field kernel\'s '
+                                      f'{FIELD_POINTS_MAX} points per call')
+        if not isinstance(planes, _renderer.HWCPlanes):
+            planes = _renderer.planes_to_hwc(planes)
+        draws = {k: (None if opts.get(k) is None else opts[k].reshape(B, R, -1)) for k in ('u_coarse', 'u_fine', 'n_coarse', 'n_fine')}
+        rgb = depth = None
+        h = R // w
+        imgs = FIELD_POINTS_MAX // (R * per_ray)
+        if imgs >= 1:
+            parts = [(slice(b0, min(b0 + imgs, B)), slice(0, R)) for b0 in range(0, B, imgs)]
+        else:
+            rows = FIELD_POINTS_MAX // (w * per_ray)
+            rows = rows - rows % 4 if rows >= 4 else rows              # whole 4-row tile strips where the bound allows
+            assert rows >= 1, f'one image row of {w} rays x {per_ray} samples exceeds the field kernel\'s {FIELD_POINTS_MAX} points per call'
+            parts = [(slice(b, b + 1), slice(a * w, min(a + rows, h) * w)) for b in range(B) for a in range(0, h, rows)]
+        for bs, rs in parts:
+            o = dict(opts, ray_grid_w=w)
+            for k, t in draws.items():            # the draws of these rays, in the layouts the renderer takes
+                if t is not None:
+                    tc = t[bs, rs].contiguous()
+                    o[k] = tc.reshape(-1, tc.shape[-1]) if k == 'u_fine' else (tc.reshape(tc.shape[0], -1, 1) if k in ('n_coarse', 'n_fine') else tc)
+            rgb_c, depth_c, _w, _T = self.renderer(_renderer.HWCPlanes(planes.t[bs]), self.tri_plane_mlp, ray_o[bs, rs].contiguous(),
+                                                   ray_d[bs, rs].contiguous(), o)
+            if rgb is None:
+                rgb = torch.empty([B, R, rgb_c.shape[-1]], dtype=torch.float32, device=ray_o.device)
+                depth = torch.empty([B, R, 1], dtype=torch.float32, device=ray_o.device)
+            rgb[bs, rs], depth[bs, rs] = rgb_c, depth_c
+        return rgb, depth
+
     @torch.no_grad()
     def compute_densities(self, ws, coords, max_batch_res=32, **block_kwargs):
         """networks_epigraf.py:196-208: sigma at explicit coordinates."""
@@ -606,6 +650,7 @@ class SynthesisNetwork(torch.nn.Module):
         renderer = one autograd node (`renderer.render_autograd`), depth adaptor = conv2d_gradfix + bias_act.  When a camera parameter
         requires a gradient (the camera adaptor applied by the caller, loss.py:76-77) the rays are built by `renderer.camera_rays_autograd`
         and the renderer node returns d(rays) from the field kernel's coordinate gradient; otherwise rays come from the fused kernels."""
+        _renderer.check_grad_sample_counts(self.cfg.num_ray_steps, self.cfg.num_ray_steps)
         render_opts = {**self._default_render_options, **render_opts}
         if (render_opts['return_depth_adapted'] or render_opts['concat_depth']) and self.depth_adaptor is None:
             raise RuntimeError('return_depth_adapted / concat_depth need cfg.depth_adaptor')
@@ -697,7 +742,7 @@ class SynthesisNetwork(torch.nn.Module):
                             oc[k] = tc.reshape(-1, tc.shape[-1]) if k == 'u_fine' else tc
                     rgb[:, rs], depth[:, rs], _w, _T = self.renderer(planes, self.tri_plane_mlp, ray_o[:, rs].contiguous(), ray_d[:, rs].contiguous(), oc)
                 continue
-            rgb_c, depth_c, _w, _T = self.renderer(planes, self.tri_plane_mlp, ray_o[sl], ray_d[sl], o)
+            rgb_c, depth_c = self._render_within_field_bound(planes, ray_o[sl], ray_d[sl], o, w)
             if whole:
                 rgb, depth = rgb_c, depth_c
             else:
@@ -768,6 +813,7 @@ class Generator(torch.nn.Module):
 
     def forward_autograd(self, z, c, camera_params, truncation_psi=1, truncation_cutoff=None, update_emas=False, **synthesis_kwargs):
         """Generator.forward as a differentiable graph: mapping network (eager tensor ops) -> `synthesis.forward_autograd`."""
+        _renderer.check_grad_sample_counts(self.cfg.num_ray_steps, self.cfg.num_ray_steps)
         ws = self.mapping(z, c, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff, update_emas=update_emas)
         return self.synthesis.forward_autograd(ws, camera_params=camera_params, **synthesis_kwargs)
 

@@ -27,7 +27,9 @@ class GraphedGenerator:
             if float(render_opts.get('cut_quantile', 0.0)) > 0.0:
                 raise NotImplementedError('cut_quantile reads a threshold back to the host (torch.quantile -> float): not capturable')
             self.kw['render_opts'] = dict(render_opts)
-        R, S = cfg.img_resolution ** 2, cfg.num_ray_steps
+        syn = G.synthesis                              # the resolution the forward renders at (inference.configure_for_inference may have set it)
+        res = syn.train_resolution if syn.training else syn.test_resolution
+        R, S = res ** 2, cfg.num_ray_steps
         f = dict(dtype=torch.float32, device=dev)
         self.z = torch.zeros([batch, cfg.z_dim], **f)
         self.c = torch.zeros([batch, cfg.c_dim], **f)

@@ -17,6 +17,33 @@ def _tg(cfg, name, default=None):
     return cfg.get(name, default) if isinstance(cfg, dict) else getattr(cfg, name, default)
 
 
+def configure_for_inference(G, img_resolution, ray_step_multiplier, force_whiteback=False, far_plane_offset=0.0):
+    """scripts/inference.py:38-48 on this package's `Generator`, in place: render at `img_resolution` (synthesis.img_resolution and
+    synthesis.test_resolution), `cfg.num_ray_steps` multiplied by `ray_step_multiplier` (the coarse and the fine pass alike), a white
+    background when `force_whiteback`, the far plane (`cfg.ray_end`) moved by `far_plane_offset`, no density noise.  Returns G.
+
+    The eval forward renders up to renderer.MAX_STEPS (512) coarse + 512 fine samples per ray; a larger product is refused here, before
+    anything is changed.  The differentiable forward (`forward_autograd`) keeps its own limit of renderer.MAX_GRAD_SAMPLES (256) merged
+    samples per ray.  A `graphs.GraphedGenerator` captured BEFORE this call keeps the resolution and sample counts it was captured with
+    (the kernels' arguments are frozen in the graph): capture a new one afterwards."""
+    from .renderer import MAX_STEPS
+    cfg, syn = G.cfg, G.synthesis
+    if int(ray_step_multiplier) != ray_step_multiplier or ray_step_multiplier < 1:
+        raise ValueError(f'ray_step_multiplier must be a positive integer, got {ray_step_multiplier!r}')
+    steps = int(cfg.num_ray_steps) * int(ray_step_multiplier)
+    if steps > MAX_STEPS:
+        raise NotImplementedError(f'{cfg.num_ray_steps} ray steps x {ray_step_multiplier} = {steps} samples per ray and pass: the renderer takes at most '
+                                  f'{MAX_STEPS} (beyond it torch\'s summation order of the pdf normaliser is not restated)')
+    assert syn.cfg is cfg, 'G and G.synthesis share one configuration'
+    syn.img_resolution = syn.test_resolution = int(img_resolution)
+    cfg.num_ray_steps = steps
+    if force_whiteback:
+        cfg.white_back = True
+    cfg.ray_end = cfg.ray_end + far_plane_offset
+    syn.nerf_noise_std = 0.0
+    return G
+
+
 def generate(G, ws, camera_params, batch_size=8, **synthesis_kwargs):
     """inference_utils.py:107-126: frames for (ws[i], camera[i]) in chunks of `batch_size`, `noise_mode='const'`, mapped to
     [0, 1] on the CPU; depth (when requested) normalised to [-1, 1] by the ray range first."""

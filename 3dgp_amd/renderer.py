@@ -25,6 +25,27 @@ from . import _lib
 MARCHER_IDS = {'classical': 0, 'mip': 1}
 
 
+# Samples per ray: the eval forward takes up to MAX_STEPS coarse and MAX_STEPS fine samples per pass (csrc/sampling.hip: MAXS_PASS; beyond
+# it torch's summation order of the pdf normaliser is not restated), the gradient path up to MAX_GRAD_SAMPLES merged samples
+# (csrc/render_grad.hip: RG_MAXS).
+MAX_STEPS = 512
+MAX_GRAD_SAMPLES = 256
+
+
+def check_sample_counts(S, N):
+    """The eval forward's limit, checked before any work (the kernels return TDGP_EUNSUPPORTED for the same counts)."""
+    if not (2 <= S <= MAX_STEPS and 0 <= N <= MAX_STEPS):
+        raise _lib.Unsupported(f'ImportanceRenderer: {S} coarse + {N} fine samples per ray; each pass takes 2 ... {MAX_STEPS} '
+                               f'(fine: 0 ... {MAX_STEPS}) samples per ray')
+
+
+def check_grad_sample_counts(S, N):
+    """The gradient path's limit (tdgp_ray_march_grad marches the merged list of S + N samples in one wave's registers)."""
+    if S + N > MAX_GRAD_SAMPLES:
+        raise NotImplementedError(f'gradients through the renderer take at most {MAX_GRAD_SAMPLES} merged samples per ray (S + N = {S} + {N}); '
+                                  f'the eval forward takes up to {MAX_STEPS} + {MAX_STEPS}')
+
+
 def _marcher_flags(opts, marcher):
     flags = 0
     if opts.get('use_inf_depth', True):
@@ -568,6 +589,7 @@ class ImportanceRenderer(torch.nn.Module):
     def forward(self, planes, decoder, ray_origins, ray_directions, rendering_options, return_intermediates=False):
         opts = rendering_options
         marcher = self.ray_marcher_type
+        check_sample_counts(int(opts['num_proposal_steps']), int(opts['num_fine_steps']))
         _lib.require_cuda(ray_origins, 'ray_origins')
         if isinstance(opts.get('ray_start'), str):
             raise NotImplementedError("ray_start='auto' (use_full_box) is never resolved by the reference renderer either (SURVEY.md 8a)")
@@ -715,6 +737,7 @@ class _RenderFunction(torch.autograd.Function):
 def render_autograd(renderer, planes, decoder, ray_origins, ray_directions, rendering_options):
     """(rgb [B,R,3], depth [B,R,1]) with gradients flowing to `planes` ([B,3F,H,W]), the decoder's four tensors and -- when they carry
     a graph (camera_rays_autograd) -- the ray origins / directions."""
+    check_grad_sample_counts(int(rendering_options['num_proposal_steps']), int(rendering_options['num_fine_steps']))
     m = decoder.model
     return _RenderFunction.apply(planes, m[0].weight, m[0].bias, m[1].weight, m[1].bias, renderer, decoder, ray_origins, ray_directions,
                                  rendering_options)

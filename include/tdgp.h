@@ -299,7 +299,8 @@ int     tdgp_triplane_field_grad(const float* planes_hwc, const float* coords, c
                                  float* d_b0, float* d_w1, float* d_b1, float* d_coords, void* workspace, int64_t workspace_bytes,
                                  int B, int64_t P, int F, int H, int W, int hid, float scale, int marcher, tdgp_stream_t stream);
 
-/* Generic marcher on [rays,S,C] colours, [rays,S] densities/depths (any S <= 256, C <= 8).
+/* Generic marcher on [rays,S,C] colours, [rays,S] densities/depths (2 <= S <= 1024: a merged list of up to 512 + 512 samples; C <= 8).
+ * Lists longer than 256 round alpha's exp from fp64; S > 1024 -> TDGP_EUNSUPPORTED.
  * weights: [rays,S] (classical, or mip with inf depth) / [rays,S-1] (mip without); may be NULL.
  * flags: bit0 use_inf_depth, bit1 last_back (classical), bit2 white_back (mip), bit3 clamp_mode relu.
  * cut_threshold: the `cut_quantile` option (tri_plane_renderer.py:324-326, 366-368): activated densities below it are set to 0
@@ -311,18 +312,22 @@ int tdgp_ray_march(const float* colors, const float* densities, const float* dep
 /* Gradient of tdgp_ray_march: autograd through ClassicalRayMarcher / MipRayMarcher2 (:353-398, :299-349).
  * d_rgb [rays,C], d_depth [rays] (may be NULL), d_weights [rays,M] (may be NULL; M as in tdgp_ray_march) ->
  * d_colors [rays,S,C], d_densities [rays,S] (gradient w.r.t. the RAW densities, through softplus / relu).  Depths carry no
- * gradient.  C in {1,3,4}, S <= 256; marcher / flags / density_bias as in tdgp_ray_march. */
+ * gradient.  C in {1,3,4}, S <= 256 (the gradient path's limit: S + N <= 256 merged samples); marcher / flags / density_bias as in
+ * tdgp_ray_march. */
 int tdgp_ray_march_grad(const float* colors, const float* densities, const float* depths, const float* d_rgb,
                         const float* d_depth, const float* d_weights, float* d_colors, float* d_densities,
                         int64_t rays, int S, int C, int marcher, int flags, float density_bias, tdgp_stream_t stream);
 
 /* sample_importance: z [rays,S] (s-space), weights [rays,Wn], u [rays,N] -> samples [rays,N].
- * Optional outputs: inds/below/above int32 [rays,N] (searchsorted right=True, clamped), cdf [rays,Wn-1]. */
+ * Optional outputs: inds/below/above int32 [rays,N] (searchsorted right=True, clamped), cdf [rays,Wn-1].
+ * 4 <= S <= 512, 3 <= Wn <= S, N >= 1: the pdf row (Wn - 2 <= 510 entries) is normalised in torch's CPU summation order, which
+ * is restated up to 575 entries; S > 512 -> TDGP_EUNSUPPORTED. */
 int tdgp_sample_importance(const float* z, const float* weights, const float* u, float* samples,
                            int32_t* inds, int32_t* below, int32_t* above, float* cdf,
                            int64_t rays, int S, int Wn, int N, int marcher, tdgp_stream_t stream);
 
-/* unify_samples: concat + stable sort by depth + gather; perm (int32 [rays,S1+S2]) optional. */
+/* unify_samples: concat + stable sort by depth + gather; perm (int32 [rays,S1+S2]) optional.  S1, S2 >= 1, S1 + S2 <= 1024.
+ * On ties the order is the stable one (the reference's torch.sort(stable=False) orders equal depths its own way beyond 16 elements). */
 int tdgp_unify_samples(const float* d1, const float* c1, const float* s1, int S1,
                        const float* d2, const float* c2, const float* s2, int S2,
                        float* d, float* c, float* s, int32_t* perm, int64_t rays, int C,
@@ -333,7 +338,8 @@ int tdgp_unify_samples(const float* d1, const float* c1, const float* s1, int S1
  * the reference keeps draw order and sorts coarse+fine together afterwards, so the final composite is unchanged, but the
  * second field pass becomes spatially coherent and the merge below is a merge of two sorted lists.
  * Optional: sdist_fine [rays,N] and inds int32 [rays,N] in DRAW order; fine_perm int32 [rays,N]: draw index of sorted slot.
- * cut_threshold as in tdgp_ray_march (here and in tdgp_merge_composite). */
+ * cut_threshold as in tdgp_ray_march (here and in tdgp_merge_composite).  4 <= S <= 512, 1 <= N <= 512 (as tdgp_sample_importance);
+ * beyond -> TDGP_EUNSUPPORTED. */
 int tdgp_importance_from_coarse(const float* rgbs_coarse, const float* sdist, const float* u_fine,
                                 float* tdist_fine, float* sdist_fine, int32_t* inds, int32_t* fine_perm,
                                 int64_t rays, int S, int N, int marcher, int flags, float density_bias,
@@ -342,7 +348,7 @@ int tdgp_importance_from_coarse(const float* rgbs_coarse, const float* sdist, co
 /* Fused chain, step 2: merge coarse+fine by depth (stable, coarse before fine on ties), march in t-space.
  * rgbs_* [rays,S*,4], t_* [rays,S*] (any order; ascending lists take a fast path) -> rgb [rays,3], depth [rays],
  * wsum [rays], final_T [rays]; perm optional int32 [rays,S1+S2] = index into the concatenation [coarse ; fine in draw
- * order] (fine_perm, optional, maps the fine list's slots back to draw order; NULL = identity). */
+ * order] (fine_perm, optional, maps the fine list's slots back to draw order; NULL = identity).  S1, S2 >= 1, S1 + S2 <= 1024. */
 int tdgp_merge_composite(const float* rgbs_coarse, const float* t_coarse, int S1,
                          const float* rgbs_fine, const float* t_fine, int S2,
                          float* rgb, float* depth, float* wsum, float* final_T, int32_t* perm,
@@ -355,7 +361,9 @@ int tdgp_merge_composite(const float* rgbs_coarse, const float* t_coarse, int S1
  * final_T [B*R] (may be NULL).  ray_w > 0: the R rays are a [R/ray_w, ray_w] image (4x4-pixel tiles, same results); scale = box_size / 2;
  * flags as in tdgp_ray_march; no cut_quantile / density noise / intermediates (those go through the staged entry points above).
  * Same kernels, same bits as tdgp_sample_stratified + tdgp_triplane_field + tdgp_importance_from_coarse + tdgp_triplane_field +
- * tdgp_merge_composite.  workspace: tdgp_render_fused_workspace_bytes(B, R, S, N) bytes, 16-byte aligned, caller-owned. */
+ * tdgp_merge_composite.  workspace: tdgp_render_fused_workspace_bytes(B, R, S, N) bytes, 16-byte aligned, caller-owned.
+ * Limits: 4 <= S <= 512, 1 <= N <= 512 (tdgp_importance_from_coarse), and B * R * max(S, N) <= INT32_MAX / 4 points per field pass
+ * (tdgp_triplane_field): the caller splits larger renders by images or runs of image rows. */
 int64_t tdgp_render_fused_workspace_bytes(int B, int64_t R, int S, int N);
 int     tdgp_render_fused(const float* planes_hwc, const float* w0, const float* b0, const float* w1, const float* b1,
                           const float* ray_o, const float* ray_d, const float* u_coarse, const float* u_fine,

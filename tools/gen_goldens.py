@@ -13,7 +13,9 @@ oracle and to the HIP kernels.  Integer intermediates the reference never return
 sort permutation) are captured by wrapping torch.searchsorted / torch.sort.
 
 Run:  python tools/gen_goldens.py        (needs /root/reference; writes tests/golden/)
+      python tools/gen_goldens.py sampling_long e2e_long    (selected files only: the names after gen_ / the e2e groups)
 """
+import hashlib
 import importlib
 import os
 import sys
@@ -573,6 +575,69 @@ def gen_sampling_hot():
             arrays[f'{tag}_sdist_fine'] = npy(sf)
             arrays[f'{tag}_inds'] = npy(cap.inds[0]).astype(np.int16)
     save('sampling_hot', **arrays)
+
+
+def unify_long_payload(lead, S1, S2):
+    """The colours / densities that ride along in sampling_long's unify vectors: regenerated from a seed by the test
+    (tests/test_long_rays.py keeps the same function); only the depths decide the permutation."""
+    rs = np.random.RandomState(S1 * 7 + S2)
+    return (rs.randn(*lead, S1, 3).astype(np.float32), rs.randn(*lead, S1, 1).astype(np.float32),
+            rs.randn(*lead, S2, 3).astype(np.float32), rs.randn(*lead, S2, 1).astype(np.float32))
+
+
+def gen_sampling_long():
+    """Long rays (up to 512 + 512 samples, scripts/inference.py:44-46 with ray_step_multiplier): sample_importance at S = 192, 256, 384,
+    512 in the style of gen_sampling_hot (pdf rows of 190 ... 510 elements: up to 63 whole 8-lane vectors of torch's CPU sum, still below
+    its first cascade level at 576), 16 rays each; unify_samples on 256 + 256 and 512 + 512 samples, 8 rays each, once without ties and
+    once with ties across and inside the lists (the reference's order on ties is recorded, not assumed).  The colours and densities of the unify vectors are not stored (unify_long_payload); a
+    sha256 of the reference's gathered outputs is."""
+    g = np.random.RandomState(77)
+    arrays = {}
+    for marcher in ('classical', 'mip'):
+        rend = ref_tpr.ImportanceRenderer(marcher)
+        for S in (192, 256, 384, 512):
+            B, R = 1, 16
+            u = g.rand(B, R, S, 1).astype(np.float32)
+            with PatchedRNG(rand_like=[T(u)]):
+                sd = rend.sample_stratified(torch.zeros(B, R, 3), 0.0, 1.0, S)
+            sig = np.maximum(g.randn(B, R, S, 1) * 4.0 - 1.0, 0).astype(np.float32) * (g.rand(B, R, S, 1) > 0.5)
+            alpha = 1.0 - np.exp(-sig * (1.0 / S) * 20.0)
+            Tr = np.cumprod(np.concatenate([np.ones_like(alpha[:, :, :1]), 1.0 - alpha[:, :, :-1] + 1e-10], 2), 2)
+            wts = (alpha * Tr).astype(np.float32)
+            Wn = S if marcher == 'classical' else S - 1
+            wts = wts[:, :, :Wn]
+            u2 = g.rand(B * R, S).astype(np.float32)
+            with PatchedRNG(rand=[T(u2)]), Capture() as cap:
+                sf = rend.sample_importance(sd, T(wts), S)
+            tag = f'{marcher}{S}'
+            arrays[f'{tag}_sdist'], arrays[f'{tag}_weights'], arrays[f'{tag}_u_fine'] = npy(sd), wts, u2
+            arrays[f'{tag}_sdist_fine'] = npy(sf)
+            arrays[f'{tag}_inds'] = npy(cap.inds[0]).astype(np.int16)
+    # unify_samples: tie-free lists (the permutation is then THE sorted order), and lists with ties across and inside them.  On ties the
+    # reference's order is torch's CPU sort with stable=False (torch 2.10: an introsort beyond 16 elements), not the stable order.
+    rend = ref_tpr.ImportanceRenderer('classical')
+    for S in (256, 512):
+        for ties in (False, True):
+            B, R = 1, 8
+            d1 = np.sort(g.uniform(0.75, 1.25, (B, R, S, 1)).astype(np.float32), axis=2)
+            d2 = g.uniform(0.75, 1.25, (B, R, S, 1)).astype(np.float32)    # fine samples in draw order
+            if ties:
+                d1[:, :, 11] = d1[:, :, 10]                               # ties inside the (ascending) coarse list
+                d2[:, :, 0:S:7] = d1[:, :, 0:S:7]                         # ties across the lists
+                d2[:, :, 5] = d2[:, :, 2]                                 # ties inside the fine list
+            else:
+                cat = np.concatenate([d1, d2], 2)[..., 0]
+                assert all(len(np.unique(row)) == row.size for row in cat.reshape(-1, 2 * S)), 'draw a tie-free list'
+            c1, s1, c2, s2 = unify_long_payload((B, R), S, S)
+            with Capture() as cap:
+                d, c, s = rend.unify_samples(T(d1), T(c1), T(s1), T(d2), T(c2), T(s2))
+            h = hashlib.sha256()
+            for t in (d, c, s):
+                h.update(np.ascontiguousarray(npy(t), dtype=np.float32).tobytes())
+            tag = f'un{S}' + ('_ties' if ties else '')
+            arrays.update({f'{tag}_d1': d1, f'{tag}_d2': d2, f'{tag}_perm': npy(cap.perm[0])[..., 0].astype(np.int16),
+                           f'{tag}_out_sha256': np.frombuffer(h.digest(), dtype=np.uint8)})
+    save('sampling_long', **arrays)
 
 
 def gen_marchers():
@@ -1608,6 +1673,35 @@ def main():
     gen_cut_chunked()
     gen_e2e_all()
     gen_e2e_full_all()
+    gen_sampling_long()
+    gen_e2e_long()
+
+
+def gen_e2e_long():
+    """The reference's whole G.synthesis at config_tiny (16^2 image, 32^2 planes) with num_ray_steps = 384 (384 + 384 samples per ray):
+    gen_e2e's arrays, then only what tests/test_long_rays.py reads is kept -- image and depth (with the reference's re-run and float64
+    figures), the integer rows `inds` / `perm`, and the importance stage's input weights; its coarse depths (which regenerate from the
+    draws) and its fine samples are kept as sha256 digests.  The draws regenerate from the seed (weights.synthetic_inputs); their sha256
+    is stored."""
+    cfg = tdgp.config.config_tiny()
+    cfg.num_ray_steps = 384
+    seed = 51
+    gen_e2e('e2e_long', cfg, batch=1, seed=seed, keep_intermediates=True)
+    path = os.path.join(OUT, 'e2e_long.npz')
+    full = dict(np.load(path))
+    keep = ['z', 'c', 'ws', 'seed', 'img', 'depth', 'img_alt', 'depth_alt', 'img_f64', 'depth_f64', 'imp_weights']
+    arrays = {k: full[k] for k in keep}
+    for k in ('imp_sdist', 'imp_sdist_fine'):           # 384 KB each: the stratified samples regenerate from the draws, the fine samples are compared by hash
+        arrays[k + '_sha256'] = np.frombuffer(hashlib.sha256(np.ascontiguousarray(full[k], dtype=np.float32).tobytes()).digest(), dtype=np.uint8)
+    arrays.update({k: v for k, v in full.items() if k.startswith('cam_')})
+    arrays['inds'] = full['inds'].astype(np.int16)
+    arrays['perm'] = full['perm'].astype(np.int16)
+    h = hashlib.sha256()
+    for k in ('u_coarse', 'u_fine'):
+        h.update(np.ascontiguousarray(full[k], dtype=np.float32).tobytes())
+    arrays['draws_sha256'] = np.frombuffer(h.digest(), dtype=np.uint8)
+    os.remove(path)
+    save('e2e_long', **arrays)
 
 
 def gen_e2e_all():
