@@ -1,0 +1,199 @@
+"""Shape extraction (scripts/extract_geometry.py): the reference's voxel grid built on the device, densities evaluated in bounded slabs
+through the field kernel, marching cubes as HIP kernels that leave an indexed mesh on the device, and the three file writers.
+
+The reference materialises res^3 x 3 coordinates on the host, gets a [1, res^3, 4]-backed tensor back, copies the grid to the host and
+hands it to `mcubes` / `trimesh` / `mrcfile`.  Here only the mesh (and, for .mrc, the cropped grid) crosses to the host.
+
+Conventions of `marching_cubes` (csrc/geometry.hip, csrc/mc_table.inc): a corner is inside when its value is >= the threshold; vertices
+are in index units of the volume, axis order (d, h, w) as `mcubes` returns them; every sign-changing grid edge carries ONE vertex, ordered by
+the edge's lower grid point then axis; triangles are ordered by cell then table order and wound so that their normals point toward lower
+density (read (d, h, w) as a right-handed (x, y, z): a blob of high density has positive signed volume).  PyMCubes' own vertex / triangle
+ORDER is not reproduced.
+"""
+import collections
+import struct
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import renderer as _renderer
+
+Shape = collections.namedtuple('Shape', ['vertices', 'triangles', 'sigma'])
+FIELD_POINTS_MAX = (2 ** 31 - 1) // 4          # points one tdgp_triplane_field call takes (csrc/field.hip)
+
+
+def _grid_constants(resolution, voxel_origin, cube_size):
+    """extract_geometry.py:58-59,72-74 in double, each rounded to fp32 once (a Python scalar meeting an fp32 tensor): voxel_size and
+    the offsets of output columns (x, y, z) = voxel_origin[(2, 1, 0)] - cube_size / 2."""
+    origin = np.array(voxel_origin, dtype=np.float64) - cube_size / 2.0
+    voxel_size = cube_size / (resolution - 1)
+    return float(voxel_size), float(origin[2]), float(origin[1]), float(origin[0])
+
+
+def _voxel_coords_into(out, i0, resolution, consts):
+    with torch.cuda.device(out.device):
+        _lib.call('tdgp_voxel_coords', out.data_ptr(), int(i0), out.shape[0], int(resolution), *consts, _lib.stream_of(out))
+    return out
+
+
+def create_voxel_coords(resolution=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=2.0, batch_size=1, device='cuda'):
+    """extract_geometry.py:55-76 on the device, bit for bit (sheared grid and inexact index conversion included): [batch_size, resolution^3, 3]."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise RuntimeError(f'create_voxel_coords builds the grid on the GPU (got device {device}); the HIP ops have no CPU path')
+    out = torch.empty([int(resolution) ** 3, 3], dtype=torch.float32, device=device)
+    _voxel_coords_into(out, 0, resolution, _grid_constants(resolution, voxel_origin, cube_size))
+    return out.unsqueeze(0) if batch_size == 1 else out.repeat(batch_size, 1, 1)
+
+
+@torch.no_grad()
+def density_grid(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=0.3, slab_points=2 ** 22, noise_mode='const'):
+    """Raw sigma of `G.synthesis.compute_densities(ws, create_voxel_coords(volume_res, voxel_origin, cube_size))` as [B, res, res, res] fp32:
+    the backbone runs once, then slabs of `slab_points` grid indices go through tdgp_voxel_coords and the field kernel (coords mode), and
+    their sigma column is copied into the grid.  Temporaries are O(slab_points); the grid itself is the only O(res^3) tensor."""
+    syn = G.synthesis
+    _lib.require_cuda(ws, 'ws')
+    res = int(volume_res)
+    total = res ** 3
+    slab = int(min(max(int(slab_points), 1), total, FIELD_POINTS_MAX))
+    planes = _renderer.planes_to_hwc(syn.tri_plane_decoder(ws[:, :syn.tri_plane_decoder.num_ws], hwc=True, noise_mode=noise_mode))
+    mlp, scale = syn.tri_plane_mlp, syn.cfg.cube_scale
+    fused = _renderer.fused_form(mlp)
+    params = _renderer._mlp_params(mlp) if fused else None
+    consts = _grid_constants(res, voxel_origin, cube_size)
+    B = planes.t.shape[0]
+    grid = torch.empty([B, total], dtype=torch.float32, device=ws.device)
+    coords = torch.empty([slab, 3], dtype=torch.float32, device=ws.device)
+    for i0 in range(0, total, slab):
+        n = min(slab, total - i0)
+        c = _voxel_coords_into(coords[:n], i0, res, consts).unsqueeze(0)
+        for b in range(B):
+            pb = _renderer.HWCPlanes(planes.t[b:b + 1])
+            rgbs = _renderer._field(pb, params, scale, coords=c) if fused else _renderer._field_eager(pb, mlp, scale, coords=c)
+            grid[b, i0:i0 + n] = rgbs[0, :, -1]
+    return grid.reshape(B, res, res, res)
+
+
+
+def crop_reference(res):
+    """The three slices of extract_geometry.py:33, `sigma[res//8:-res//8, res//2:, :-res//3]`, with Python's floor semantics for the
+    negative bounds (`-res//8` is floor(-res / 8), not -(res // 8))."""
+    res = int(res)
+    return slice(res // 8, -res // 8), slice(res // 2, None), slice(None, -res // 3)
+
+
+def marching_cubes(volume, thresh):
+    """Marching cubes of a [D,H,W] volume at `thresh` on the device -> (vertices [V,3] fp32, triangles [T,3] int32), device tensors (module
+    docstring for the conventions).  The only host read-back is the pair (V, T) that sizes the outputs."""
+    _lib.require_cuda(volume, 'volume')
+    if volume.ndim != 3:
+        raise ValueError(f'marching_cubes takes a [D,H,W] volume, got {tuple(volume.shape)}')
+    vol = _lib.f32c(volume)
+    D, H, W = (int(s) for s in vol.shape)
+    dev = vol.device
+    empty = lambda: (torch.empty([0, 3], dtype=torch.float32, device=dev), torch.empty([0, 3], dtype=torch.int32, device=dev))   # noqa: E731
+    if min(D, H, W) < 2:
+        return empty()
+    need = int(_lib.load().tdgp_mcubes_workspace_bytes(D, H, W))
+    if need < 0:
+        raise _lib.Unsupported(f'marching_cubes: a volume of {D}x{H}x{W} points exceeds the 2^31 - 1 this build indexes; extract it in parts')
+    ws = torch.empty([need], dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = _lib.stream_of(vol)
+        _lib.call('tdgp_mcubes_count', vol.data_ptr(), D, H, W, float(thresh), ws.data_ptr(), need, stream)
+        V, T = (int(x) for x in ws[:16].view(torch.int64).cpu())
+        if V == 0 or T == 0:
+            return empty()
+        verts = torch.empty([V, 3], dtype=torch.float32, device=dev)
+        tris = torch.empty([T, 3], dtype=torch.int32, device=dev)
+        _lib.call('tdgp_mcubes_emit', vol.data_ptr(), D, H, W, float(thresh), ws.data_ptr(), need, verts.data_ptr(), V, tris.data_ptr(), T, stream)
+    return verts, tris
+
+
+@torch.no_grad()
+def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=0.3, thresh_value=25.0, crop='reference', normalize=True,
+                     slab_points=2 ** 22, noise_mode='const'):
+    """scripts/extract_geometry.py:26-42 per sample of `ws`: density grid -> crop -> marching cubes -> (optionally) scale.  Returns a list of
+    Shape(vertices [V,3] fp32, triangles [T,3] int32, sigma [D,H,W] fp32 -- the cropped grid), all on the device.
+    crop: 'reference' (extract_geometry.py:33), None, or three slices.  normalize: divide the vertices by the length of their bounding-box
+    diagonal (`mesh.apply_scale(1.0 / mesh.scale)`, extract_geometry.py:42 -- trimesh's `scale`; no translation)."""
+    if crop == 'reference':
+        crop = crop_reference(volume_res)
+    elif crop is not None:
+        crop = tuple(crop)
+        if len(crop) != 3 or not all(isinstance(s, slice) for s in crop):
+            raise ValueError("crop must be 'reference', None or three slices")
+    out = []
+    for b in range(ws.shape[0]):               # one sample's grid alive at a time, as the reference loops
+        sigma = density_grid(G, ws[b:b + 1], volume_res, voxel_origin, cube_size, slab_points, noise_mode)[0]
+        if crop is not None:
+            sigma = sigma[crop]
+        verts, tris = marching_cubes(sigma, thresh_value)
+        if normalize and verts.shape[0] > 0:
+            diag = (verts.max(dim=0).values - verts.min(dim=0).values).norm()
+            if float(diag) > 0:
+                verts = verts / diag
+        out.append(Shape(verts, tris, sigma))
+    return out
+
+
+# ---- writers: host side, numpy only --------------------------------------------------------------------------------------------------
+
+def _host(a, dtype):
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def save_obj(path, vertices, triangles):
+    """Wavefront .obj: `v x y z` lines (shortest text that reads back as the same fp32) and 1-based `f a b c` lines."""
+    v, f = _host(vertices, np.float32).reshape(-1, 3), _host(triangles, np.int32).reshape(-1, 3)
+    with open(path, 'w') as fh:
+        fh.write(''.join(f'v {np.format_float_positional(x, unique=True, trim="-")} {np.format_float_positional(y, unique=True, trim="-")} '
+                         f'{np.format_float_positional(z, unique=True, trim="-")}\n' for x, y, z in v))
+        fh.write(''.join(f'f {a + 1} {b + 1} {c + 1}\n' for a, b, c in f.tolist()))
+
+
+def save_ply(path, vertices, triangles):
+    """Binary little-endian .ply: float32 x y z per vertex, then per face a uchar count (3) and three int32 indices."""
+    v, f = _host(vertices, '<f4').reshape(-1, 3), _host(triangles, '<i4').reshape(-1, 3)
+    header = ('ply\nformat binary_little_endian 1.0\n'
+              f'element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n'
+              f'element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n')
+    faces = np.empty(len(f), dtype=[('n', 'u1'), ('i', '<i4', (3,))])
+    faces['n'], faces['i'] = 3, f
+    with open(path, 'wb') as fh:
+        fh.write(header.encode('ascii'))
+        fh.write(v.tobytes())
+        fh.write(faces.tobytes())
+
+
+def save_mrc(path, volume):
+    """MRC2014 map of a [D,H,W] fp32 volume, what `mrcfile.new_mmap(..., mrc_mode=2)` + `mrc.data[:] = sigma` leaves (extract_geometry.py:50-51):
+    1024-byte header, mode 2, nx / ny / nz = W / H / D (x is the fastest axis), mx / my / mz and the unit cell equal to the dimensions
+    (1 A voxels, 90 degree angles), mapc / mapr / maps = 1 / 2 / 3, dmin / dmax / dmean / rms filled in, ispg 1, nsymbt 0, nversion 20140,
+    'MAP ' at byte 208, little-endian machine stamp 0x44 0x44 0 0, no labels, then the data.
+    Written from the public format description (Cheng et al. 2015, J. Struct. Biol. 192:146); neither `mrcfile` nor ChimeraX was
+    available to confirm that they read it."""
+    vol = _host(volume, '<f4')
+    if vol.ndim != 3:
+        raise ValueError(f'save_mrc takes a [D,H,W] volume, got {vol.shape}')
+    D, H, W = vol.shape
+    hdr = bytearray(1024)
+    v64 = vol.astype(np.float64)
+    dmean = float(v64.mean()) if vol.size else 0.0
+    rms = float(np.sqrt(((v64 - dmean) ** 2).mean())) if vol.size else 0.0
+    struct.pack_into('<10i', hdr, 0, W, H, D, 2, 0, 0, 0, W, H, D)                  # nx ny nz mode nxstart nystart nzstart mx my mz
+    struct.pack_into('<6f', hdr, 40, float(W), float(H), float(D), 90.0, 90.0, 90.0)    # cella, cellb
+    struct.pack_into('<3i', hdr, 64, 1, 2, 3)                                       # mapc mapr maps
+    struct.pack_into('<3f', hdr, 76, float(vol.min()) if vol.size else 0.0, float(vol.max()) if vol.size else 0.0, dmean)
+    struct.pack_into('<2i', hdr, 88, 1, 0)                                          # ispg, nsymbt
+    struct.pack_into('<i', hdr, 108, 20140)                                         # nversion
+    hdr[208:212] = b'MAP '
+    hdr[212:216] = bytes([0x44, 0x44, 0x00, 0x00])
+    struct.pack_into('<f', hdr, 216, rms)
+    struct.pack_into('<i', hdr, 220, 0)                                             # nlabl
+    with open(path, 'wb') as fh:
+        fh.write(bytes(hdr))
+        fh.write(vol.tobytes())

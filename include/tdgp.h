@@ -375,6 +375,30 @@ int     tdgp_render_fused(const float* planes_hwc, const float* w0, const float*
 /* [B, h*w, 3] ray colours -> [B,3,h,w] image (networks_epigraf.py:242). */
 int tdgp_rays_to_image(const float* rgb, float* img, int B, int hw, tdgp_stream_t stream);
 
+/* create_voxel_coords (scripts/extract_geometry.py:55-76; torch CPU ops over the whole grid there): the coordinates of grid indices
+ * [i0, i0 + n) of a res^3 grid -> coords [n,3], bit for bit the reference's fp32 chain: the index converted to fp32 (inexact above 2^24),
+ * y = (idx / res) % res and x = ((idx / res) / res) % res as UNFLOORED fp32 divisions, z from the integer remainder, then
+ * `* voxel_size + origin` in two roundings.  voxel_size = cube_size / (res - 1) and origin_{x,y,z} = voxel_origin[{2,1,0}] - cube_size / 2
+ * are computed by the caller in double and rounded once.  2 <= res <= 2048. */
+int tdgp_voxel_coords(float* coords, int64_t i0, int64_t n, int res, float voxel_size, float origin_x, float origin_y, float origin_z,
+                      tdgp_stream_t stream);
+
+/* Marching cubes on a contiguous fp32 volume [D,H,W] (mcubes.marching_cubes on a host copy of the grid, scripts/extract_geometry.py:38-40).
+ * tdgp_mcubes_count classifies every cell (corner inside <=> value >= thresh), counts triangles and owned sign-changing edges, scans
+ * the per-block sums in a launch of its own and leaves the totals as two int64 (V, T) at the START of the workspace -- the one pair of
+ * numbers the caller reads back, to size the outputs.  tdgp_mcubes_emit (same volume, threshold and workspace) then writes
+ * vertices [V,3] fp32 in index units, axis order (d, h, w), each at p0 + (thresh - v0) / (v1 - v0) along its edge, and
+ * triangles [T,3] int32 into them: one shared vertex per sign-changing edge, normals toward lower values.
+ * Order: vertices by owning grid point (the edge's lower end) then axis, triangles by cell then table order (csrc/mc_table.inc,
+ * written by tools/gen_mc_table.py); no atomics, identical bytes from run to run; no kernel waits on another block.
+ * workspace: tdgp_mcubes_workspace_bytes(D, H, W) bytes (about 6 per grid point; -1 for a shape it refuses), 16-byte aligned, caller-owned.
+ * Every side >= 2, D * H * W <= INT32_MAX; V >= 2^29 or T > INT32_MAX -> TDGP_EUNSUPPORTED.  Writes never pass the V / T given. */
+int64_t tdgp_mcubes_workspace_bytes(int D, int H, int W);
+int     tdgp_mcubes_count(const float* volume, int D, int H, int W, float thresh, void* workspace, int64_t workspace_bytes,
+                          tdgp_stream_t stream);
+int     tdgp_mcubes_emit(const float* volume, int D, int H, int W, float thresh, void* workspace, int64_t workspace_bytes,
+                         float* vertices, int64_t V, int32_t* triangles, int64_t T, tdgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

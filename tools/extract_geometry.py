@@ -1,0 +1,107 @@
+#!/usr/bin/env python3
+"""Extract shapes from a generator: density grid -> marching cubes on the GPU -> .mrc / .obj / .ply (scripts/extract_geometry.py).
+
+    python tools/extract_geometry.py --ckpt exported_dir/ --seeds 0,1,5-7 --save-obj
+
+`--ckpt` is a directory written by tools/export_reference_checkpoint.py.  The options carry the keys and defaults of the reference's
+configs/scripts/extract_geometry.yaml; exactly one of --seeds / --num-seeds must be given.  Files are named `{seed:04d}` or, with
+--classes, `c{class:04d}-s{seed:04d}`.  `num_ply_points` (unused by the reference script too) has no counterpart.
+"""
+import argparse
+import importlib
+import os
+import re
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def parse_range(s):
+    """'1,2,5-7' -> [1, 2, 5, 6, 7] (scripts/inference.py:166-180)."""
+    out = []
+    for p in s.split(','):
+        m = re.match(r'^(\d+)-(\d+)$', p)
+        if m:
+            out.extend(range(int(m.group(1)), int(m.group(2)) + 1))
+        else:
+            out.append(int(p))
+    return out
+
+
+def _flag(parser, name, default, help):
+    parser.add_argument(f'--{name}', dest=name.replace('-', '_'), action=argparse.BooleanOptionalAction, default=default, help=help)
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    p.add_argument('--seeds', type=parse_range, default=None, help="seeds, e.g. '0,1,5-7'")
+    p.add_argument('--num-seeds', type=int, default=None, help='use seeds 0 .. N-1')
+    p.add_argument('--classes', type=parse_range, default=None, help='class indices (conditional generators); every seed is extracted under every class')
+    p.add_argument('--cube-size', type=float, default=0.3)
+    p.add_argument('--volume-res', type=int, default=256)
+    p.add_argument('--voxel-origin', type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=('X', 'Y', 'Z'))
+    p.add_argument('--output-dir', default='shapes')
+    p.add_argument('--thresh-value', type=float, default=25.0)
+    p.add_argument('--truncation-psi', type=float, default=0.7)
+    _flag(p, 'verbose', True, 'print one line per shape')
+    _flag(p, 'save-mrc', True, 'write the cropped density grid as an MRC2014 map (for UCSF ChimeraX)')
+    _flag(p, 'save-obj', False, 'write the mesh as Wavefront .obj')
+    _flag(p, 'save-ply', False, 'write the mesh as binary .ply')
+    p.add_argument('--ckpt', default=None, metavar='DIR', help='directory written by tools/export_reference_checkpoint.py')
+    return p
+
+
+def parse_args(argv=None):
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.seeds is None and args.num_seeds is None:
+        p.error('You must specify either `num_seeds` or `seeds`')
+    if args.seeds is not None and args.num_seeds is not None:
+        p.error('You cannot specify both `num_seeds` and `seeds`')
+    return args
+
+
+def sample_names(seeds, classes):
+    return [f'{s:04d}' for s in seeds] if classes is None else [f'c{c:04d}-s{s:04d}' for c in classes for s in seeds]
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if args.ckpt is None:
+        raise SystemExit('--ckpt DIR is required (a directory written by tools/export_reference_checkpoint.py)')
+    if REPO not in sys.path:
+        sys.path.insert(0, REPO)
+    import torch
+    tdgp = importlib.import_module('3dgp_amd')
+    geometry = tdgp.geometry
+    torch.manual_seed(42)                                       # set_seed(42): "to fix non-z randomization"
+    seeds = args.seeds if args.num_seeds is None else list(range(args.num_seeds))
+    cfg, sd = tdgp.weights.load_exported(args.ckpt)
+    G = tdgp.generator.Generator(cfg)
+    G.load_numpy_state_dict(sd)
+    G = G.to('cuda').eval()
+    ws, _z, _c = tdgp.inference.sample_ws_from_seeds(G, seeds, truncation_psi=args.truncation_psi, device='cuda', classes=args.classes)
+    names = sample_names(seeds, args.classes)
+    os.makedirs(args.output_dir, exist_ok=True)
+    need_mesh = args.save_obj or args.save_ply
+    for name, w in zip(names, ws.split(1, dim=0)):
+        if need_mesh:
+            shape = geometry.extract_geometry(G, w, volume_res=args.volume_res, voxel_origin=args.voxel_origin, cube_size=args.cube_size,
+                                              thresh_value=args.thresh_value, crop='reference', normalize=True)[0]
+            sigma = shape.sigma
+            if args.save_obj:
+                geometry.save_obj(os.path.join(args.output_dir, f'{name}.obj'), shape.vertices, shape.triangles)
+            if args.save_ply:
+                geometry.save_ply(os.path.join(args.output_dir, f'{name}.ply'), shape.vertices, shape.triangles)
+            if args.verbose:
+                print(f'{name}: {shape.vertices.shape[0]} vertices, {shape.triangles.shape[0]} triangles')
+        else:
+            sigma = geometry.density_grid(G, w, args.volume_res, args.voxel_origin, args.cube_size)[0][geometry.crop_reference(args.volume_res)]
+            if args.verbose:
+                print(f'{name}: density grid {tuple(sigma.shape)}')
+        if args.save_mrc:
+            geometry.save_mrc(os.path.join(args.output_dir, f'{name}.mrc'), sigma)
+
+
+if __name__ == '__main__':
+    main()

@@ -1704,6 +1704,63 @@ def gen_e2e_long():
     save('e2e_long', **arrays)
 
 
+def _reference_create_voxel_coords():
+    """scripts/extract_geometry.py imports hydra / omegaconf at module level; only the definition of `create_voxel_coords` is compiled out of
+    the file (at generation time, nothing of it is kept) and run with torch / numpy as its globals."""
+    import ast
+    path = os.path.join(REF, 'scripts', 'extract_geometry.py')
+    tree = ast.parse(open(path).read(), filename=path)
+    fn = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == 'create_voxel_coords')
+    ns = dict(torch=torch, np=np)
+    exec(compile(ast.Module(body=[fn], type_ignores=[]), path, 'exec'), ns)
+    return ns['create_voxel_coords']
+
+
+GEOMETRY_GOLDEN = dict(origin=(0.05, -0.1, 0.2), coord_cases=((8, 2.0), (21, 0.3)), strip_res=300, strip_len=4096, strip_cube=0.3,
+                       density_res=32, density_cube=0.6, seed=61)
+
+
+def gen_geometry():
+    """tests/golden/geometry.npz: the reference's voxel grids (two whole grids and the END of a grid whose index count passes 2^24, all
+    with an asymmetric origin) and its densities on a 32^3 grid (config_tiny): fp32 as shipped and the reference itself in float64."""
+    ref_coords = _reference_create_voxel_coords()
+    gg = GEOMETRY_GOLDEN
+    origin = list(gg['origin'])
+    arrays = dict(voxel_origin=np.array(origin, dtype=np.float64))
+    for res, cube in gg['coord_cases']:
+        arrays[f'coords_r{res}'] = npy(ref_coords(res, origin, cube, 1))[0]
+        arrays[f'coords_r{res}_cube'] = np.array(cube, dtype=np.float64)
+    res, n = gg['strip_res'], gg['strip_len']
+    assert res ** 3 > 2 ** 24
+    arrays['strip_coords'] = npy(ref_coords(res, origin, gg['strip_cube'], 1))[0, -n:]
+    arrays['strip_spec'] = np.array([res, res ** 3 - n, n], dtype=np.int64)
+    arrays['strip_cube'] = np.array(gg['strip_cube'], dtype=np.float64)
+
+    cfg = tdgp.config.config_tiny()
+    seed = gg['seed']
+    sd = tdgp.weights.random_state_dict(cfg, seed=seed, exercise_all=True)
+    inp = tdgp.weights.synthetic_inputs(cfg, batch=1, seed=seed + 1)
+    G = build_ref_generator(cfg, sd)
+    res, cube = gg['density_res'], gg['density_cube']
+    with torch.no_grad():
+        ws = G.mapping(T(inp['z']), T(inp['c']))
+        coords = ref_coords(res, origin, cube, 1)
+        sigma = G.synthesis.compute_densities(ws, coords, noise_mode='const')
+        G64 = build_ref_generator(cfg, sd).double()
+        torch.set_default_dtype(torch.float64)
+        f32 = torch.float32
+        torch.float32 = torch.float64                   # as in gen_e2e: the reference names its working precision `torch.float32`
+        try:
+            sigma64 = G64.synthesis.compute_densities(ws.double(), coords.double(), noise_mode='const')
+        finally:
+            torch.float32 = f32
+            torch.set_default_dtype(torch.float32)
+        assert sigma.dtype == torch.float32 and sigma64.dtype == torch.float64
+    arrays.update(z=inp['z'], c=inp['c'], ws=npy(ws), seed=np.array([seed, 1], dtype=np.int64), density_spec=np.array([res], dtype=np.int64),
+                  density_cube=np.array(cube, dtype=np.float64), sigma=npy(sigma).reshape(res, res, res), sigma_f64=npy(sigma64).reshape(res, res, res))
+    save('geometry', **arrays)
+
+
 def gen_e2e_all():
     gen_e2e('e2e_tiny', tdgp.config.config_tiny(), batch=2, seed=21, keep_intermediates=True)
     gen_e2e('e2e_mid', tdgp.config.config_mid(), batch=2, seed=31, keep_intermediates=False)
