@@ -2725,711 +2725,6 @@ __global__ __launch_bounds__(256) void style_affine_kernel(const float* __restri
     if (lane_id() == 0) styles[(int64_t)obase + (int64_t)b * olen + oidx] = (acc + abias[row]) * scale[row];
 }
 
-inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
-
-struct PackInfo { int T, KC, CoutP, nchunks, niter16, nch32, nch8, nch4, nsl64; int64_t wp_floats, wsq_floats, wsplit_floats, wbf_floats, wino_floats, wino4_floats; };
-inline PackInfo pack_info(int Cout, int Cin, int k) {
-    PackInfo pi;
-    pi.T = k * k;
-    pi.KC = KC3;
-    pi.CoutP = round_up(Cout, 4);
-    pi.nchunks = round_up((Cin + pi.KC - 1) / pi.KC, k == 1 ? 16 : 2);      // zero-padded to whole K iterations (1x1 kernels stage up to 16 chunks)
-    pi.wp_floats = (int64_t)pi.nchunks * pi.T * pi.KC * pi.CoutP;
-    pi.wsq_floats = (int64_t)Cin * pi.CoutP;
-    pi.niter16 = (Cin + 15) / 16;
-    pi.wsplit_floats = k == 3 ? (int64_t)pi.niter16 * 9 * 3 * pi.CoutP * 8 : 0;      // split-bf16 copy of the 3x3 weights (opt-in arithmetic)
-    pi.nch32 = (Cin + 31) / 32;
-    pi.wbf_floats = k == 3 ? (int64_t)pi.nch32 * 9 * 2 * pi.CoutP * 8 : 0;          // bf16 copy of the 3x3 weights (reduced-precision blocks)
-    pi.nch8 = (Cin + 7) / 8;
-    pi.wino_floats = k == 3 ? (int64_t)pi.nch8 * 16 * 2 * pi.CoutP * 4 : 0;          // Winograd-domain weights G g G^T (modconv_wino.inc)
-    pi.nch4 = (Cin + 3) / 4; pi.nsl64 = (Cout + 63) / 64;
-    pi.wino4_floats = (k == 3 && Cin >= TDGP_WINO4_MIN_C && Cout >= TDGP_WINO4_MIN_C) ? (int64_t)cdiv(Cout, W4_BM) * pi.nch4 * W4_UCH : 0;      // F(4x4,3x3)-domain weights (modconv_wino4.inc)
-    return pi;
-}
-
-// pixel tiles of a launch whose blocks cover NT 32-pixel subtiles
-inline int px_tiles(const ConvParams& p, int NT) {
-    const int TW = 1 << p.tw_log2, RPS = 32 >> p.tw_log2, TR = NT * RPS;
-    return cdiv(p.ph.gridW, TW) * cdiv(p.B * p.ph.gridH, TR);
-}
-
-// Split-K factor: low-resolution layers have K = Cin*9 = 4608 but only a handful of output tiles, so a plain launch
-// leaves most of the 256 CUs idle behind a 64-iteration serial K loop.  Split K until ~2 blocks per CU exist.
-inline int pick_ksplit(int blocks, int niter) {
-    if (blocks >= 256 || niter < 4) return 1;
-    int ks = cdiv(512, blocks);
-    if (ks > niter / 2) ks = niter / 2;
-    if (ks > 32) ks = 32;
-    return ks < 1 ? 1 : ks;
-}
-
-template <int MTW, int NTW, int WM, int WN, int KCS, int MAXT>
-int launch_conv(ConvParams& p, float* partial, int64_t partial_floats, hipStream_t s) {
-    constexpr int BM = 32 * MTW * WM, NT = NTW * WN, BN = 32 * NT;
-    constexpr int HALO = MAXT == 25 ? 2 : 1;
-    constexpr int XS_MAX = (BN / 4 + 2 * HALO) * (4 + 2 * HALO) > (BN / 32 + 2 * HALO) * (32 + 2 * HALO) ? (BN / 4 + 2 * HALO) * (4 + 2 * HALO) : (BN / 32 + 2 * HALO) * (32 + 2 * HALO);
-    const size_t lds = (size_t)(2 * (MAXT * KCS * BM + KCS * XS_MAX + 64) + 32 + 5 * BM) * sizeof(float);
-    TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)conv_mfma_kernel<MTW, NTW, WM, WN, KCS, MAXT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds););   // raise the dynamic-LDS cap once per instantiation and device
-    const int gx = px_tiles(p, NT), gy = cdiv(p.Cout, BM);
-    const int niter = cdiv(cdiv(p.Cin, KC3), KCS / KC3);
-    const int64_t slice = (int64_t)p.e.B * p.e.Cout * p.e.Hout * p.e.Wout;
-    int ks = pick_ksplit(gx * gy, niter);
-    while (ks > 1 && ks * slice > partial_floats) ks--;          // never exceed the caller's workspace
-    p.ksplit = ks;
-    p.partial = partial;
-    dim3 grid(gx, gy, ks);
-    TDGP_LAUNCH("conv_mfma_kernel", (conv_mfma_kernel<MTW, NTW, WM, WN, KCS, MAXT>), grid, dim3(256), lds, s, p);
-    if (ks > 1)
-        TDGP_LAUNCH("splitk_reduce_kernel", splitk_reduce_kernel, dim3((int)min((int64_t)2048, cdiv64(slice, 256))), dim3(256), 0, s, partial, ks, p.e);
-    return 0;
-}
-
-// Split-K for launches that already fill the chip: tail balancing.  512 block slots (2 blocks per CU); a launch of n blocks
-// runs n / 512 full rounds plus a tail that costs ~0.7 of a round when <= 256 blocks are left (one block per CU runs faster)
-// -- e.g. 560 blocks are 1.7 rounds for 1.09 rounds of work.  Splitting K by ks shrinks the rounds; each extra slice costs
-// one more pass over the partial sums (~4 TB/s, mostly served by the 256 MB MALL).  Times in microseconds at ~100 TFLOP/s of
-// block throughput.
-inline int tail_ksplit(int blocks, int niter, double flop, int64_t slice_floats, int max_ks) {
-    double best = 1e30;
-    int ks = 1;
-    for (int k = 1; k <= max_ks && k <= 4 && niter / k >= 16; k++) {
-        const int n = blocks * k, full = n / 512, rem = n % 512;
-        const double rounds = full + (rem == 0 ? 0.0 : (rem <= 256 ? 0.7 : 1.0));
-        const double t = rounds * (flop / n) / (100e12 / 512) * 1e6 + (k - 1) * (double)slice_floats * 4.0 / 4e12 * 1e6;
-        if (t < best * 0.97) { best = t; ks = k; }
-    }
-    return ks;
-}
-
-// x2 layers: tile configuration, split-K factor and Z geometry -- shared by the workspace query and the launch.
-struct UpPlan { int cfg, BM, BN, G1, GS, ksplit; int64_t zslice; };
-inline UpPlan up_plan(int B, int Cin, int Cout, int H, int W) {
-    UpPlan u;
-    u.cfg = Cout > 64 ? 0 : 1;
-    u.BM = Cout > 64 ? 128 : 64; u.BN = Cout > 64 ? 64 : 128;
-    u.G1 = W + 2;                  // grid pitch: W + 1 would do (one zero column); W + 2 makes the Z row pitch 2*G1 a multiple of 4 floats -> 16-B FIR loads
-    u.GS = round_up((H + 1) * (W + 2), 32);
-    u.zslice = (int64_t)B * Cout * 4 * u.GS;
-    const int blocks = cdiv(B * u.GS, u.BN) * cdiv(Cout, u.BM);
-    const int niter = cdiv(Cin, 4);
-    int ks;
-    if (blocks < 256) {
-        ks = pick_ksplit(blocks, niter);
-        const int64_t cap = ((int64_t)64 << 20) / 4;             // low-resolution layers: at most 64 MiB of slices
-        while (ks > 1 && ks * u.zslice > cap) ks--;
-    } else {
-        ks = tail_ksplit(blocks, niter, 2.0 * Cin * Cout * 9.0 * H * W * B, u.zslice, 4);
-    }
-    u.ksplit = ks;
-    return u;
-}
-
-template <int MTW, int NTW, int WM, int WN, bool DEEP>
-void launch_upconv(const UpParams& u, hipStream_t s) {
-    constexpr int BM = 32 * MTW * WM, BN = 32 * NTW * WN, NW = WM * WN;
-    constexpr int stage = 2 * (9 * BM * 4 + 2 * (BN + 2) * 4), epi = NW * 32 * UP_CT_W;
-    const size_t lds = (size_t)(stage > epi ? stage : epi) * sizeof(float);
-    TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)upconv_mfma_kernel<MTW, NTW, WM, WN, DEEP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds););
-    dim3 grid(cdiv(u.B * u.GS, BN), cdiv(u.Cout, BM), u.ksplit);
-    TDGP_LAUNCH("upconv_mfma_kernel", (upconv_mfma_kernel<MTW, NTW, WM, WN, DEEP>), grid, dim3(64 * NW), lds, s, u);
-}
-
-// timing experiment (tools/dev/build_variant.sh): extra dynamic LDS per block = fewer resident blocks per CU.  0 in the shipped library.
-#ifndef TDGP_RGB_LDS_PAD
-#define TDGP_RGB_LDS_PAD 0
-#endif
-template <int MT, bool RESIDENT, bool FAST, bool XBF>
-void launch_torgb_v(const RgbParams& r, hipStream_t s) {
-    constexpr int BM = 32 * MT;
-    const size_t lds = (size_t)(16 * BM * 4 + 16 * 128 * 4 + BM) * sizeof(float) + TDGP_RGB_LDS_PAD;
-    TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)torgb_mfma_kernel<MT, RESIDENT, FAST, XBF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds););
-    // RESIDENT: several consecutive tiles per block once there are more tiles than ~4 rounds of the 512 resident blocks
-    RgbParams rr = r;
-    const int64_t ntiles = cdiv64(r.P, 128);
-#ifndef TDGP_RGB_WS
-#define TDGP_RGB_WS 1                  // 0: torgb_mfma_kernel for every layer (A/B builds, same bits)
-#endif
-    if constexpr (RESIDENT && FAST && !XBF) {
-        // the two-role form: enough tiles for >= 16 per block on a grid of four blocks per CU (C3 / C4: the 512^2 layer; at B = 1 the 512^2 layer still has 2048 tiles)
-        const int cus = tdgp_cu_count();
-        if (TDGP_RGB_WS && r.e.skip && ntiles >= (int64_t)cus * 8) {
-            constexpr size_t lds_ws = (size_t)(16 * BM * 4 + 2 * 16 * 128 * 4 + 4 * MT * 32 * CT_LD + BM) * sizeof(float);
-            TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)torgb_ws_kernel<MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ws););
-            const int64_t blocks = (int64_t)cus * 4;
-            rr.tpb = (int)cdiv64(ntiles, blocks);
-            TDGP_LAUNCH("torgb_mfma_kernel", (torgb_ws_kernel<MT>), dim3((unsigned)cdiv64(ntiles, rr.tpb)), dim3(512), lds_ws, s, rr);
-            return;
-        }
-    }
-    rr.tpb = RESIDENT ? (int)max((int64_t)1, min((int64_t)8, ntiles / 2048)) : 1;
-    TDGP_LAUNCH("torgb_mfma_kernel", (torgb_mfma_kernel<MT, RESIDENT, FAST, XBF>), dim3((unsigned)cdiv64(ntiles, rr.tpb)), dim3(256), lds, s, rr);
-}
-
-template <int MT, bool XBF = false>
-void launch_torgb(const RgbParams& r, hipStream_t s) {
-    const bool fast = r.lw >= 0 && r.e.clamp < 0.f && r.e.gain == 1.f;
-    if constexpr (XBF) {                                    // the reduced-precision blocks always clamp: one output stage
-        if (r.Cin <= 64) launch_torgb_v<MT, true, false, true>(r, s); else launch_torgb_v<MT, false, false, true>(r, s);
-    } else {
-        if (r.Cin <= 64) { if (fast) launch_torgb_v<MT, true, true, false>(r, s); else launch_torgb_v<MT, true, false, false>(r, s); }
-        else { if (fast) launch_torgb_v<MT, false, true, false>(r, s); else launch_torgb_v<MT, false, false, false>(r, s); }
-    }
-}
-
-// KS x KS stride-1 fast path (W % 32 == 0)
-template <int KS, int MTW, int NTW, int WM, int WN>
-int launch_conv3(Conv3Params& p, float* partial, int64_t partial_floats, hipStream_t s) {
-    constexpr int BM = 32 * MTW * WM, NT = NTW * WN, R = KS / 2;
-    constexpr int stage = 2 * (KS * KS * BM * 4 + (NT + 2 * R) * (32 + 2 * R) * 4) + 5 * BM, epi = 4 * 32 * CT_LD;
-    const size_t lds = (size_t)(stage > epi ? stage : epi) * sizeof(float);
-    TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)conv3_mfma_kernel<KS, MTW, NTW, WM, WN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds););
-    const int gx = (p.W >> 5) * cdiv(p.B * (p.H + R), NT), gy = cdiv(p.Cout, BM);
-    const int niter = cdiv(p.Cin, 4);
-    const int64_t slice = (int64_t)p.B * p.Cout * p.H * p.W;
-    const int max_ks = (int)min((int64_t)32, partial_floats / slice);
-    int ks = gx * gy < 256 ? pick_ksplit(gx * gy, niter) : tail_ksplit(gx * gy, niter, 2.0 * p.Cin * p.Cout * KS * KS * p.H * p.W * p.B, 2 * slice, max_ks);
-    if (ks > max_ks) ks = max_ks;
-    if (ks < 1) ks = 1;
-    p.ksplit = ks;
-    p.partial = partial;
-    TDGP_LAUNCH("conv_mfma_kernel", (conv3_mfma_kernel<KS, MTW, NTW, WM, WN>), dim3(gx, gy, ks), dim3(256), lds, s, p);
-    if (ks > 1)
-        TDGP_LAUNCH("splitk_reduce_kernel", splitk_reduce_kernel, dim3((int)min((int64_t)2048, cdiv64(slice, 256))), dim3(256), 0, s, partial, ks, p.e);
-    return 0;
-}
-
-inline int pick_tw_log2(int gridW) {
-    int tw = 4, lg = 2;
-    while (tw < 32 && tw < gridW) { tw <<= 1; lg++; }
-    return lg;
-}
-
-// F(4x4,3x3) Winograd (modconv_wino4.inc): which stride-1 3x3 layers take it -- by shape only (the workspace is sized from the same test).
-// whole tile groups of 512 pixels (64 x 8, or 32 x 16 for the 32-pixel-wide layers); Cin, Cout >= 128: below, the separate input-transform pass (2.25 x the input, written and
-// read back) costs more than it saves; at least one item per CU; V addressed through a 4 GiB buffer descriptor.
-inline int64_t wino4_v_bytes(int B, int Cin, int H, int W) { return (int64_t)B * ((H * W) >> 9) * ((Cin + 3) / 4) * (9 * 4 * 32 * 4) * 4; }       // 512 pixels per tile group
-inline int wino4_txl(int H, int W) { return (W & 63) == 0 && (H & 7) == 0 ? 4 : ((W & 31) == 0 && (H & 15) == 0 ? 3 : 0); }
-// The batch goes through the two kernels in sub-batches whose V fits one buffer descriptor (< 4 GiB; TDGP_WINO4_VCAP_MB lowers the cap for
-// experiments): C4's 512^2 x 128 layer at B = 16 has 4.8 GB of V.  The sub-batches share one V buffer (stream order).
-#ifndef TDGP_WINO4_VCAP_MB
-#define TDGP_WINO4_VCAP_MB 4095
-#endif
-// Layers with few channels move 2.25 x their input through V for little arithmetic: there a sub-batch whose V stays inside the 256 MB
-// Infinity Cache between the two kernels (TDGP_WINO4_VSMALL_MB) beats one big launch (measured B = 16: 256^2 x 128 1.38 (one sample per launch) /
-// 1.22 (two) / 1.25 (three) ms; 128^2 x 256 0.93 -> 1.03 ms -- hence Cin <= 128 only, and at least two samples per launch).
-#ifndef TDGP_WINO4_VSMALL_MB
-#define TDGP_WINO4_VSMALL_MB 192
-#endif
-#ifndef TDGP_WINO4_VSMALL_MINB
-#define TDGP_WINO4_VSMALL_MINB 2          // fewest samples per launch on that path (1: A/B builds)
-#endif
-inline int64_t wino4_items(int bs, int Cout, int H, int W) { return (int64_t)bs * ((H * W) >> 9) * cdiv(Cout, 64); }
-inline int wino4_sub_batch(int B, int Cin, int Cout, int H, int W) {
-    const int64_t per = wino4_v_bytes(1, Cin, H, W);
-    if (Cin <= 128 && TDGP_WINO4_VSMALL_MB > 0) {
-        const int bs = (int)std::min<int64_t>(B, ((int64_t)TDGP_WINO4_VSMALL_MB << 20) / per);
-        if (bs >= TDGP_WINO4_VSMALL_MINB && wino4_items(bs, Cout, H, W) >= 256) return bs;      // (one sample per launch -- 512^2 x 64: 151 MB of V next to 134 MB of x and y -- does not stay in the cache anyway: 1.84 vs 1.77 ms for the whole batch at once)
-    }
-    return (int)std::min<int64_t>(B, ((int64_t)TDGP_WINO4_VCAP_MB << 20) / per);
-}
-// Launches with too few items for the chip (the 32^2 layers at batch 4 .. 8) split the input channels of every item 2 or 4 ways (plain layers
-// only; >= 16 chunks per split; the whole batch in one launch); the splits' raw sums go through the split-K buffer of the direct kernels.
-// 0 = not a split-K shape.  B = 4, 32^2 x 512: direct sums 0.235 ms -> 4 splits (measured).
-#ifndef TDGP_WINO4_SPLITK
-#define TDGP_WINO4_SPLITK 1
-#endif
-inline int wino4_ksplit_log2(int B, int Cin, int Cout, int H, int W) {
-    if (!TDGP_WINO4_SPLITK || wino4_v_bytes(B, Cin, H, W) > ((int64_t)TDGP_WINO4_VSMALL_MB << 20)) return 0;
-    const int64_t base = wino4_items(B, Cout, H, W);
-    const int nch = Cin >> 2;
-    for (int l = 1; l <= 2; l++)
-        if ((base << l) >= 256 && (nch & ((1 << l) - 1)) == 0 && (nch >> l) >= 16) return l;
-    return 0;
-}
-inline bool wino4_shape_ok(int B, int Cin, int Cout, int H, int W, int k, int up, bool plain = false) {
-    if (!(k == 3 && up == 1 && wino4_txl(H, W) != 0 && (Cin & 3) == 0 && Cin >= TDGP_WINO4_MIN_C && Cout >= TDGP_WINO4_MIN_C)) return false;
-    const int bs = wino4_sub_batch(B, Cin, Cout, H, W);
-    if (bs >= 1 && wino4_items(bs, Cout, H, W) >= 256) return true;
-    return plain && wino4_items(B, Cout, H, W) < 256 && wino4_ksplit_log2(B, Cin, Cout, H, W) > 0;
-}
-
-// Workspace layout: [demod coefficients B*Cout] [transposed-conv intermediate, up=2 only] [split-K partial sums] [Winograd-domain input V]
-struct WsLayout { int64_t dco, z, partial, partial_floats, wino_v, total; };
-WsLayout ws_layout(int B, int Cin, int Cout, int H, int W, int k, int up) {
-    WsLayout w;
-    auto al = [](int64_t v) { return (v + 255) / 256 * 256; };
-    w.dco = 0;
-    w.z = al((int64_t)B * Cout * sizeof(float));
-    if (up == 2) {
-        // the parity-planar transposed-conv intermediate (x its split-K slices); the FIR kernel reduces the slices itself
-        const UpPlan u = up_plan(B, Cin, Cout, H, W);
-        w.partial = w.z + al(u.zslice * u.ksplit * (int64_t)sizeof(float));
-        w.partial_floats = 0;
-        w.wino_v = w.total = w.partial;
-        return w;
-    }
-    const int64_t out_elems = (int64_t)B * Cout * H * W;
-    w.partial = w.z;
-    // split-K is only chosen for launches with < 256 blocks: bound its buffer at 32 slices and 64 MiB
-    int64_t pf = out_elems * 32;
-    const int64_t cap = ((int64_t)64 << 20) / 4;
-    if (pf > cap) pf = (cap / out_elems) * out_elems;
-    w.partial_floats = pf;
-    w.wino_v = w.partial + al(pf * (int64_t)sizeof(float));
-    w.total = w.wino_v + (wino4_shape_ok(B, Cin, Cout, H, W, k, up, true) ? al(wino4_v_bytes(wino4_sub_batch(B, Cin, Cout, H, W), Cin, H, W)) + 256 : 0);      // + the item counters
-    return w;
-}
-
 }  // namespace
 
-TDGP_API int64_t tdgp_modconv_pack_bytes(int Cout, int Cin, int k) {
-    if (Cout < 1 || Cin < 1 || (k != 1 && k != 3 && k != 5)) return -1;
-    const PackInfo pi = pack_info(Cout, Cin, k);
-    return (pi.wp_floats + pi.wsq_floats + pi.wsplit_floats + pi.wbf_floats + pi.wino_floats + pi.wino4_floats) * (int64_t)sizeof(float);
-}
-
-TDGP_API int tdgp_modconv_pack(const float* weight, void* wpack, int Cout, int Cin, int k, tdgp_stream_t stream) {
-    TDGP_CHECK(weight && wpack, TDGP_EINVAL, "modconv_pack: null pointer");
-    TDGP_CHECK(Cout >= 1 && Cin >= 1, TDGP_EINVAL, "modconv_pack: bad channel counts");
-    TDGP_CHECK(k == 1 || k == 3 || k == 5, TDGP_EUNSUPPORTED, "modconv_pack: kernel size %d not on the generator path (1, 3 or 5)", k);
-    const PackInfo pi = pack_info(Cout, Cin, k);
-    float* wp = (float*)wpack;
-    TDGP_LAUNCH("pack_kernel", pack_kernel, dim3((int)min((int64_t)4096, cdiv64(pi.wp_floats, 256))), dim3(256), 0, (hipStream_t)stream, weight, wp,
-                       wp + pi.wp_floats, Cout, Cin, pi.T, pi.KC, pi.CoutP, pi.nchunks);
-    if (pi.wsplit_floats > 0)
-        TDGP_LAUNCH("pack_kernel", pack_split_kernel, dim3((int)min((int64_t)4096, cdiv64(pi.wsplit_floats, 256))), dim3(256), 0, (hipStream_t)stream, weight,
-                    (uint32_t*)(wp + pi.wp_floats + pi.wsq_floats), Cout, Cin, pi.CoutP, pi.niter16);
-    if (pi.wbf_floats > 0)
-        TDGP_LAUNCH("pack_kernel", pack_bf16_kernel, dim3((int)min((int64_t)4096, cdiv64(pi.wbf_floats, 256))), dim3(256), 0, (hipStream_t)stream, weight,
-                    (uint32_t*)(wp + pi.wp_floats + pi.wsq_floats + pi.wsplit_floats), Cout, Cin, pi.CoutP, pi.nch32);
-    if (pi.wino_floats > 0)
-        TDGP_LAUNCH("pack_kernel", pack_wino_kernel, dim3((int)min((int64_t)4096, cdiv64(pi.wino_floats, 256))), dim3(256), 0, (hipStream_t)stream, weight,
-                    wp + pi.wp_floats + pi.wsq_floats + pi.wsplit_floats + pi.wbf_floats, Cout, Cin, pi.CoutP, pi.nch8);
-    if (pi.wino4_floats > 0)
-        TDGP_LAUNCH("pack_kernel", pack_wino4_kernel, dim3((int)min((int64_t)4096, cdiv64(pi.wino4_floats, 256))), dim3(256), 0, (hipStream_t)stream, weight,
-                    wp + pi.wp_floats + pi.wsq_floats + pi.wsplit_floats + pi.wbf_floats + pi.wino_floats, Cout, Cin, cdiv(Cout, W4_BM), pi.nch4);
-    TDGP_LAUNCH_CHECK();
-    return TDGP_OK;
-}
-
-static int g_conv_arith = 0;
-static inline bool arith_wino4() { return g_conv_arith == 0 || g_conv_arith == 4; }
-TDGP_API int tdgp_set_conv_arith(int mode) {
-    TDGP_CHECK(mode >= 0 && mode <= 4, TDGP_EINVAL, "set_conv_arith: mode %d (0 = fp32 MFMA, Winograd F(4x4,3x3) / F(2x2,3x3) where they pay; 1 = split-bf16 MFMA with fp32 accumulation; 2 = fp32 MFMA, direct sums only; 3 = as 0 without F(4x4); 4 = as 0 with the F(4x4) input transform always as a pass of its own)", mode);
-    const int old = g_conv_arith;
-    g_conv_arith = mode;
-    return old;
-}
-
-
-// Cheap shape query (no launch, no allocation): does tdgp_modconv2d take a FOLDED x2 layer (out_layout 2: four parity 3x3 kernels, Cout4 = 4 x the
-// layer's output channels) of this shape on the Winograd F(4x4) kernels under the current arithmetic mode?  The binding asks BEFORE it folds and
-// packs the [4 Cout, Cin, 3, 3] weights (small launches paid the fold, the pack and an exception to learn the answer).
-TDGP_API int tdgp_modconv2d_takes_folded_up2(int B, int Cin, int Cout4, int H, int W) {
-    return (arith_wino4() && B >= 1 && (Cout4 & 3) == 0 && wino4_shape_ok(B, Cin, Cout4, H, W, 3, 1)) ? 1 : 0;
-}
-
-TDGP_API int64_t tdgp_modconv2d_workspace_bytes(int B, int Cin, int Cout, int H, int W, int k, int up) {
-    return ws_layout(B, Cin, Cout, H, W, k, up).total;
-}
-
-// Winograd kernel (modconv_wino.inc): which stride-1 3x3 layers take it.  TDGP_WINO_MIN_CIN: below it the direct kernel's staging
-// economy wins (K = Cin per position instead of 9 Cin); measured per layer, see DESIGN.md.
-#ifndef TDGP_WINO_MIN_CIN
-#define TDGP_WINO_MIN_CIN 64
-#endif
-inline size_t wino_lds_bytes(int) { return (size_t)(2 * 8192 + 2 * 8192 + 2 * 8 * 10 * 48 + 128) * 4; }
-inline bool wino_ok(int B, int Cin, int Cout, int H, int W) {
-    // (fewer than one block per CU: the direct kernel's split-K fills the chip better)
-    return (W & 31) == 0 && (H & 7) == 0 && (Cin & 7) == 0 && Cin >= TDGP_WINO_MIN_CIN && wino_lds_bytes(Cin) <= 160 * 1024 &&
-           (int64_t)(W >> 5) * (H >> 3) * B * cdiv(Cout, 64) >= 256;
-}
-
-TDGP_API int tdgp_modconv2d(const float* x, const void* wpack, const float* styles, const float* dcoef_in, const float* noise, int64_t noise_bstride,
-                            const float* bias, const float* fir4x4, const float* skip, float* y, int B, int Cin, int Cout, int H, int W,
-                            int k, int up, int demodulate, int act, float alpha, float gain, float clamp, int out_layout, int out_feat,
-                            void* workspace, int64_t workspace_bytes, tdgp_stream_t stream) {
-    TDGP_CHECK(x && wpack && y, TDGP_EINVAL, "modconv2d: null pointer");
-    TDGP_CHECK(B >= 1 && Cin >= 1 && Cout >= 1 && H >= 1 && W >= 1, TDGP_EINVAL, "modconv2d: bad shape");
-    TDGP_CHECK(k == 1 || k == 3 || k == 5, TDGP_EUNSUPPORTED, "modconv2d: kernel size %d not supported (1, 3 or 5)", k);
-    TDGP_CHECK(up == 1 || (up == 2 && k == 3), TDGP_EUNSUPPORTED, "modconv2d: up=%d with k=%d not supported", up, k);
-    TDGP_CHECK(up == 1 || fir4x4, TDGP_EINVAL, "modconv2d: up=2 needs the 4x4 resample filter");
-    TDGP_CHECK(!skip || (up == 1 && k == 1 && fir4x4 && (H % 2) == 0 && (W % 2) == 0), TDGP_EINVAL, "modconv2d: skip needs k=1, up=1, even H/W and the filter");
-    TDGP_CHECK(!demodulate || styles, TDGP_EINVAL, "modconv2d: demodulate needs styles");
-    TDGP_CHECK(act >= 1 && act <= 9, TDGP_EUNSUPPORTED, "modconv2d: unknown activation %d", act);
-    TDGP_CHECK(out_layout == 0 || out_layout == 2 || (out_layout == 1 && out_feat >= 4 && (out_feat % 4) == 0 && (Cout % out_feat) == 0 && up == 1 && k == 1), TDGP_EINVAL,
-               "modconv2d: the channel-last plane layout is a ToRGB (k=1, up=1) output");
-    // out_layout 2: the x2 layers with the FIR folded into four 3x3 parity kernels (Cout = 4 x the real channels, channel 4 o + 2 py + px;
-    // y is [B, Cout / 4, 2H, 2W], noise a 2H x 2W map, bias / dcoef_in replicated per parity by the caller).  Only the F(4x4) kernels write it.
-    TDGP_CHECK(out_layout != 2 || (k == 3 && up == 1 && (Cout & 3) == 0 && !skip && (!demodulate || dcoef_in)), TDGP_EINVAL,
-               "modconv2d: out_layout 2 (folded x2 layer) needs k=3, up=1, Cout %% 4 == 0, no skip and precomputed demodulation coefficients");
-    TDGP_CHECK(out_layout != 2 || (arith_wino4() && wino4_shape_ok(B, Cin, Cout, H, W, k, up) && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 &&
-                                   (!noise || (((uintptr_t)noise & 15) == 0 && (noise_bstride & 3) == 0))), TDGP_EUNSUPPORTED,
-               "modconv2d: out_layout 2 is written by the Winograd F(4x4) kernels only (shape %dx%d, %d -> %d channels, batch %d does not take them)", H, W, Cin, Cout, B);
-    TDGP_CHECK((int64_t)B * Cin * H * W < ((int64_t)1 << 30) && (int64_t)B * Cout * (H * up + 1) * (W * up + 1) <= INT32_MAX, TDGP_EINVAL,
-               "modconv2d: tensor too large (activations are addressed through 4 GiB buffer descriptors)");
-    const WsLayout wl = ws_layout(B, Cin, Cout, H, W, k, up);
-    TDGP_CHECK(workspace && workspace_bytes >= wl.total, TDGP_EWORKSPACE, "modconv2d: workspace %lld < %lld bytes", (long long)workspace_bytes,
-               (long long)wl.total);
-    hipStream_t s = (hipStream_t)stream;
-    const PackInfo pi = pack_info(Cout, Cin, k);
-    const float* wp = (const float*)wpack;
-    const float* wsq = wp + pi.wp_floats;
-    float* dco = (float*)((char*)workspace + wl.dco);
-    float* z = (float*)((char*)workspace + wl.z);
-    float* partial = (float*)((char*)workspace + wl.partial);
-    if (demodulate && dcoef_in) dco = const_cast<float*>(dcoef_in);             // precomputed by tdgp_demod_batch
-    else if (demodulate) TDGP_LAUNCH("demod_kernel", demod_kernel, dim3(cdiv(Cout, 64), B), dim3(1024), 0, s, styles, wsq, dco, B, Cin, Cout, pi.CoutP);
-    else dco = nullptr;
-
-    ConvParams p;
-    p.x = x; p.wp = wp; p.styles = styles; p.B = B; p.Cin = Cin; p.Cout = Cout; p.CoutP = pi.CoutP; p.Hin = H; p.Win = W;
-    p.T = pi.T; p.ksplit = 1; p.partial = nullptr;
-    EpiParams& e = p.e;
-    e.B = B; e.Cout = Cout; e.round_bf16 = 0;
-    for (int i = 0; i < 16; i++) e.fir[i] = 0.f;
-    if (fir4x4) {
-        // fir4x4 is a HOST pointer (the filter is a static 64-byte buffer; reading it on the host keeps the call async)
-        for (int ky = 0; ky < 4; ky++)
-            for (int kx = 0; kx < 4; kx++) e.fir[ky * 4 + kx] = fir4x4[(3 - ky) * 4 + (3 - kx)] * 4.0f;   // no flip_filter: taps = flipped f; gain up^2
-    }
-    if (up == 1) {
-        e.dcoef = dco; e.noise = noise; e.noise_bstride = noise_bstride; e.bias = bias; e.skip = skip; e.y = y;
-        e.Hout = H; e.Wout = W; e.out_layout = out_layout; e.out_feat = out_feat > 0 ? out_feat : 1;
-        e.act = act; e.alpha = alpha; e.gain = gain; e.clamp = clamp;
-        TapTable& ph = p.ph;
-        ph.ntaps = k * k; ph.halo = k / 2;
-        for (int t = 0; t < k * k; t++) {
-            ph.tap_w[t] = t;
-            ph.tap_off_y[t] = t / k - k / 2;                 // correlation, padding k/2 (conv2d_resample.py:132-134)
-            ph.tap_off_x[t] = t % k - k / 2;
-        }
-        ph.gridH = H; ph.gridW = W;
-        p.tw_log2 = pick_tw_log2(W);
-        if (k >= 3 && (W & 31) == 0) {
-            Conv3Params c;
-            c.x = x; c.wp = wp; c.styles = styles; c.partial = nullptr; c.e = e;
-            c.B = B; c.Cin = Cin; c.Cout = Cout; c.CoutP = pi.CoutP; c.H = H; c.W = W; c.ksplit = 1;
-            c.x_bytes = (uint32_t)((int64_t)B * Cin * H * W * 4); c.wp_bytes = (uint32_t)(pi.wp_floats * 4); c.st_bytes = (uint32_t)((int64_t)B * Cin * 4);
-            const int s_blocks = (W >> 5) * cdiv(B * (H + 1), 8) * cdiv(Cout, 64);
-            if (k == 3 && g_conv_arith == 1 && s_blocks >= 256 && styles && (Cin & 15) == 0 && Cin <= 2048 && H >= 16) {
-                Conv3sParams q;
-                q.x = x; q.wsp = wp + pi.wp_floats + pi.wsq_floats; q.styles = styles; q.e = e;
-                q.B = B; q.Cin = Cin; q.Cout = Cout; q.CoutP = pi.CoutP; q.H = H; q.W = W;
-                q.x_bytes = c.x_bytes; q.wsp_bytes = (uint32_t)(pi.wsplit_floats * 4); q.st_bytes = c.st_bytes;
-                const size_t lds = (size_t)(2 * 3 * 3 * 64 * 32 + 3 * 10 * 34 * 32 + 5 * 64 * 4 + 2 * Cin * 4);
-                TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)conv3s_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds - 2 * Cin * 4 + 2 * 2048 * 4)););
-                TDGP_LAUNCH("conv_mfma_kernel", conv3s_mfma_kernel, dim3((W >> 5) * cdiv(B * (H + 1), 8), cdiv(Cout, 64)), dim3(256), lds, s, q);
-            } else if (g_conv_arith == 0 && TDGP_WINO4F_MAXCIN > 0 && out_layout == 0 && Cin <= TDGP_WINO4F_MAXCIN && (Cin & 15) == 0 && (Cout & 63) == 0 && wino4_txl(H, W) == 4 &&
-                       wino4_shape_ok(B, Cin, Cout, H, W, k, up) && pi.wino4_floats > 0 && (int64_t)B * ((H * W) >> 9) * (Cout >> 6) >= 256 && !skip && ((uintptr_t)x & 15) == 0 &&
-                       ((uintptr_t)y & 15) == 0 && (!noise || (((uintptr_t)noise & 15) == 0 && (noise_bstride & 3) == 0))) {
-                // few input channels (the 256^2 / 512^2 blocks): the input transform runs inside the GEMM kernel, V never leaves the CU (modconv_wino4f.inc)
-                float* vbuf = (float*)((char*)workspace + wl.wino_v);
-                int* ticket = (int*)((char*)vbuf + ((wino4_v_bytes(wino4_sub_batch(B, Cin, Cout, H, W), Cin, H, W) + 255) / 256 * 256));
-                const int cus = tdgp_cu_count(), nxcd = (cus % 8 == 0 && cus >= 64) ? 8 : 1, per = cus / nxcd, nsl = Cout >> 6;
-                int rs = 1;
-                while (rs * 2 <= nsl && (per % (rs * 2)) == 0 && (rs * 2) * 64 + per / (rs * 2) * 32 < rs * 64 + per / rs * 32) rs *= 2;
-                Wino4fParams q;
-                q.x = x; q.styles = styles; q.u = wp + pi.wp_floats + pi.wsq_floats + pi.wsplit_floats + pi.wbf_floats + pi.wino_floats; q.e = e;
-                q.B = B; q.Cin = Cin; q.Cout = Cout; q.H = H; q.W = W; q.u_bytes = (uint32_t)(pi.wino4_floats * 4); q.x_bytes = c.x_bytes; q.st_bytes = c.st_bytes;
-                q.nz_bytes = noise ? (uint32_t)(((noise_bstride ? (int64_t)(B - 1) * noise_bstride : 0) + (int64_t)H * W) * 4) : 0u;
-                q.gxn = W / 64; q.gyn = H / 8; q.rs = rs; q.rt = per / rs; q.nxcd = nxcd; q.ticket = ticket;
-                const size_t lds = (size_t)W4F_LDS_FLOATS * 4;
-                TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)conv3_wino4f_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds););
-                TDGP_CHECK(hipMemsetAsync(ticket, 0, 32, s) == hipSuccess, TDGP_ELAUNCH, "modconv2d: clearing the item counters failed");
-                TDGP_LAUNCH("conv_wino4f_kernel", conv3_wino4f_kernel, dim3((unsigned)(nxcd * per)), dim3(512), lds, s, q);
-            } else if (arith_wino4() && wino4_shape_ok(B, Cin, Cout, H, W, k, up, out_layout == 0) && pi.wino4_floats > 0 && (out_layout == 0 || out_layout == 2) && !skip && ((uintptr_t)x & 15) == 0 &&
-                       ((uintptr_t)y & 15) == 0 && (!noise || (((uintptr_t)noise & 15) == 0 && (noise_bstride & 3) == 0))) {
-                float* vbuf = (float*)((char*)workspace + wl.wino_v);
-                // persistent grid; the blocks of an XCD (b, b + 8, ...) take a rectangle of rs slices x rt tile groups per pass: per pass an XCD's L2 then
-                // fetches rs U slices + rt V tile groups instead of one of each per block (bytes ~ rs * BM + rt * 32: a slice's U chunk : a tile group's V chunk)
-#ifndef TDGP_WINO4_PAIR
-#define TDGP_WINO4_PAIR 1          // 1: the 8-wave form (a slice x a pair of tile groups per block, three V stages; modconv_wino4.inc)
-#endif
-                constexpr bool pairk = TDGP_WINO4_PAIR && W4_BM == 32;
-                const int bpc = (W4_BM == 64 || pairk) ? 1 : 2;                 // resident blocks per CU
-                // K split (too few items for the chip): only when the unsplit shape does not qualify, the split-K buffer holds the slices, plain layers
-                int ksl = (out_layout == 0 && !wino4_shape_ok(B, Cin, Cout, H, W, k, up)) ? wino4_ksplit_log2(B, Cin, Cout, H, W) : 0;
-                const int64_t kslice = (int64_t)B * Cout * H * W;
-                if ((kslice << ksl) > wl.partial_floats) ksl = 0;               // (cannot happen for shapes under 256 items: 4 splits x 255 items x 32768 floats < the 64 MiB buffer; unsplit is still correct)
-                const int cus = tdgp_cu_count(), nxcd = (cus % 8 == 0 && cus >= 64) ? 8 : 1, per = cus / nxcd * bpc, nsl = cdiv(Cout, W4_BM) << ksl;
-                int rs = 1;
-                const int tpi = pairk ? 64 : 32;                                // tiles per item
-                while (rs * 2 <= nsl && (per % (rs * 2)) == 0 && (rs * 2) * W4_BM + per / (rs * 2) * tpi < rs * W4_BM + per / rs * tpi) rs *= 2;
-                const size_t lds = pairk ? (size_t)(8 * W4_UCH + 3 * W4_BM + 4) * 4 : (size_t)(2 * W4_STAGE + 2 * W4_BM + 4) * 4;          // the stages, bias + demodulation of the slice, the ticket
-                TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)conv3_wino4_kernel<false, pairk>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); (void)hipFuncSetAttribute((const void*)conv3_wino4_kernel<true, pairk>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds););
-                const int bsub = ksl ? B : wino4_sub_batch(B, Cin, Cout, H, W);
-                int* ticket = (int*)((char*)vbuf + ((wino4_v_bytes(wino4_sub_batch(B, Cin, Cout, H, W), Cin, H, W) + 255) / 256 * 256));
-                for (int b0 = 0; b0 < B; b0 += bsub) {
-                    const int bn = std::min(bsub, B - b0);
-                    Wino4Params q;
-                    q.v = vbuf; q.u = wp + pi.wp_floats + pi.wsq_floats + pi.wsplit_floats + pi.wbf_floats + pi.wino_floats; q.e = e;
-                    q.e.y = y + (int64_t)b0 * Cout * H * W;                        // (out_layout 2: Cout / 4 channels of 4 H W pixels -- the same count)
-                    q.ups = out_layout == 2 ? 1 : 0;
-                    if (e.dcoef) q.e.dcoef = e.dcoef + (int64_t)b0 * Cout;
-                    if (e.noise) q.e.noise = e.noise + (int64_t)b0 * noise_bstride;
-                    q.e.B = bn;
-                    q.B = bn; q.Cin = Cin; q.Cout = Cout; q.CoutP = pi.CoutP; q.H = H; q.W = W;
-                    q.v_bytes = (uint32_t)wino4_v_bytes(bn, Cin, H, W); q.u_bytes = (uint32_t)(pi.wino4_floats * 4);
-                    q.txl = wino4_txl(H, W); q.gxn = W / (4 << q.txl); q.gyn = H / (128 >> q.txl);
-                    q.rs = rs; q.rt = per / rs; q.nxcd = nxcd; q.ticket = ticket; q.ksl = ksl; q.partial = partial;
-                    const int ntg = q.gxn * q.gyn * bn;
-                    TDGP_LAUNCH("wino4_input_kernel", wino4_input_kernel, dim3((unsigned)(ntg * pi.nch4)), dim3(128), 0, s, x + (int64_t)b0 * Cin * H * W,
-                                styles ? styles + (int64_t)b0 * Cin : nullptr, vbuf, bn, Cin, H, W, q.gxn, q.gyn, pi.nch4, q.txl, ticket);
-                    if (q.ups) TDGP_LAUNCH("upconv_wino4_kernel", (conv3_wino4_kernel<true, pairk>), dim3((unsigned)(nxcd * per)), dim3(pairk ? 512 : W4_NW * 64), lds, s, q);
-                    else TDGP_LAUNCH("conv_wino4_kernel", (conv3_wino4_kernel<false, pairk>), dim3((unsigned)(nxcd * per)), dim3(pairk ? 512 : W4_NW * 64), lds, s, q);
-                    if (ksl) TDGP_LAUNCH("splitk_reduce_kernel", splitk_reduce_kernel, dim3((int)min((int64_t)2048, cdiv64(kslice, 256))), dim3(256), 0, s, partial, 1 << ksl, e);
-                }
-            } else if (k == 3 && (arith_wino4() || g_conv_arith == 3) && wino_ok(B, Cin, Cout, H, W) && out_layout == 0 && !skip && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 7) == 0 &&
-                       (!noise || (((uintptr_t)noise & 7) == 0 && (noise_bstride & 1) == 0))) {        // 16-byte activation loads, 8-byte noise loads / stores
-                WinoParams q;
-                q.x = x; q.u = wp + pi.wp_floats + pi.wsq_floats + pi.wsplit_floats + pi.wbf_floats; q.styles = styles; q.e = e;
-                q.B = B; q.Cin = Cin; q.Cout = Cout; q.CoutP = pi.CoutP; q.H = H; q.W = W;
-                q.x_bytes = c.x_bytes; q.u_bytes = (uint32_t)(pi.wino_floats * 4);
-                const size_t lds = wino_lds_bytes(Cin);
-                TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)conv3_wino_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024););
-                if (TDGP_WINO_PERSIST) {
-                    const int cus = tdgp_cu_count();
-                    const int64_t nitems = (int64_t)(W >> 5) * (H >> 3) * B * cdiv(Cout, 64);
-                    TDGP_LAUNCH("conv_wino_kernel", conv3_wino_kernel, dim3((unsigned)min((int64_t)cus, nitems)), dim3(512), lds, s, q);
-                } else
-                TDGP_LAUNCH("conv_wino_kernel", conv3_wino_kernel, dim3((W >> 5) * (H >> 3) * B, cdiv(Cout, 64)), dim3(512), lds, s, q);
-            } else if (k == 3) {
-                if (Cout > 64) launch_conv3<3, 2, 2, 2, 2>(c, partial, wl.partial_floats, s);
-                else launch_conv3<3, 2, 2, 1, 4>(c, partial, wl.partial_floats, s);
-            } else {
-                if (Cout > 64) launch_conv3<5, 2, 2, 2, 2>(c, partial, wl.partial_floats, s);
-                else launch_conv3<5, 2, 2, 1, 4>(c, partial, wl.partial_floats, s);
-            }
-        } else if (k == 3) {
-            if (Cout > 64) launch_conv<2, 2, 2, 2, 4, 9>(p, partial, wl.partial_floats, s);
-            else launch_conv<2, 2, 1, 4, 4, 9>(p, partial, wl.partial_floats, s);
-        } else if (k == 5) {
-            if (Cout > 64) launch_conv<2, 2, 2, 2, 4, 25>(p, partial, wl.partial_floats, s);
-            else launch_conv<2, 2, 1, 4, 4, 25>(p, partial, wl.partial_floats, s);
-        } else if (out_layout == 1 && Cout <= 96 && !demodulate && !noise && e.act == 1 && ((H * W) & 3) == 0) {
-            RgbParams r;
-            r.x = x; r.wp = wp; r.styles = styles; r.e = e;
-            r.B = B; r.Cin = Cin; r.Cout = Cout; r.CoutP = pi.CoutP; r.HW = H * W; r.W = W; r.P = (int64_t)B * H * W;
-            r.lw = r.lhw = -1;
-            if ((W & (W - 1)) == 0 && (H & (H - 1)) == 0 && (int64_t)B * H * W < ((int64_t)1 << 31) - 512) {
-                r.lw = 0; while ((1 << r.lw) < W) r.lw++;
-                r.lhw = 0; while ((1 << r.lhw) < H * W) r.lhw++;
-            }
-            r.x_bytes = (uint32_t)((int64_t)B * Cin * H * W * 4); r.wp_bytes = (uint32_t)(pi.wp_floats * 4); r.st_bytes = (uint32_t)((int64_t)B * Cin * 4);
-            if (Cout <= 32) launch_torgb<1>(r, s);
-            else if (Cout <= 64) launch_torgb<2>(r, s);
-            else launch_torgb<3>(r, s);
-        } else {
-            if (Cout > 64 && Cout <= 96) launch_conv<3, 1, 1, 4, 32, 1>(p, partial, wl.partial_floats, s);
-            else if (Cout > 64) launch_conv<2, 2, 2, 2, 16, 1>(p, partial, wl.partial_floats, s);
-            else launch_conv<2, 2, 1, 4, 16, 1>(p, partial, wl.partial_floats, s);
-        }
-    } else {
-        // transposed conv, stride 2, UNFLIPPED weights (conv2d_resample.py:108-125) -> parity-planar Z -> FIR + output stage
-        const UpPlan pl = up_plan(B, Cin, Cout, H, W);
-        UpParams u;
-        u.x = x; u.wp = wp; u.styles = styles; u.z = z;
-        u.B = B; u.Cin = Cin; u.Cout = Cout; u.CoutP = pi.CoutP; u.H = H; u.W = W; u.G1 = pl.G1; u.GS = pl.GS; u.ksplit = pl.ksplit; u.zslice = pl.zslice;
-        u.x_bytes = (uint32_t)((int64_t)B * Cin * H * W * 4); u.wp_bytes = (uint32_t)(pi.wp_floats * 4); u.st_bytes = (uint32_t)((int64_t)B * Cin * 4);
-        // opt-in split-bf16 arithmetic (tdgp_set_conv_arith(1)): same Z, one slice
-        const int s_blocks = cdiv(B * pl.GS, 128) * cdiv(Cout, 64);
-        const bool split = g_conv_arith == 1 && s_blocks >= 256 && styles && (Cin & 15) == 0 && Cin <= 2048 && pl.GS >= 2 * (128 + pl.G1 + 2);
-        if (split) {
-            Up3sParams q;
-            q.x = x; q.wsp = wp + pi.wp_floats + pi.wsq_floats; q.styles = styles; q.z = z;
-            q.B = B; q.Cin = Cin; q.Cout = Cout; q.CoutP = pi.CoutP; q.H = H; q.W = W; q.G1 = pl.G1; q.GS = pl.GS; q.zslice = pl.zslice;
-            q.x_bytes = u.x_bytes; q.wsp_bytes = (uint32_t)(pi.wsplit_floats * 4);
-            const size_t lds = (size_t)(2 * 3 * 3 * 64 * 32 + 3 * 2 * 130 * 32 + (2 * 8 * 256 + 8 * 64) * 4 + 2 * 64 * 4);
-            TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)upconv3s_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds););
-            TDGP_LAUNCH("upconv_mfma_kernel", upconv3s_mfma_kernel, dim3(cdiv(B * pl.GS, 128), cdiv(Cout, 64)), dim3(256), lds, s, q);
-        }
-        // (Round 3, measured and not kept: 8-wave blocks -- 128 x 128 for Cout > 64, 64 x 256 below -- so that one staged weight chunk serves twice the
-        //  MFMAs: -0.7 % / -1.3 % on the whole step; the staging instructions are not what holds this kernel at 0.65 of the MFMA peak.)
-        else if (pl.cfg == 0) launch_upconv<2, 1, 2, 2, true>(u, s);
-        else launch_upconv<2, 1, 1, 4, false>(u, s);
-        FirParams f;
-        f.z = z; f.dcoef = dco; f.noise = noise; f.noise_bstride = noise_bstride; f.bias = bias; f.y = y; f.y16 = nullptr;
-        f.noise_vec = noise && (((uintptr_t)noise) & 15) == 0 && (noise_bstride & 3) == 0;
-        for (int i = 0; i < 16; i++) f.fir[i] = e.fir[i];
-        f.B = B; f.C = Cout; f.ZROWS = 2 * H + 2; f.P2 = 2 * pl.G1; f.GS2 = 2 * pl.GS; f.ksplit = split ? 1 : pl.ksplit; f.zslice = pl.zslice;
-        f.OH = 2 * H; f.OW = 2 * W;
-        f.act = act; f.alpha = alpha; f.gain = gain; f.clamp = clamp;
-        if (TDGP_FIR_ADJ && f.OW >= 128 && (f.OH & 31) == 0 && f.ksplit == 1 && f.act == 3 && f.alpha >= 0.f && f.alpha <= 1.f) {
-            const int64_t ntiles = (int64_t)B * Cout * cdiv(f.OH, 32) * cdiv(f.OW, 128);
-            TDGP_LAUNCH("fir_act_kernel", (fir_act_kernel<32, 128, false, true, true>), dim3((int)min((int64_t)(256 * 32), ntiles)), dim3(256), 0, s, f);
-        } else if (f.OW >= 128 && !TDGP_AB_FIR_SERIAL) {
-            const int64_t ntiles = (int64_t)B * Cout * cdiv(f.OH, 16) * cdiv(f.OW, 128);
-            if (f.act == 3 && f.alpha >= 0.f && f.alpha <= 1.f)
-                TDGP_LAUNCH("fir_act_kernel", (fir_act_kernel<16, 128, false, true>), dim3((int)min((int64_t)(256 * 32), ntiles)), dim3(256), 0, s, f);
-            else
-                TDGP_LAUNCH("fir_act_kernel", (fir_act_kernel<16, 128>), dim3((int)min((int64_t)(256 * 32), ntiles)), dim3(256), 0, s, f);
-        } else {
-            const int64_t ntiles = (int64_t)B * Cout * cdiv(f.OH, 32) * cdiv(f.OW, 64);
-            TDGP_LAUNCH("fir_act_kernel", (fir_act_kernel<32, 64>), dim3((int)min((int64_t)(256 * 32), ntiles)), dim3(256), 0, s, f);
-        }
-    }
-    TDGP_LAUNCH_CHECK();
-    return TDGP_OK;
-}
-
-// Reduced-precision blocks (BASELINE configs[4], modconv_bf16.inc): x is bf16 NCHW; y is bf16 NCHW (3x3 layers) or, for the ToRGB
-// form (k = 1, channel-last planes + fused skip), fp32.  Forms the bf16 MFMA kernels take: 3x3 with Cin % 32 == 0 and, for up = 1,
-// W % 32 == 0; the channel-last ToRGB.  Anything else returns TDGP_EUNSUPPORTED (the caller widens to fp32 and uses tdgp_modconv2d).
-TDGP_API int tdgp_modconv2d_bf16(const void* x, const void* wpack, const float* styles, const float* dcoef_in, const float* noise, int64_t noise_bstride,
-                                 const float* bias, const float* fir4x4, const float* skip, void* y, int B, int Cin, int Cout, int H, int W, int k, int up,
-                                 int demodulate, int act, float alpha, float gain, float clamp, int out_layout, int out_feat, void* workspace,
-                                 int64_t workspace_bytes, tdgp_stream_t stream) {
-    TDGP_CHECK(x && wpack && y, TDGP_EINVAL, "modconv2d_bf16: null pointer");
-    TDGP_CHECK(B >= 1 && Cin >= 1 && Cout >= 1 && H >= 1 && W >= 1, TDGP_EINVAL, "modconv2d_bf16: bad shape");
-    TDGP_CHECK(act >= 1 && act <= 9, TDGP_EUNSUPPORTED, "modconv2d_bf16: unknown activation %d", act);
-    TDGP_CHECK(!demodulate || styles, TDGP_EINVAL, "modconv2d_bf16: demodulate needs styles");
-    TDGP_CHECK((int64_t)B * Cin * H * W < ((int64_t)1 << 30) && (int64_t)B * Cout * (H * up + 1) * (W * up + 1) <= INT32_MAX, TDGP_EINVAL,
-               "modconv2d_bf16: tensor too large (activations are addressed through 4 GiB buffer descriptors)");
-    const bool rgb = k == 1 && up == 1 && out_layout == 1 && Cout <= 96 && !demodulate && !noise && act == 1 && ((H * W) & 3) == 0 && out_feat >= 4 &&
-                     (out_feat % 4) == 0 && (Cout % out_feat) == 0 && (!skip || (fir4x4 && (H % 2) == 0 && (W % 2) == 0));
-    const bool c3 = k == 3 && up == 1 && out_layout == 0 && !skip && (W & 31) == 0 && (Cin & 31) == 0 && Cin <= 2048;
-    bool u3 = k == 3 && up == 2 && out_layout == 0 && !skip && fir4x4 && (Cin & 31) == 0 && (W & 1) == 0;
-    size_t u3_lds = 0;
-    if (u3) {                                     // every acceptance test before the first launch: the x2 kernel keeps the styles of all samples a block's
-        const UpPlan pl0 = up_plan(B, Cin, Cout, H, W);                                   // grid points can touch in LDS
-        const int nsb0 = std::min(B, (130 + pl0.G1) / pl0.GS + 2);
-        u3_lds = (size_t)(9 * 2 * 64 * 32 + 2 * 2 * 130 * 32) + (size_t)nsb0 * Cin * 4;
-        TDGP_CHECK(u3_lds <= 80 * 1024, TDGP_EUNSUPPORTED, "modconv2d_bf16: x2 layer with Cin=%d, B=%d, H=%d needs %zu bytes of LDS (> 80 KiB)", Cin, B, H, u3_lds);
-    }
-    TDGP_CHECK(rgb || c3 || u3, TDGP_EUNSUPPORTED, "modconv2d_bf16: no bf16 kernel for k=%d up=%d Cin=%d W=%d layout=%d", k, up, Cin, W, out_layout);
-    const bool nz16 = !noise || ((((uintptr_t)noise) & 15) == 0 && (noise_bstride & 3) == 0);
-    TDGP_CHECK(nz16, TDGP_EINVAL, "modconv2d_bf16: noise must be 16-byte aligned with a batch stride that is a multiple of 4 floats");
-    const WsLayout wl = ws_layout(B, Cin, Cout, H, W, k, up);
-    TDGP_CHECK(workspace && workspace_bytes >= wl.total, TDGP_EWORKSPACE, "modconv2d_bf16: workspace %lld < %lld bytes", (long long)workspace_bytes,
-               (long long)wl.total);
-    hipStream_t s = (hipStream_t)stream;
-    const PackInfo pi = pack_info(Cout, Cin, k);
-    const float* wp = (const float*)wpack;
-    const float* wsq = wp + pi.wp_floats;
-    const void* wb = wp + pi.wp_floats + pi.wsq_floats + pi.wsplit_floats;
-    float* dco = (float*)((char*)workspace + wl.dco);
-    float* z = (float*)((char*)workspace + wl.z);
-    if (demodulate && dcoef_in) dco = const_cast<float*>(dcoef_in);
-    else if (demodulate) TDGP_LAUNCH("demod_kernel", demod_kernel, dim3(cdiv(Cout, 64), B), dim3(1024), 0, s, styles, wsq, dco, B, Cin, Cout, pi.CoutP);
-    else dco = nullptr;
-    EpiParams e;
-    e.B = B; e.Cout = Cout; e.round_bf16 = 1;
-    for (int i = 0; i < 16; i++) e.fir[i] = 0.f;
-    if (fir4x4)
-        for (int ky = 0; ky < 4; ky++)
-            for (int kx = 0; kx < 4; kx++) e.fir[ky * 4 + kx] = fir4x4[(3 - ky) * 4 + (3 - kx)] * 4.0f;
-    e.dcoef = dco; e.noise = noise; e.noise_bstride = noise_bstride; e.bias = bias; e.skip = skip; e.y = (float*)y;
-    e.Hout = H * up; e.Wout = W * up; e.out_layout = out_layout; e.out_feat = out_feat > 0 ? out_feat : 1;
-    e.act = act; e.alpha = alpha; e.gain = gain; e.clamp = clamp;
-    const uint32_t x_bytes = (uint32_t)((int64_t)B * Cin * H * W * 2);
-    if (rgb) {
-        RgbParams r;
-        r.x = (const float*)x; r.wp = wp; r.styles = styles; r.e = e;
-        r.B = B; r.Cin = Cin; r.Cout = Cout; r.CoutP = pi.CoutP; r.HW = H * W; r.W = W; r.P = (int64_t)B * H * W;
-        r.lw = r.lhw = -1;
-        if ((W & (W - 1)) == 0 && (H & (H - 1)) == 0 && (int64_t)B * H * W < ((int64_t)1 << 31) - 512) {
-            r.lw = 0; while ((1 << r.lw) < W) r.lw++;
-            r.lhw = 0; while ((1 << r.lhw) < H * W) r.lhw++;
-        }
-        r.x_bytes = x_bytes; r.wp_bytes = (uint32_t)(pi.wp_floats * 4); r.st_bytes = (uint32_t)((int64_t)B * Cin * 4);
-        if (Cout <= 32) launch_torgb<1, true>(r, s);
-        else if (Cout <= 64) launch_torgb<2, true>(r, s);
-        else launch_torgb<3, true>(r, s);
-    } else if (c3) {
-        ConvBfParams q;
-        q.x = (const uint16_t*)x; q.wb = wb; q.styles = styles; q.e = e; q.y16 = (uint16_t*)y;
-        q.B = B; q.Cin = Cin; q.Cout = Cout; q.CoutP = pi.CoutP; q.H = H; q.W = W;
-        q.x_bytes = x_bytes; q.wb_bytes = (uint32_t)(pi.wbf_floats * 4);
-        const size_t lds = (size_t)(9 * 2 * 64 * 32 + 2 * 10 * 34 * 32 + 5 * 64 * 4 + 2 * Cin * 4);
-        TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)conv3_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds - 2 * Cin * 4 + 2 * 2048 * 4)););
-        TDGP_LAUNCH("conv_bf16_kernel", conv3_bf16_kernel<true>, dim3((W >> 5) * cdiv(B * (H + 1), 8), cdiv(Cout, 64)), dim3(256), lds, s, q);
-    } else {
-        const UpPlan pl = up_plan(B, Cin, Cout, H, W);
-        UpBfParams q;
-        q.x = (const uint16_t*)x; q.wb = wb; q.styles = styles; q.z = z;
-        q.B = B; q.Cin = Cin; q.Cout = Cout; q.CoutP = pi.CoutP; q.H = H; q.W = W; q.G1 = pl.G1; q.GS = pl.GS; q.zslice = pl.zslice;
-        q.x_bytes = x_bytes; q.wb_bytes = (uint32_t)(pi.wbf_floats * 4); q.st_bytes = (uint32_t)((int64_t)B * Cin * 4);
-        const size_t lds = u3_lds;                                              // checked against the 80 KiB budget above
-        TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)upconv_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024););
-        TDGP_LAUNCH("upconv_bf16_kernel", upconv_bf16_kernel, dim3(cdiv(B * pl.GS, 128), cdiv(Cout, 64)), dim3(256), lds, s, q);
-        FirParams f;
-        f.z = z; f.dcoef = dco; f.noise = noise; f.noise_bstride = noise_bstride; f.bias = bias; f.y = nullptr; f.y16 = (uint16_t*)y;
-        f.noise_vec = noise != nullptr;          // alignment checked at entry
-        for (int i = 0; i < 16; i++) f.fir[i] = e.fir[i];
-        f.B = B; f.C = Cout; f.ZROWS = 2 * H + 2; f.P2 = 2 * pl.G1; f.GS2 = 2 * pl.GS; f.ksplit = 1; f.zslice = pl.zslice;
-        f.OH = 2 * H; f.OW = 2 * W;
-        f.act = act; f.alpha = alpha; f.gain = gain; f.clamp = clamp;
-        if (f.OW >= 128) {
-            const int64_t ntiles = (int64_t)B * Cout * cdiv(f.OH, 16) * cdiv(f.OW, 128);
-            if (f.act == 3 && f.alpha >= 0.f && f.alpha <= 1.f)
-                TDGP_LAUNCH("fir_act_kernel", (fir_act_kernel<16, 128, true, true>), dim3((int)min((int64_t)(256 * 32), ntiles)), dim3(256), 0, s, f);
-            else
-                TDGP_LAUNCH("fir_act_kernel", (fir_act_kernel<16, 128, true>), dim3((int)min((int64_t)(256 * 32), ntiles)), dim3(256), 0, s, f);
-        } else {
-            const int64_t ntiles = (int64_t)B * Cout * cdiv(f.OH, 32) * cdiv(f.OW, 64);
-            TDGP_LAUNCH("fir_act_kernel", (fir_act_kernel<32, 64, true>), dim3((int)min((int64_t)(256 * 32), ntiles)), dim3(256), 0, s, f);
-        }
-    }
-    TDGP_LAUNCH_CHECK();
-    return TDGP_OK;
-}
-
-TDGP_API int tdgp_cast_f32_bf16(const float* x, void* y_bf16, int64_t n, tdgp_stream_t stream) {
-    TDGP_CHECK((x && y_bf16) || n == 0, TDGP_EINVAL, "cast_f32_bf16: null pointer");
-    if (n <= 0) return TDGP_OK;
-    TDGP_LAUNCH("cast_f32_bf16_kernel", cast_f32_bf16_kernel, dim3((int)min((int64_t)8192, cdiv64(n, 512))), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)y_bf16, n);
-    TDGP_LAUNCH_CHECK();
-    return TDGP_OK;
-}
-
-TDGP_API int tdgp_conv_transpose2d_x2(const float* x, const void* wpack, const float* styles, float* y, int B, int Cin, int Cout, int H, int W,
-                                      void* workspace, int64_t workspace_bytes, tdgp_stream_t stream) {
-    TDGP_CHECK(x && wpack && y, TDGP_EINVAL, "conv_transpose2d_x2: null pointer");
-    TDGP_CHECK(B >= 1 && Cin >= 1 && Cout >= 1 && H >= 1 && W >= 1, TDGP_EINVAL, "conv_transpose2d_x2: bad shape");
-    TDGP_CHECK((int64_t)B * Cin * H * W < ((int64_t)1 << 30) && (int64_t)B * Cout * (H * 2 + 1) * (W * 2 + 1) <= INT32_MAX, TDGP_EINVAL,
-               "conv_transpose2d_x2: tensor too large (activations are addressed through 4 GiB buffer descriptors)");
-    const WsLayout wl = ws_layout(B, Cin, Cout, H, W, 3, 2);
-    TDGP_CHECK(workspace && workspace_bytes >= wl.total, TDGP_EWORKSPACE, "conv_transpose2d_x2: workspace %lld < %lld bytes", (long long)workspace_bytes,
-               (long long)wl.total);
-    hipStream_t s = (hipStream_t)stream;
-    const PackInfo pi = pack_info(Cout, Cin, 3);
-    float* z = (float*)((char*)workspace + wl.z);
-    const UpPlan pl = up_plan(B, Cin, Cout, H, W);
-    UpParams u;
-    u.x = x; u.wp = (const float*)wpack; u.styles = styles; u.z = z;
-    u.B = B; u.Cin = Cin; u.Cout = Cout; u.CoutP = pi.CoutP; u.H = H; u.W = W; u.G1 = pl.G1; u.GS = pl.GS; u.ksplit = pl.ksplit; u.zslice = pl.zslice;
-    u.x_bytes = (uint32_t)((int64_t)B * Cin * H * W * 4); u.wp_bytes = (uint32_t)(pi.wp_floats * 4); u.st_bytes = (uint32_t)((int64_t)B * Cin * 4);
-    if (pl.cfg == 0) launch_upconv<2, 1, 2, 2, true>(u, s);
-    else launch_upconv<2, 1, 1, 4, false>(u, s);
-    const int64_t rows = (int64_t)B * Cout * (2 * H + 1);
-    TDGP_LAUNCH("z_gather_kernel", z_gather_kernel, dim3((unsigned)min((int64_t)65535 * 8, rows)), dim3(256), 0, s, (const float*)z, y, rows, 2 * H + 1, 2 * W + 1,
-                2 * pl.G1, 2 * pl.GS, pl.ksplit, pl.zslice);
-    TDGP_LAUNCH_CHECK();
-    return TDGP_OK;
-}
-
-TDGP_API int64_t tdgp_modconv_wsq_offset(int Cout, int Cin, int k) {
-    if (Cout < 1 || Cin < 1 || (k != 1 && k != 3 && k != 5)) return -1;
-    return pack_info(Cout, Cin, k).wp_floats * (int64_t)sizeof(float);
-}
-
-TDGP_API int tdgp_demod_batch(const float* styles_all, const int64_t* meta, float* dcoef_all, int B, int num_layers, int max_cout, tdgp_stream_t stream) {
-    TDGP_CHECK(styles_all && meta && dcoef_all, TDGP_EINVAL, "demod_batch: null pointer");
-    TDGP_CHECK(B >= 1 && num_layers >= 1 && max_cout >= 1, TDGP_EINVAL, "demod_batch: bad shape");
-    TDGP_LAUNCH("demod_kernel", demod_batch_kernel, dim3(cdiv(max_cout, 64), B, num_layers), dim3(1024), 0, (hipStream_t)stream, styles_all, meta, dcoef_all, B);
-    TDGP_LAUNCH_CHECK();
-    return TDGP_OK;
-}
-
-TDGP_API int tdgp_style_affine(const float* ws, const float* A, const float* abias, const int32_t* row_meta, const float* row_scale,
-                               float* styles, int B, int num_ws, int w_dim, int rows_total, tdgp_stream_t stream) {
-    TDGP_CHECK(ws && A && abias && row_meta && row_scale && styles, TDGP_EINVAL, "style_affine: null pointer");
-    TDGP_CHECK(B >= 1 && num_ws >= 1 && w_dim >= 1 && rows_total >= 1, TDGP_EINVAL, "style_affine: bad shape");
-    const int64_t waves = (int64_t)B * rows_total;
-    const float wgain = (float)(1.0 / sqrt((double)w_dim));
-    TDGP_LAUNCH("style_affine_kernel", style_affine_kernel, dim3((int)cdiv64(waves, 4)), dim3(256), 0, (hipStream_t)stream, ws, A, abias, row_meta, row_scale, styles, B,
-                       num_ws, w_dim, rows_total, wgain);
-    TDGP_LAUNCH_CHECK();
-    return TDGP_OK;
-}
+#include "modconv_host.inc"      // the host half: pack layout, launch plan, workspace layout, launchers, the exported entry points

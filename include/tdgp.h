@@ -124,10 +124,34 @@ int tdgp_upfirdn2d(const void* x, const float* f, void* y, int N, int C, int inH
  * --------------------------------------------------------------------------------------------- */
 int64_t tdgp_modconv_pack_bytes(int Cout, int Cin, int k);
 int     tdgp_modconv_pack(const float* weight, void* wpack, int Cout, int Cin, int k, tdgp_stream_t stream);
+/* The workspace size is decided by the shape alone: an upper bound over every kernel family the shape can take, whatever the arithmetic mode
+ * (tdgp_set_conv_arith), the alignment of the tensors and the output layout of the call turn out to be. */
 int64_t tdgp_modconv2d_workspace_bytes(int B, int Cin, int Cout, int H, int W, int k, int up);
 /* 1 when tdgp_modconv2d would take a folded x2 layer (out_layout 2, Cout4 = 4 x Cout parity channels) of this shape on the F(4x4) kernels
  * under the current arithmetic mode, else 0 -- a host-side query (no launch) the binding makes before folding and packing the weights. */
 int     tdgp_modconv2d_takes_folded_up2(int B, int Cin, int Cout4, int H, int W);
+/* Which kernel family tdgp_modconv2d runs a call as -- the launch plan the call itself reads, so a caller (a benchmark pricing a layer, a
+ * test pinning the selection) asks instead of mirroring the conditions.
+ * replaces: nothing in the reference (cuDNN picks its algorithm out of sight); answers: the dispatch of tdgp_modconv2d.
+ * Same shape arguments as the workspace query + out_layout; `flags` = TDGP_PATHQ_* facts of the call (ALIGNED: x, y and the noise map 16-byte
+ * aligned, noise batch stride a multiple of 4 floats; LRELU: the activation of a synthesis layer -- lrelu, alpha 0.2, gain sqrt 2, no clamp --,
+ * clear: linear, gain 1).  Returns a tdgp_conv_path under the current arithmetic mode, or a negative TDGP_E* code for a call tdgp_modconv2d
+ * would refuse.  Host-side only: no launch, no GPU needed. */
+typedef enum tdgp_conv_path {
+    TDGP_PATH_DIRECT = 0,        /* conv_mfma_kernel: 3x3 / 5x5, any width */
+    TDGP_PATH_CONV3 = 1,         /* conv3_mfma_kernel: 3x3 / 5x5 with W % 32 == 0 */
+    TDGP_PATH_SPLIT3 = 2,        /* split-bf16 arithmetic (mode 1), 3x3 */
+    TDGP_PATH_WINO2 = 3,         /* Winograd F(2x2,3x3) */
+    TDGP_PATH_WINO4 = 4,         /* Winograd F(4x4,3x3): input transform pass + GEMM */
+    TDGP_PATH_WINO4F = 5,        /* F(4x4) with the input transform inside the GEMM kernel */
+    TDGP_PATH_WINO4_SPLITK = 6,  /* F(4x4), input channels split 2 or 4 ways (too few items for the chip) */
+    TDGP_PATH_WINO4_FOLDED = 7,  /* out_layout 2: x2 layer folded into four parity 3x3 kernels on F(4x4) */
+    TDGP_PATH_UP = 8,            /* up = 2: transposed convolution + FIR pass */
+    TDGP_PATH_TORGB = 9,         /* 1x1, channel-last planes (+ fused skip): torgb_mfma_kernel */
+    TDGP_PATH_CONV1 = 10         /* any other 1x1: conv_mfma_kernel */
+} tdgp_conv_path;
+enum { TDGP_PATHQ_STYLES = 1, TDGP_PATHQ_SKIP = 2, TDGP_PATHQ_NOISE = 4, TDGP_PATHQ_DEMODULATE = 8, TDGP_PATHQ_ALIGNED = 16, TDGP_PATHQ_LRELU = 32 };
+int     tdgp_modconv2d_path(int B, int Cin, int Cout, int H, int W, int k, int up, int out_layout, int flags);
 int     tdgp_modconv2d(const float* x, const void* wpack, const float* styles, const float* dcoef, const float* noise,
                        int64_t noise_bstride, const float* bias, const float* fir4x4, const float* skip,
                        float* y, int B, int Cin, int Cout, int H, int W, int k, int up, int demodulate,

@@ -215,6 +215,66 @@ def test_device_fault_word_is_exported_and_quiet(tdgp):
     assert tdgp._lib.device_fault() == 0 and tdgp._lib.device_fault(clear=True) == 0
 
 
+def test_modconv2d_path_query_agrees_with_the_bench_mirrors(tdgp):
+    """tdgp_modconv2d_path answers from the launch plan tdgp_modconv2d itself reads (no GPU needed).  bench.py prices the layers with hand-written
+    mirrors of the selection: on every stride-1 3x3 layer shape of C1-C5 at B = 1 .. 32 (plain layers, aligned tensors, arithmetic mode 0) the
+    two must name the same kernel family, and on the x2 layer shapes tdgp_modconv2d_takes_folded_up2 must be the path query's answer for the
+    folded form."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(REPO, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    lib = tdgp._lib.load()
+    DIRECT, CONV3, WINO2, WINO4, WINO4F, WINO4_SPLITK, WINO4_FOLDED = 0, 1, 3, 4, 5, 6, 7        # tdgp_conv_path (include/tdgp.h)
+    STYLES, NOISE, DEMODULATE, ALIGNED, LRELU = 1, 4, 8, 16, 32                                    # TDGP_PATHQ_*
+    plain = STYLES | NOISE | DEMODULATE | ALIGNED | LRELU
+    header = open(os.path.join(REPO, 'include', 'tdgp.h')).read()
+    for name, val in (('DIRECT', DIRECT), ('CONV3', CONV3), ('WINO2', WINO2), ('WINO4', WINO4), ('WINO4F', WINO4F), ('WINO4_SPLITK', WINO4_SPLITK),
+                      ('WINO4_FOLDED', WINO4_FOLDED)):
+        assert re.search(rf'TDGP_PATH_{name} = {val}\b', header), name
+    for name, val in (('STYLES', STYLES), ('NOISE', NOISE), ('DEMODULATE', DEMODULATE), ('ALIGNED', ALIGNED), ('LRELU', LRELU)):
+        assert re.search(rf'TDGP_PATHQ_{name} = {val}\b', header), name
+    prev = lib.tdgp_set_conv_arith(0)
+    try:
+        stride1, x2 = set(), set()
+        for cfg in (getattr(tdgp.config, f'config_c{i}')() for i in range(1, 6)):
+            for i, r in enumerate(cfg.block_resolutions):
+                stride1.add((cfg.channels[r], r))
+                if i > 0:
+                    x2.add((cfg.channels[r // 2], cfg.channels[r], r // 2))
+        assert len(stride1) >= 8 and len(x2) >= 7
+        seen = set()
+        for B in (1, 2, 4, 8, 16, 32):
+            for c, r in sorted(stride1):
+                path = lib.tdgp_modconv2d_path(B, c, c, r, r, 3, 1, 0, plain)
+                if (B, c, r) == (32, 128, 512):
+                    # the one shape of the sweep left out (C4's 512^2 x 128 layer at B = 32): 2^30 input elements, one more than a call takes
+                    # ("tensor too large": activations are addressed through 4 GiB buffer descriptors), so the query answers TDGP_EINVAL like the
+                    # call would; the mirrors know nothing of that bound (the generator runs such a batch in chunks)
+                    assert path == -1 and B * c * r * r == 1 << 30
+                    continue
+                fused, w4, w2 = bench.winograd4_fused_takes(B, c, c, r), bench.winograd4_takes(B, c, c, r), bench.winograd_takes(B, c, c, r)
+                want = (WINO4F,) if fused else ((WINO4, WINO4_SPLITK) if w4 else ((WINO2,) if w2 else (DIRECT, CONV3)))
+                assert path in want, (B, c, r, path, want)
+                seen.add(path)
+            for cin, cout, h in sorted(x2):
+                takes = lib.tdgp_modconv2d_takes_folded_up2(B, cin, 4 * cout, h, h)
+                path = lib.tdgp_modconv2d_path(B, cin, 4 * cout, h, h, 3, 1, 2, plain)
+                assert path in (WINO4_FOLDED, -2) and takes == int(path == WINO4_FOLDED), (B, cin, cout, h, takes, path)     # -2 = TDGP_EUNSUPPORTED: the call refuses the folded form
+                seen.add(path)
+        assert {CONV3, DIRECT, WINO4, WINO4F, WINO4_SPLITK, WINO4_FOLDED, -2} <= seen, seen
+        # the facts of the call count: an unaligned tensor or another arithmetic mode leaves the Winograd kernels
+        assert lib.tdgp_modconv2d_path(16, 64, 64, 512, 512, 3, 1, 0, plain) == WINO4F
+        assert lib.tdgp_modconv2d_path(16, 64, 64, 512, 512, 3, 1, 0, plain & ~ALIGNED) == CONV3
+        lib.tdgp_set_conv_arith(4)
+        assert lib.tdgp_modconv2d_path(16, 64, 64, 512, 512, 3, 1, 0, plain) == WINO4
+        lib.tdgp_set_conv_arith(2)
+        assert lib.tdgp_modconv2d_path(16, 64, 64, 512, 512, 3, 1, 0, plain) == CONV3
+        assert lib.tdgp_modconv2d_path(16, 64, 64, 512, 512, 7, 1, 0, plain) == -2 and lib.tdgp_modconv2d_path(0, 64, 64, 512, 512, 3, 1, 0, plain) == -1
+    finally:
+        lib.tdgp_set_conv_arith(prev)
+
+
 def test_fold_up2_table_is_the_x2_layer(tdgp):
     """ops/modconv.fold_up2_table: the stride-2 transposed 3x3 convolution + 4x4 FIR of conv2d_resample.py:108-125 (flip_weight=False) as four
     3x3 'same' correlations of x, one per output parity -- against the op's own reference path (torch CPU ops, float64), image borders
