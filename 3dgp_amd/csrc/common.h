@@ -185,11 +185,7 @@ __device__ __forceinline__ float wave_sum_f32(float v) { return wave_last_f32(wa
 // every instruction the two per-ray kernels issue (they are bound by their VALU count, profiles/r02_pmc_sq_mix.md).  Measured on
 // gfx950 over [-30, 22] against the exactly rounded value (tools/dev/softplus_acc.hip): max 2.7 ulp / mean 0.33 ulp here, 1.6 / 0.26
 // for log1pf(expf(x)), 1.5 / 0.28 for torch's own CPU softplus (Sleef): the same noise floor the reference itself sits on.
-#ifndef TDGP_SOFTPLUS_OCML
-#define TDGP_SOFTPLUS_OCML 0        // 1: the literal log1pf(expf(x)) (A/B timing and accuracy comparisons)
-#endif
 __device__ __forceinline__ float softplus20f(float x) {
-    if (TDGP_SOFTPLUS_OCML) return x > 20.f ? x : log1pf(expf(x));
     const float t = expf(-fabsf(x));
     const float u = 1.0f + t;
     const float l1 = logf(u) + (t - (u - 1.0f)) * __builtin_amdgcn_rcpf(u);

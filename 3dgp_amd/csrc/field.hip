@@ -28,11 +28,7 @@
 // SIMD; 4.95 ms per 67 M points, matrix pipe 43 % busy.  DESIGN.md (e) lists what was tried on top and measured slower.
 #include "common.h"
 
-// Compile-time ablations for timing experiments (tools/dev/build_variant.sh): 1 = no tap loads, 2 = no layer-1 MFMAs,
-// 4 = no stores, 32 = per-phase cycle counts of one wave (printed).  Always 0 in the shipped library.
-#ifndef TDGP_WALK_WAVES
-#define TDGP_WALK_WAVES 2      // waves per SIMD the table walk is compiled for (3: 168 registers, 24 spilled -- measured slower)
-#endif
+constexpr int WALK_WAVES = 2;  // waves per SIMD the table walk is compiled for (3: 168 registers, 24 spilled -- measured slower)
 
 namespace {
 
@@ -576,7 +572,7 @@ template <int FQ, int MT, bool TAPS>
 __global__ __launch_bounds__(256, 2) void triplane_field_kernel(FieldParams p) { field_body<FQ, MT, TAPS, false>(p); }
 
 template <int FQ, int MT, bool TAPS>
-__global__ __launch_bounds__(256, TDGP_WALK_WAVES) void triplane_walk_kernel(FieldParams p) { field_body<FQ, MT, TAPS, true>(p); }
+__global__ __launch_bounds__(256, WALK_WAVES) void triplane_walk_kernel(FieldParams p) { field_body<FQ, MT, TAPS, true>(p); }
 
 #include "field_walk2.inc"
 
@@ -644,22 +640,18 @@ __global__ __launch_bounds__(256) void planes_to_hwc_kernel(const float* __restr
     }
 }
 
-#ifndef TDGP_WALK2
-#define TDGP_WALK2 1           // 0: the one-role table walk (triplane_walk_kernel) everywhere -- A/B builds
-#endif
-
 template <int FQ, int MT, bool TAPS>
 void launch_field_t(const FieldParams& p, hipStream_t s) {
     int64_t want;
     const bool walk = FQ % 4 == 0 && p.ray_w > 0 && p.planes_bytes != 0;
-    if constexpr (FQ % 4 == 0 && FQ <= 8 && TDGP_WALK2) {
+    if constexpr (FQ % 4 == 0 && FQ <= 8) {
         // producer / consumer walk (field_walk2.inc): whole groups of four samples, a ring that is shorter than a patch's march
         // (the walk addresses ray_o / ray_d / t through scalar base + 32-bit byte offset)
         if (walk && (p.S & 3) == 0 && p.S >= 16 && p.total * 4 < ((int64_t)1 << 32) && (p.total / p.S) * 12 < ((int64_t)1 << 32)) {
             using L = Walk2Lds<FQ, MT>;
             const int cus = tdgp_cu_count();
             TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)triplane_walk2_kernel<FQ, MT, TAPS>, hipFuncAttributeMaxDynamicSharedMemorySize, L::total));
-            const int ps = ((p.S & 15) == 0 && TDGP_WALK2_DEPTHSPLIT) ? 4 : 8;       // patch side (field_walk2.inc: DEPTHSPLIT)
+            const int ps = 8;                                            // patch side (field_walk2.inc)
             const int64_t npatch = (p.total / p.P) * cdiv(p.ray_w, ps) * cdiv(p.ray_h, ps);
             int blocks = (int)min((int64_t)cus, npatch);                // one 512-thread block per CU, each striding over the patches
             if (blocks > 8) blocks -= blocks % 8;

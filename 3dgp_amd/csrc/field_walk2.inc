@@ -20,17 +20,10 @@
 // such waves per SIMD cannot cover each other (measured r02/r03: 2900 cycles per tile against 1152 matrix + ~620 vector-issue cycles;
 // 2440 with the tap loads compiled out).  Here the matrix stream of a SIMD never waits for memory, and the memory side runs ahead by up
 // to NSLOT tiles.
-#ifndef TDGP_WALK2_SLOTS
-#define TDGP_WALK2_SLOTS 6
-#endif
-#ifndef TDGP_WALK2_ABL
-#define TDGP_WALK2_ABL 0                // 1 / 2 / 3: timing experiments on the tap loads (tools/dev only; wrong results) -- see issue()
-#endif
-#ifndef TDGP_WALK2_SPIN
-#define TDGP_WALK2_SPIN (1 << 15)      // bounded waits (~2 ms; a legitimate one lasts microseconds): a protocol bug or a stall under a debugger must
+constexpr int WALK2_SLOTS = 6;         // ring tiles per pair (4 when HID >= 128: Walk2Lds::NS)
+constexpr int WALK2_SPIN = 1 << 15;    // bounded waits (~2 ms; a legitimate one lasts microseconds): a protocol bug or a stall under a debugger must
                                        // never hang the GPU -- on a timeout the wave sets the library's device-fault word (include/tdgp.h:
                                        // tdgp_device_fault) and ends; its partner times out once and ends too: the launch finishes, flagged
-#endif
 __device__ __forceinline__ void walk2_fault(int* word, int code) {
     if (word && lane_id() == 0) __hip_atomic_fetch_or(word, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
@@ -48,16 +41,10 @@ struct Walk2Lds {
     //              bank slots with slot = 16 sample + ray (4-way, 32 LDS cycles per store);
     //   park       [16 rays][33] float4 as before (its flush reads stay 2-way: 4 of ~100 LDS cycles per tile; the conflict-free pitch
     //              47 does not fit the 160 KB).
-#ifndef TDGP_WALK2_RING_PAIRED
-#define TDGP_WALK2_RING_PAIRED 1       // 0: round 3's rows of F + 4 floats (A/B builds)
-#endif
-#ifndef TDGP_WALK2_TAB_PITCH
-#define TDGP_WALK2_TAB_PITCH 18        // 16: round 3's table (A/B builds)
-#endif
-    static constexpr int RP2 = TDGP_WALK2_RING_PAIRED ? 20 : 2 * (FQ + 1), RPO = TDGP_WALK2_RING_PAIRED ? 12 : FQ + 1;     // float4 slots per pair of points, offset of the odd one
+    static constexpr int RP2 = 20, RPO = 12;                           // float4 slots per pair of points, offset of the odd one
     static constexpr int RT = 8 * RP2 * 4;                             // floats per ring tile
-    static constexpr int TS = TDGP_WALK2_TAB_PITCH, TP = 4 * TS;       // tap table: slots per sample, slots per row
-    static constexpr int NS = (MT >= 8) ? 4 : TDGP_WALK2_SLOTS;
+    static constexpr int TS = 18, TP = 4 * TS;                               // tap table: slots per sample, slots per row
+    static constexpr int NS = (MT >= 8) ? 4 : WALK2_SLOTS;
     static constexpr int off_a0 = 0;                                   // [MT*FQ][64] layer-1 A operands (start-up only)
     static constexpr int off_a1 = off_a0 + MT * FQ * 64 * 4;           // [MT*4][64]  layer-2 A operands
     static constexpr int off_b0 = off_a1 + MT * 4 * 64 * 4;            // [HID]
@@ -73,7 +60,7 @@ struct Walk2Lds {
 };
 
 // float offset of (point pt, channel quad c) inside a ring tile
-__device__ __forceinline__ int walk2_ring_off(int pt, int c, int RP2, int RPO) { return ((pt >> 1) * RP2 + (pt & 1) * RPO + (TDGP_WALK2_RING_PAIRED ? (c ^ (2 * (pt & 1))) : c)) * 4; }
+__device__ __forceinline__ int walk2_ring_off(int pt, int c, int RP2, int RPO) { return ((pt >> 1) * RP2 + (pt & 1) * RPO + (c ^ (2 * (pt & 1)))) * 4; }
 
 // the counters: wave-uniform values (every lane reads / writes the same word), compared on the scalar unit
 __device__ __forceinline__ int lds_peek(int* p) { return __builtin_amdgcn_readfirstlane(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)); }
@@ -109,18 +96,12 @@ __global__ __launch_bounds__(512, 1) void triplane_walk2_kernel(FieldParams p) {
     float* const ring = (float*)(smem + L::off_ring + pair * L::ring_bytes);
     const int S = p.S;
 
-#ifndef TDGP_WALK2_DEPTHSPLIT
-#define TDGP_WALK2_DEPTHSPLIT 0         // measured (r03): correct (same bits), 3-4 % SLOWER than quadrants (4.54 vs 4.38 ms): the L1 is not what the gather waits for
-#endif
-    // Work of a block.  DEPTHSPLIT (an experiment, off; when S % 16 == 0): a patch is ONE 4x4-pixel quad and the four pairs share it, pair w marching the
-    // samples [w S/4, (w+1) S/4) of its 16 rays.  The (x,y)-plane texels of a ray hardly move along the ray (perspective only), so the
-    // four producers of the CU keep re-touching the same 64 lines of that plane -- 8 KB that stay in the L1 -- instead of each cycling
-    // through its own quadrant's lines (4 x 8 KB of (x,y) lines plus the depth-dependent planes thrash a 32 KB L1).  Otherwise a patch is
-    // 8x8 pixels and pair w takes quadrant w.  Same points, same arithmetic either way.
-    const bool dsplit = TDGP_WALK2_DEPTHSPLIT && (S & 15) == 0;
-    const int PS = dsplit ? 4 : 8;                      // patch side in pixels
-    const int Sq = dsplit ? S >> 2 : S;                 // samples a pair marches per patch
-    const int kb = dsplit ? pair * Sq : 0;              // its first sample
+    // Work of a block: a patch is 8x8 pixels and pair w takes quadrant w.  (Measured, r03: one 4x4-pixel quad per patch shared by the four pairs,
+    // pair w marching a quarter of the depth range so that the (x,y)-plane lines stay in the L1: correct (same bits), 3-4 % SLOWER than quadrants
+    // (4.54 vs 4.38 ms): the L1 is not what the gather waits for.)
+    const int PS = 8;                                   // patch side in pixels
+    const int Sq = S;                                   // samples a pair marches per patch
+    const int kb = 0;                                   // its first sample
     // patches of this block: ids lb, lb + nb, ... in the XCD-compact order of triplane_walk_kernel
     const int pX = (p.ray_w + PS - 1) / PS, pY = (p.ray_h + PS - 1) / PS;
     const int npatch = (int)(p.total / p.P) * pX * pY;
@@ -130,11 +111,7 @@ __global__ __launch_bounds__(512, 1) void triplane_walk2_kernel(FieldParams p) {
     const int total = npl * Sq;                                        // tiles this pair marches
     if (total == 0) return;
     auto decode = [&](int patch, int& b, int& py, int& px) {
-        if (dsplit && ((pX | pY) & 15) == 0) {           // quads run through 16 x 16-quad (64 x 64-pixel) squares
-            const int per_img = pX * pY, r = patch % per_img, sq = r >> 8, in = r & 255;
-            b = patch / per_img;
-            px = (sq % (pX >> 4)) * 16 + (in & 15); py = (sq / (pX >> 4)) * 16 + (in >> 4);
-        } else if (!dsplit && ((pX | pY) & 7) == 0) {
+        if (((pX | pY) & 7) == 0) {
             const int per_img = pX * pY, r = patch % per_img, sq = r >> 6, in = r & 63;
             b = patch / per_img;
             px = (sq % (pX >> 3)) * 8 + (in & 7); py = (sq / (pX >> 3)) * 8 + (in >> 3);
@@ -143,44 +120,24 @@ __global__ __launch_bounds__(512, 1) void triplane_walk2_kernel(FieldParams p) {
         }
     };
     auto ray_of = [&](int b, int py, int px, int tpt, bool& ok) {          // pixel tpt of this pair's 4x4 quadrant -> ray index
-        const int y = dsplit ? py * 4 + (tpt >> 2) : py * 8 + ((pair >> 1) & 1) * 4 + (tpt >> 2);
-        const int x = dsplit ? px * 4 + (tpt & 3) : px * 8 + (pair & 1) * 4 + (tpt & 3);
+        const int y = py * 8 + ((pair >> 1) & 1) * 4 + (tpt >> 2);
+        const int x = px * 8 + (pair & 1) * 4 + (tpt & 3);
         ok = y < p.ray_h && x < p.ray_w;
         return b * (int)p.R + (ok ? y * p.ray_w + x : 0);
     };
 
-#ifndef TDGP_WALK2_PRIO
-#define TDGP_WALK2_PRIO 0               // measured (r03, one box, interleaved): producer at priority 3: +6 % time, consumer at 3: +8 %
-#endif
     if (role == 0) {
         // ================================================================ producer
-        // Static priority: the producer's short instructions go ahead of the consumer's queue of 32-cycle MFMAs whenever they are ready --
-        // its critical path (table read -> addresses -> loads ... -> blend -> ring) is a chain of issue latencies, the consumer's is
-        // pipe time.
-        if (TDGP_WALK2_PRIO > 0) __builtin_amdgcn_s_setprio(TDGP_WALK2_PRIO);
+        // (No static priority for either role.  Measured, r03, one box, interleaved: producer at priority 3: +6 % time, consumer at 3: +8 %.)
         uint4* const atab = (uint4*)(smem + L::off_atab + pair * L::atab_bytes);      // [2][6][TP]
         const int gpt = l >> 2, gc4 = l & 3;
-        const uint32_t c4off = (uint32_t)gc4 * 16u;
         const int plane_elems = p.H * p.W * F;
         const uint32_t plane_bytes = (uint32_t)plane_elems * 4u;
-#ifndef TDGP_WALK2_ADDTID
-#define TDGP_WALK2_ADDTID 1            // measured: 4.56 -> 4.43 ms per 67 M points (B = 16, average of the two passes)
-#endif
-#if TDGP_WALK2_ADDTID
         // ADD_TID_ENABLE (descriptor word 3 bit 23) with stride 16: the hardware adds lane_id * 16 to every address.  The table rows are
         // biased by 1024 - 64 * ray (ray = lane >> 2), the descriptor base by -1024: lane 4 * ray + c4 lands on texel + 16 * c4 -- the
         // piece offset costs no vector instruction (12 v_add per tile otherwise).  DATA_FORMAT doubles as stride bits when ADD_TID is on: 0.
-        const __amdgpu_buffer_rsrc_t rpl = __builtin_amdgcn_make_buffer_rsrc((char*)const_cast<float*>(p.planes) - 1024, 16, 0x7fffffff, 0x00800000);
+        // Measured: 4.56 -> 4.43 ms per 67 M points (B = 16, average of the two passes).
         const uint32_t tid_adj = 1024u - 64u * (uint32_t)gpt;
-#else
-        const __amdgpu_buffer_rsrc_t rpl = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.planes), 0, p.planes_bytes, 0x00020000);
-        const uint32_t tid_adj = 0u;
-#endif
-#ifndef TDGP_WALK2_ASMLOAD
-#define TDGP_WALK2_ASMLOAD 1
-#endif
-#if TDGP_WALK2_ASMLOAD
-        static_assert(TDGP_WALK2_ADDTID, "the hand-issued loads use the ADD_TID descriptor");
         // The tap loads and their waits are issued by hand (inline asm).  Reason: for loads whose results are used in the NEXT loop iteration
         // the compiler's wait-count bookkeeping gives up and waits for everything at the first use (vmcnt(0) at the loop head; reproduced
         // on a ten-line loop), so the two buffers were requested, awaited and refilled as one batch and the texture path sat idle while
@@ -193,7 +150,6 @@ __global__ __launch_bounds__(512, 1) void triplane_walk2_kernel(FieldParams p) {
         typedef unsigned int w2_u32x4 __attribute__((ext_vector_type(4)));
         const uint64_t dbase = (uint64_t)(uintptr_t)((const char*)p.planes - 1024);
         const w2_u32x4 dsc = {(uint32_t)dbase, (uint32_t)((dbase >> 32) & 0xffffu) | (16u << 16), 0x7fffffffu, 0x00800000u};
-#endif
         const int wslot = gc4 * TS + gpt;                  // table slot this lane writes: sample gc4 of the group, ray gpt
         const float sx = (float)(p.W - 1) / 2.f, sy = (float)(p.H - 1) / 2.f;
         const int gpp = Sq >> 2;                           // groups of four samples per patch and pair (S % 4 == 0, checked on the host)
@@ -221,31 +177,20 @@ __global__ __launch_bounds__(512, 1) void triplane_walk2_kernel(FieldParams p) {
                 t_voff = ((uint32_t)gray * (uint32_t)S + (uint32_t)(kb + gc4)) * 4u;
                 pq_cached = pi_;
             }
-#if TDGP_WALK2_ASMLOAD
             // scalar base + 32-bit vector offset (the launcher checks that ray_o / ray_d / t stay below 4 GiB): the per-lane part is computed once per
             // patch, the group adds one scalar -- the 64-bit pointer arithmetic these three requests used to need was 9 vector instructions per pair of tiles
             const uint32_t tv = t_voff + (uint32_t)__builtin_amdgcn_readfirstlane(gl_ * 16);
             asm volatile("global_load_dwordx3 %0, %1, %2" : "=v"(ray_o3) : "v"(ray_voff), "s"(p.ray_o));
             asm volatile("global_load_dwordx3 %0, %1, %2" : "=v"(ray_d3) : "v"(ray_voff), "s"(p.ray_d));
             asm volatile("global_load_dword %0, %1, %2" : "=v"(t_grp) : "v"(tv), "s"(p.t));
-#else
-            const float* ro = p.ray_o + gray * 3;
-            const float* rdp = p.ray_d + gray * 3;
-            const float* tq = p.t + ((int64_t)gray * S + kb + gl_ * 4 + gc4);
-            ray_o3 = (w2_f32x3){ro[0], ro[1], ro[2]};
-            ray_d3 = (w2_f32x3){rdp[0], rdp[1], rdp[2]};
-            t_grp = *tq;
-#endif
         };
         // One (ray, sample) per lane: the arithmetic of triplane_walk_kernel's address_phase, step for step (tap indices bit-exact).
         auto address_phase = [&](int tb, int k0) {
             uint4* const tab = atab + tb * (6 * TP);
             const int ks = kb + k0 + gc4;
-#if TDGP_WALK2_ASMLOAD
             // the three requested values become the compiler's HERE, behind the hand-written wait that covers them (a component copied
             // out of a vector that is still in flight was the one bug of this scheme: the first group of every block)
             asm volatile("" : "+v"(ray_o3), "+v"(ray_d3), "+v"(t_grp));
-#endif
             const float ox = ray_o3[0], oy = ray_o3[1], oz = ray_o3[2], dxr = ray_d3[0], dyr = ray_d3[1], dzr = ray_d3[2];
             const float tt = t_grp;
             const f32x2 cxy = (f32x2){ox, oy} + (f32x2){tt, tt} * (f32x2){dxr, dyr};
@@ -301,70 +246,27 @@ __global__ __launch_bounds__(512, 1) void triplane_walk2_kernel(FieldParams p) {
         //  single v_add per call.  Left to itself the compiler rebuilt the address from `tb`, `j` and the ray with 4-5 vector instructions per call --
         //  9 per tile on the issue port the matrix pipe shares.)
         const uint4* const rowbase = atab + gpt;
-#if TDGP_WALK2_ABL == 4
-        // timing experiment (wrong results): WHOLE-LINE gathers.  The two rays of a pair (lanes 8 p .. 8 p + 7) address the SAME texel with eight different 16-byte
-        // pieces: the first load of a tap takes the even ray's texel for both rays (the odd ray's lanes land on its second half), the second load -- 64 bytes on --
-        // the odd ray's (even lanes on the first half): 8 whole 128-B lines per instruction instead of 16 half lines.  The weight rows are not read; the odd ray's
-        // OFFSET rows travel in their place (same LDS reads, same registers), and the blend multiplies by their bits.  What it measures: the L1's tag rate.
-        const uint4* const rowbase_e = atab + (gpt & ~1);
-        const uint4* const rowbase_o = atab + (gpt | 1);
-        auto read_rows = [&](uint4 (&r)[3], int tb, int j, int which) {
-            const int so = __builtin_amdgcn_readfirstlane(tb * (6 * TP) + j * TS);
-            const uint4* const tab = (which ? rowbase_e : rowbase_o) + so;
-#pragma unroll
-            for (int pl = 0; pl < 3; pl++) r[pl] = tab[(pl * 2 + 1) * TP];
-        };
-#else
         auto read_rows = [&](uint4 (&r)[3], int tb, int j, int which) {                // which: 0 = weights, 1 = offsets
             const int so = __builtin_amdgcn_readfirstlane(tb * (6 * TP) + j * TS);
             const uint4* const tab = rowbase + so;
 #pragma unroll
             for (int pl = 0; pl < 3; pl++) r[pl] = tab[(pl * 2 + which) * TP];
         };
-#endif
-        auto issue = [&](f32x4 (&T)[3][4][FQ / 4], const uint4 (&o4)[3], uint32_t soff_b, const uint4 (&o4odd)[3]) {
+        auto issue = [&](f32x4 (&T)[3][4][FQ / 4], const uint4 (&o4)[3], uint32_t soff_b) {
 #pragma unroll
             for (int pl = 0; pl < 3; pl++) {
                 const uint32_t so = (uint32_t)__builtin_amdgcn_readfirstlane((int)(soff_b + (uint32_t)pl * plane_bytes));     // (an SGPR for the asm's "s" operand)
-#if TDGP_WALK2_ADDTID
                 const uint32_t ov[4] = {o4[pl].x, o4[pl].y, o4[pl].z, o4[pl].w};
-#else
-                const uint32_t ov[4] = {o4[pl].x + c4off, o4[pl].y + c4off, o4[pl].z + c4off, o4[pl].w + c4off};
-#endif
 #pragma unroll
                 for (int t = 0; t < 4; t++) {
-#if TDGP_WALK2_ASMLOAD
-#if TDGP_WALK2_ABL == 1                 // timing experiment: no tap loads at all (results are garbage)
-                    asm volatile("" : "=v"(T[pl][t][0]) : "v"(ov[t]), "s"(dsc), "s"(so));
-                    if constexpr (FQ / 4 > 1) asm volatile("" : "=v"(T[pl][t][FQ / 4 - 1]) : "v"(ov[t]), "s"(dsc), "s"(so));
-#elif TDGP_WALK2_ABL == 2               // timing experiment: every tap reads texel 0 of its plane (same instructions, L1-hot)
-                    asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(T[pl][t][0]) : "v"(tid_adj + 0u * ov[t]), "s"(dsc), "s"(so));
-                    if constexpr (FQ / 4 > 1) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:64" : "=v"(T[pl][t][FQ / 4 - 1]) : "v"(tid_adj + 0u * ov[t]), "s"(dsc), "s"(so));
-#elif TDGP_WALK2_ABL == 4               // timing experiment: whole-line gathers (see read_rows)
-                    { const uint32_t ovo[4] = {o4odd[pl].x, o4odd[pl].y, o4odd[pl].z, o4odd[pl].w};
-                    asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(T[pl][t][0]) : "v"(ov[t]), "s"(dsc), "s"(so));
-                    if constexpr (FQ / 4 > 1) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:64" : "=v"(T[pl][t][FQ / 4 - 1]) : "v"(ovo[t]), "s"(dsc), "s"(so)); }
-#elif TDGP_WALK2_ABL == 3               // timing experiment: half the bytes per load (dwordx2), same instruction count
-                    asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen" : "=v"(*(f32x2*)&T[pl][t][0]) : "v"(ov[t]), "s"(dsc), "s"(so));
-                    if constexpr (FQ / 4 > 1) asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen offset:64" : "=v"(*(f32x2*)&T[pl][t][FQ / 4 - 1]) : "v"(ov[t]), "s"(dsc), "s"(so));
-#else
                     asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(T[pl][t][0]) : "v"(ov[t]), "s"(dsc), "s"(so));
                     if constexpr (FQ / 4 > 1) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:64" : "=v"(T[pl][t][FQ / 4 - 1]) : "v"(ov[t]), "s"(dsc), "s"(so));
-#endif
-#else
-#pragma unroll
-                    for (int jj = 0; jj < FQ / 4; jj++) {
-                        const float4 v = buf_load4(rpl, ov[t] + 64u * jj, so);
-                        T[pl][t][jj] = (f32x4){v.x, v.y, v.z, v.w};
-                    }
-#endif
                 }
             }
         };
         // wait until at most NEWER vector-memory operations are outstanding, then hand the buffer to the compiler: every later use of a tap
         // register depends on one of these statements, and volatile asm statements keep their order
         auto await = [&](f32x4 (&T)[3][4][FQ / 4], auto newer) {
-#if TDGP_WALK2_ASMLOAD
             asm volatile("s_waitcnt vmcnt(%0)" :: "n"(decltype(newer)::value) : "memory");
 #pragma unroll
             for (int pl = 0; pl < 3; pl++) {
@@ -374,7 +276,6 @@ __global__ __launch_bounds__(512, 1) void triplane_walk2_kernel(FieldParams p) {
                 else
                     asm volatile("" : "+v"(T[pl][0][0]), "+v"(T[pl][1][0]), "+v"(T[pl][2][0]), "+v"(T[pl][3][0]));
             }
-#endif
         };
         // g[16 channels of a pass] = sum over 3 planes x 4 taps of weight * texel: ONE fma chain per channel pair in tap order 0..11 (the
         // order of triplane_walk_kernel), the NP * 2 chains of a tile interleaved so that no packed fma waits for its predecessor.
@@ -405,11 +306,11 @@ __global__ __launch_bounds__(512, 1) void triplane_walk2_kernel(FieldParams p) {
                     seen = lds_peek(ctr + 1);
                     if (n - seen < NS) break;
                     __builtin_amdgcn_s_sleep(8);
-                } while (++spin < TDGP_WALK2_SPIN);
+                } while (++spin < WALK2_SPIN);
                 // timeout: report and END THIS WAVE (the partner's own bounded wait then runs out once, ~2 ms, and it ends too).  No "stop
                 // waiting" state is carried through the loop: that state (and `seen` with it) lived in vector registers and cost ~8 vector
                 // instructions per tile on each side of the ring -- on an issue port the matrix pipe shares (round 5)
-                if (spin >= TDGP_WALK2_SPIN) { walk2_fault(p.fault, 1); asm volatile("s_endpgm"); }
+                if (spin >= WALK2_SPIN) { walk2_fault(p.fault, 1); asm volatile("s_endpgm"); }
             }
             float* dst = ring + slot * RT + ring_lane;
 #pragma unroll
@@ -423,9 +324,7 @@ __global__ __launch_bounds__(512, 1) void triplane_walk2_kernel(FieldParams p) {
 
         prefetch_group(0, 0);
         soff_cur = soff_nxt = soff_n2;
-#if TDGP_WALK2_ASMLOAD
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
         address_phase(0, 0);
         {                                                   // group 1 of this pair's march (the next patch's first group when a patch is one group)
             const int g1 = ngroups > 1 ? 1 : 0;
@@ -436,8 +335,8 @@ __global__ __launch_bounds__(512, 1) void triplane_walk2_kernel(FieldParams p) {
             uint4 o0[3], o1[3];
             read_rows(o0, 0, 0, 1);
             read_rows(o1, 0, 1, 1);
-            issue(tapA, o0, soff_cur, o0);
-            issue(tapB, o1, soff_cur, o1);
+            issue(tapA, o0, soff_cur);
+            issue(tapB, o1, soff_cur);
         }
         int gl = 0, pi = 0;                                 // group within the patch, patch index
         // Two tiles per iteration (buffers A and B), so that a loop body holds 48 + 3 loads -- inside what the hardware's 6-bit counter and
@@ -485,12 +384,12 @@ __global__ __launch_bounds__(512, 1) void triplane_walk2_kernel(FieldParams p) {
                 prefetch_group(pq, gq);
             }
             __builtin_amdgcn_sched_barrier(0);
-            issue(tapA, oA, soffn, wA);
+            issue(tapA, oA, soffn);
             __builtin_amdgcn_sched_barrier(0);
             await(tapB, std::integral_constant<int, 3 * FQ + 3>());  // younger than B's loads: the three small loads and A's 3 * FQ refills
             blend(tapB, wB, gv);
             __builtin_amdgcn_sched_barrier(0);
-            issue(tapB, oB, soffn, wB);
+            issue(tapB, oB, soffn);
             __builtin_amdgcn_sched_barrier(0);
             publish(gv);
             __builtin_amdgcn_sched_barrier(0);
@@ -504,7 +403,6 @@ __global__ __launch_bounds__(512, 1) void triplane_walk2_kernel(FieldParams p) {
 
     // ==================================================================== consumer
     {
-        if (TDGP_WALK2_PRIO < 0) __builtin_amdgcn_s_setprio(-TDGP_WALK2_PRIO);
         float4* const obuf = (float4*)(smem + L::off_obuf + pair * L::obuf_bytes);
         const int pt = l & 15, q = l >> 4;
         float a0r[MT * FQ], a1r[MT * 4];
@@ -533,8 +431,8 @@ __global__ __launch_bounds__(512, 1) void triplane_walk2_kernel(FieldParams p) {
                     seen = lds_peek(ctr + 0);
                     if (seen > want) break;
                     __builtin_amdgcn_s_sleep(1);
-                } while (++spin < TDGP_WALK2_SPIN);
-                if (spin >= TDGP_WALK2_SPIN) { walk2_fault(p.fault, 2); asm volatile("s_endpgm"); }     // see publish()
+                } while (++spin < WALK2_SPIN);
+                if (spin >= WALK2_SPIN) { walk2_fault(p.fault, 2); asm volatile("s_endpgm"); }     // see publish()
             }
             TDGP_ORDER();
 #pragma unroll
@@ -552,9 +450,6 @@ __global__ __launch_bounds__(512, 1) void triplane_walk2_kernel(FieldParams p) {
             TDGP_ORDER();
             const int nslot = slot + 1 == NS ? 0 : slot + 1;
             if (n + 1 < total) fetch(gn, n + 1, nslot);
-#ifdef TDGP_WALK2_YIELD
-            __builtin_amdgcn_s_sleep(TDGP_WALK2_YIELD);
-#endif
             f32x4 acc[MT];
 #pragma unroll
             for (int mt = 0; mt < MT; mt++) acc[mt] = b0r[mt];

@@ -29,21 +29,7 @@
 #include "common.h"
 #include <stdlib.h>
 
-// A/B switches for timing experiments (tools/dev/build_variant.sh); the defaults are the shipped code.
-#ifndef TDGP_AB_NO_SCALAR_WV
-#define TDGP_AB_NO_SCALAR_WV 0
-#endif
-#ifndef TDGP_AB_NO_PACKED_EPI
-#define TDGP_AB_NO_PACKED_EPI 0
-#endif
-#ifndef TDGP_AB_FIR_SERIAL
-#define TDGP_AB_FIR_SERIAL 0
-#endif
-#if TDGP_AB_NO_SCALAR_WV
-#define TDGP_WAVE_INDEX(tid) ((tid) >> 6)
-#else
 #define TDGP_WAVE_INDEX(tid) __builtin_amdgcn_readfirstlane((tid) >> 6)       // the wave index is uniform: keep it (and all tile arithmetic on it) scalar
-#endif
 
 namespace {
 
@@ -168,7 +154,7 @@ __device__ __forceinline__ int epi_variant(const EpiParams& e) {
 typedef float epi_f32x2 __attribute__((ext_vector_type(2)));
 template <int ACT>
 __device__ __forceinline__ float4 finish_act4(const EpiParams& e, float4 v, float d, float4 nz, float bb) {
-    if constexpr ((ACT == 1 || ACT == 3) && !TDGP_AB_NO_PACKED_EPI) {
+    if constexpr (ACT == 1 || ACT == 3) {
         const epi_f32x2 d2 = {d, d}, b2 = {bb, bb}, g2 = {e.gain, e.gain};
         epi_f32x2 lo = ((epi_f32x2){v.x, v.y} * d2 + (epi_f32x2){nz.x, nz.y}) + b2, hi = ((epi_f32x2){v.z, v.w} * d2 + (epi_f32x2){nz.z, nz.w}) + b2;
         if constexpr (ACT == 3) {
@@ -293,7 +279,7 @@ __device__ __forceinline__ void epilogue_tile(const EpiParams& e, const SideCach
         if (e.bias && okc) bias4 = make_float4(side_bias(e, sc, o, true), side_bias(e, sc, o + 1, true), side_bias(e, sc, o + 2, true), side_bias(e, sc, o + 3, true));
         // All 16 skip taps of the tile (4 passes x 4 texels, 16 B each) are put in flight BEFORE any of them is consumed, and
         // without per-pass branches: taken pass by pass, each pass waited out a full L2 round trip and the output stage was
-        // two thirds of the ToRGB kernel (per-phase cycle counts, TDGP_RGB_ABL=16).  Invalid lanes read a clamped address.
+        // two thirds of the ToRGB kernel (per-phase cycle counts).  Invalid lanes read a clamped address.
         float4 sk[4];
         int addr[4], bq[4];
         float nzq[4];
@@ -647,21 +633,12 @@ struct Conv3Params {
     uint32_t x_bytes, wp_bytes, st_bytes;       // sizes for the buffer descriptors
 };
 
-#ifndef TDGP_C3_ABL
-#define TDGP_C3_ABL 0      // 16: per-phase cycle counts of one wave, printed (timing experiments only)
-#endif
 template <int KS, int MTW, int NTW, int WM, int WN>
 __global__ __launch_bounds__(256, 2) void conv3_mfma_kernel(Conv3Params p) {
     constexpr int R = KS / 2, T = KS * KS;
     constexpr int BM = 32 * MTW * WM, NT = NTW * WN, PR = NT + 2 * R, PC = 32 + 2 * R, PSZ = PR * PC;
     constexpr int AS_SZ = T * BM * 4, XS_SZ = PSZ * 4, BUF_SZ = AS_SZ + XS_SZ;          // floats
     extern __shared__ __attribute__((aligned(16))) float smem[];
-#if TDGP_C3_ABL & 16
-    long long tq[6] = {0, 0, 0, 0, 0, 0}, tprev = __builtin_readcyclecounter();
-#define TQ(i) { const long long tn_ = __builtin_readcyclecounter(); tq[i] += tn_ - tprev; tprev = tn_; }
-#else
-#define TQ(i)
-#endif
     float* side = smem + 2 * BUF_SZ;                                // [1 + NSB][BM]: bias, demod coefficients of the tile's samples
 
     const int H1 = p.H + R;
@@ -722,7 +699,7 @@ __global__ __launch_bounds__(256, 2) void conv3_mfma_kernel(Conv3Params p) {
     constexpr int NA = (T * BM + 255) / 256;
     // Staging registers: weights one K iteration ahead (they come from L2), activations TWO iterations ahead in alternating
     // register sets -- at 64 channels the activation tensor streams from HBM, and with one iteration (4600 cycles) of flight
-    // time the LDS write waited ~8000 cycles per iteration for its loads (per-phase cycle counts, TDGP_C3_ABL=16).
+    // time the LDS write waited ~8000 cycles per iteration for its loads (per-phase cycle counts).
     float4 a_reg[NA], x_reg[2][NPOS], s_reg[2][NPOS];
     uint32_t a_vo[NA];
 #pragma unroll
@@ -806,35 +783,25 @@ __global__ __launch_bounds__(256, 2) void conv3_mfma_kernel(Conv3Params p) {
     load_x(it0 + 1, 1);
     if (it0 < it1) store_stage(0, L0, L0 + AS_SZ);
     __syncthreads();
-    TQ(0)
     int it = it0;
     for (; it + 1 < it1; it += 2) {
         // even half: L0 holds iteration `it`; x set 1 = iteration it+1 (in flight since the previous half)
         load_a(it + 1);
         load_x(it + 2, 0);
-        TQ(1)
         mma(0);
-        TQ(2)
         store_stage(1, L1, L1 + AS_SZ);
-        TQ(3)
         __syncthreads();
-        TQ(4)
         // odd half: L1 holds iteration it+1; x set 0 = iteration it+2
         load_a(it + 2);
         load_x(it + 3, 1);
-        TQ(1)
         mma(1);
-        TQ(2)
         if (it + 2 < it1) store_stage(0, L0, L0 + AS_SZ);
-        TQ(3)
         __syncthreads();
-        TQ(4)
     }
     if (it < it1) {                     // odd iteration count: the last one sits in L0 -- and the epilogue's per-wave tiles overlay the
         mma(0);                         // stage buffers: every wave must be done reading them (without this barrier a fast wave's
         __syncthreads();                // epilogue corrupted a slow wave's last fragments: rare, wave-tile-sized errors)
     }
-    TQ(2)
 
     // ---- epilogue: accumulators -> per-wave LDS tile -> epilogue_tile() (16-B stores, fused demod/noise/bias/act) ------------
     float* ct = smem + wv * (32 * CT_LD);
@@ -865,12 +832,6 @@ __global__ __launch_bounds__(256, 2) void conv3_mfma_kernel(Conv3Params p) {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
-    TQ(5)
-#if TDGP_C3_ABL & 16
-    if (tid == 0 && (blockIdx.x == 3 || blockIdx.x == 900) && blockIdx.y == 0 && blockIdx.z == 0)
-        printf("conv3 blk %d iters %d: prologue %lld load-issue %lld mma %lld store %lld barrier %lld epilogue %lld\n", (int)blockIdx.x, it1 - it0, tq[0], tq[1], tq[2], tq[3], tq[4], tq[5]);
-#endif
-#undef TQ
 }
 
 // ---- x2 layers: stride-2 transposed 3x3 convolution (conv2d_resample.py:108-125, unflipped weights) --------------------
@@ -896,9 +857,6 @@ struct UpParams {
     uint32_t x_bytes, wp_bytes, st_bytes;       // sizes for the buffer descriptors
 };
 
-#ifndef TDGP_UP_ABL
-#define TDGP_UP_ABL 0      // timing experiments (tools/dev/build_variant.sh): 1 no Z stores, 2 no global staging loads, 4 no LDS fragment reads, 8 no barriers
-#endif
 constexpr int UP_CT_W = 68;     // epilogue LDS tile: 32 channels x 64 floats (+4 pad)
 
 template <int MTW, int NTW, int WM, int WN, bool DEEP>
@@ -1039,9 +997,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : 2)) void upconv_mf
 
     float* const L0 = smem;
     float* const L1 = smem + BUF_SZ;
-#if TDGP_UP_ABL & 16
-    long long tseg[4] = {0, 0, 0, 0}, tprev = __builtin_readcyclecounter();
-#endif
     if constexpr (!DEEP) {
         // single register set: the loads of iteration i+1 fly while iteration i multiplies
         if (it0 < it1) { load_stage(it0, 0); store_stage(0, L0, L0 + AS_SZ); }
@@ -1061,12 +1016,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : 2)) void upconv_mf
     if (it0 < it1) store_stage(0, L0, L0 + AS_SZ);
     load_stage(it0 + 2, 0);
     __syncthreads();
-#if TDGP_UP_ABL & 16
-    tprev = __builtin_readcyclecounter();
-#define TSEG(i) { const long long tn = __builtin_readcyclecounter(); tseg[i] += tn - tprev; tprev = tn; }
-#else
-#define TSEG(i)
-#endif
     int it = it0;
     for (; it + 1 < it1; it += 2) {
         // even half: L0 holds iteration `it`; set 1 = iteration it+1, set 0 = iteration it+2 (both in flight).
@@ -1074,34 +1023,20 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : 2)) void upconv_mf
         //  a fixed number of loads per half-iteration and no exit in the middle of the body, the compiler's s_waitcnt in front of
         //  the LDS write is vmcnt(<one stage>) instead of the vmcnt(0) it falls back to otherwise, which un-did the second stage.)
         mma(0);
-        TSEG(0)
         store_stage(1, L1, L1 + AS_SZ);
-        TSEG(1)
         load_stage(it + 3, 1);
-        TSEG(2)
         __syncthreads();
-        TSEG(3)
         // odd half: L1 holds iteration it+1; set 0 = iteration it+2, set 1 = iteration it+3
         mma(1);
-        TSEG(0)
         if (it + 2 < it1) store_stage(0, L0, L0 + AS_SZ);
-        TSEG(1)
         load_stage(it + 4, 0);
-        TSEG(2)
         __syncthreads();
-        TSEG(3)
     }
     if (it < it1) {                     // odd iteration count: the last one sits in L0 -- and the epilogue's per-wave tiles overlay the
         mma(0);                         // stage buffers: every wave must be done reading them (without this barrier a fast wave's
         __syncthreads();                // epilogue corrupted a slow wave's last fragments: rare, wave-tile-sized errors)
     }
-    TSEG(0)
     }
-#if TDGP_UP_ABL & 16
-    if (tid == 0 && (blockIdx.x == 0 || blockIdx.x == 700) && blockIdx.y == 0 && blockIdx.z == 0)
-        printf("upconv blk %d iters %d: mma %lld store %lld load-issue %lld barrier %lld cycles\n", (int)blockIdx.x, it1 - it0, tseg[0], tseg[1], tseg[2], tseg[3]);
-#endif
-#undef TSEG
 
     // ---- epilogue: per (channel tile, point subtile, py): interleave px = 0/1 in a per-wave LDS tile, store 16 B per lane -----
     // Vector-ALU instructions of this stage queue behind the 64-cycle MFMAs of the SIMD's other waves (~60 cycles each), and with
@@ -1366,50 +1301,31 @@ __global__ __launch_bounds__(256, 2) void conv3s_mfma_kernel(Conv3sParams p) {
         }
     };
 
-#if TDGP_C3_ABL & 32
-    long long ts[5] = {0, 0, 0, 0, 0}, tprev = __builtin_readcyclecounter();
-#define TS(i) { const long long tn_ = __builtin_readcyclecounter(); ts[i] += tn_ - tprev; tprev = tn_; }
-#else
-#define TS(i)
-#endif
     // Two blocks per CU (LDS 75 KB each): one block's staging and barriers run under the other's MFMAs.  Per chunk of 16 channels:
     // the activation stage once, the weights one tap row at a time; one barrier per tap row, behind which the other weight buffer is
     // free for the next row's loads, which land under this row's MFMAs.
     load_x(0);
     load_a(0, 0);
-    TS(0)
     for (int it = 0; it < niter; it++) {
         const int g = 3 * it, b0 = g & 1;
         wait_loads();                           // tap row g has landed (and the activation registers)
         __syncthreads();                        // ... for every wave; the previous chunk's fragments have been read
-        TS(1)
         store_x(it);
-        TS(2)
         load_a(g + 1, b0 ^ 1);
         load_x(it + 1);                         // in flight during this chunk's MFMAs
-        TS(3)
         __syncthreads();
-        TS(1)
         mma_row(0, b0);
-        TS(4)
         wait_loads();
         __syncthreads();
-        TS(1)
         load_a(g + 2, b0);
-        TS(3)
         mma_row(1, b0 ^ 1);
-        TS(4)
         wait_loads();
         __syncthreads();
-        TS(1)
         load_a(g + 3, b0 ^ 1);
-        TS(3)
         mma_row(2, b0);
-        TS(4)
     }
     wait_loads();
     __syncthreads();
-    TS(0)
 
     float* ct = smem + wv * (32 * CT_LD);
     const EpiParams& e = p.e;
@@ -1438,12 +1354,6 @@ __global__ __launch_bounds__(256, 2) void conv3s_mfma_kernel(Conv3sParams p) {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
-#if TDGP_C3_ABL & 32
-    TS(1)
-    if (tid == 0 && (blockIdx.x == 3 || blockIdx.x == 400) && blockIdx.y == 0)
-        printf("conv3s blk %d iters %d: prologue %lld barrier+epilogue %lld store(+load wait) %lld load-issue %lld mma %lld\n", (int)blockIdx.x, niter, ts[0], ts[1], ts[2], ts[3], ts[4]);
-#endif
-#undef TS
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -1608,43 +1518,25 @@ __global__ __launch_bounds__(256, 2) void upconv3s_mfma_kernel(Up3sParams p) {
 
     // Tap row g (global index 3 * chunk + ky) lives in buffer g & 1.  One barrier per tap row: behind it every wave has finished the
     // previous row, so the other buffer is free for the LDS-direct loads of the next row, which land under this row's MFMAs.
-#if TDGP_C3_ABL & 32
-    long long ts[6] = {0, 0, 0, 0, 0, 0}, tprev = __builtin_readcyclecounter();
-#define TS(i) { const long long tn_ = __builtin_readcyclecounter(); ts[i] += tn_ - tprev; tprev = tn_; }
-#else
-#define TS(i)
-#endif
     load_a(0, 0);
     load_x(0);
-    TS(0)
     for (int it = 0; it < niter; it++) {
         const int g = 3 * it, b0 = g & 1;
         wait_loads();                           // tap row g, the chunk's activations and styles have landed
         lds_barrier();                          // ... for every wave; the previous chunk's fragments have been read
-        TS(1)
         store_x(it);
-        TS(2)
         load_a(g + 1, b0 ^ 1);                  // lands under tap row g's MFMAs
-        TS(3)
         lds_barrier();                          // the split activations are in place, Xraw is free again
-        TS(1)
         mma_row(R0, b0);
-        TS(4)
         wait_loads();
         lds_barrier();
-        TS(1)
         load_a(g + 2, b0);
         load_x(it + 1);                         // younger than the weight loads: the wait below leaves them in flight
-        TS(3)
         mma_row(R1, b0 ^ 1);
-        TS(4)
         if (wv == 0) __builtin_amdgcn_s_waitcnt(0x4F79); else __builtin_amdgcn_s_waitcnt(0x4F70);       // vmcnt(25 | 16): tap row g+2 has landed
         lds_barrier();
-        TS(1)
         load_a(g + 3, b0 ^ 1);
-        TS(3)
         mma_row(R2, b0);
-        TS(4)
     }
     wait_loads();
     __syncthreads();                                                // every wave is done with the stage buffers the tiles below overlay
@@ -1699,12 +1591,6 @@ __global__ __launch_bounds__(256, 2) void upconv3s_mfma_kernel(Up3sParams p) {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
-#if TDGP_C3_ABL & 32
-    TS(5)
-    if (tid == 0 && (blockIdx.x == 3 || blockIdx.x == 400) && blockIdx.y == 0)
-        printf("upconv3s blk %d iters %d: prologue %lld wait+barrier %lld store %lld load-issue %lld mma %lld epilogue %lld\n", (int)blockIdx.x, niter, ts[0], ts[1], ts[2], ts[3], ts[4], ts[5]);
-#endif
-#undef TS
 }
 
 // weight [Cout,Cin,3,3] -> split pack [chunk16][tap][piece][CoutP][16 bf16] (zero beyond Cout / Cin)
@@ -1733,8 +1619,8 @@ __global__ __launch_bounds__(256) void pack_split_kernel(const float* __restrict
 // (upfirdn2d.py:313-348), * gain, clamp, channel-last float4 stores.  lane = (pixel l>>3 of the pass, channel quad l&7).
 // One straight-line block -- 16 tap loads, 4 LDS reads, the math, 4 stores -- with selects instead of branches: with the
 // run-time activation switch of the generic epilogue in here the compiler put a full `s_waitcnt vmcnt(0)` in front of every
-// store, i.e. each of the 12 stores of a 128-pixel tile waited for the acknowledgement of the one before (per-phase counters,
-// TDGP_RGB_ABL=16: output stage 24-36 k cycles per tile against 6 k of MFMA).  ToRGB is linear and has no noise / demodulation.
+// store, i.e. each of the 12 stores of a 128-pixel tile waited for the acknowledgement of the one before (per-phase counters:
+// output stage 24-36 k cycles per tile against 6 k of MFMA).  ToRGB is linear and has no noise / demodulation.
 // What is left is vector-ALU instruction count: while the SIMD's other wave is in its MFMA phase an instruction of this stage
 // gets in once per 64-cycle MFMA, so the blend runs as v_pk_fma_f32 (two channels per slot, the same fma chain per element),
 // gain / clamp are compiled out when they are 1 / off (PLAIN), and for power-of-two images (POW2: lw = log2 W, lhw = log2 HW)
@@ -1783,14 +1669,8 @@ __device__ __forceinline__ void rgb_output_tile(const EpiParams& e, const float*
         if (SKIP) {
             tp[pass] = skip_taps(h2, w2, oy, ox, e.fir);
             const float* sp = e.skip + (int64_t)plane * h2 * w2 * e.out_feat + f;
-#if TDGP_RGB_ABL & 32                   // timing experiment: the taps from LDS (whatever sits there) -- what an LDS-staged texel tile could cost at best
-            const float4* lt = (const float4*)bias_lds;
-            ta[pass] = lt[(tp[pass].i00 * 3 + cg) & 63]; tb[pass] = lt[(tp[pass].i01 * 3 + cg) & 63];
-            tc[pass] = lt[(tp[pass].i10 * 3 + cg) & 63]; td[pass] = lt[(tp[pass].i11 * 3 + cg) & 63];
-#else
             ta[pass] = *(const float4*)(sp + (int64_t)tp[pass].i00 * e.out_feat); tb[pass] = *(const float4*)(sp + (int64_t)tp[pass].i01 * e.out_feat);
             tc[pass] = *(const float4*)(sp + (int64_t)tp[pass].i10 * e.out_feat); td[pass] = *(const float4*)(sp + (int64_t)tp[pass].i11 * e.out_feat);
-#endif
         }
     }
     float4 v[G];
@@ -1837,14 +1717,9 @@ __device__ __forceinline__ void rgb_output_tile(const EpiParams& e, const float*
 // trip but the first runs under two batches of arithmetic and stores.  Same taps, same fma chains, same bits.
 typedef float rgb_f32x4 __attribute__((ext_vector_type(4)));
 // PARKED: all MT channel tiles already sit in LDS, tile k at ct + k * 32 * CT_LD (torgb_ws_kernel: another wave put them there); else `acc` is parked tile by tile into `ct`.
-#ifndef TDGP_RGB_PRE_STREAMED
-#define TDGP_RGB_PRE_STREAMED 1        // per-pass geometry once per tile in the streamed one-role kernels too (A/B builds)
-#endif
-#ifndef TDGP_RGB_NSET_STREAMED
-#define TDGP_RGB_NSET_STREAMED 5       // register sets of taps in the one-role kernels that stream their weights (they have registers to spare; A/B builds)
-#endif
-// B0, B1 (PARKED only): the batches [B0, B1) of the tile's 4 MT -- the two roles of torgb_ws_kernel share a tile's stage.
-template <int MT, bool PLAIN, bool PARKED = false, int NSET1 = 3, bool PRE1 = false, int B0 = 0, int B1 = 4 * MT>
+constexpr int RGB_NSET_STREAMED = 5;   // register sets of taps in the one-role kernels that stream their weights (they have registers to spare)
+constexpr int RGB_WS_NSET = 6;         // register sets of taps of the memory waves of the two-role kernel
+template <int MT, bool PLAIN, bool PARKED = false, int NSET1 = 3, bool PRE1 = false>
 __device__ __forceinline__ void rgb_output_skip_pipelined(const EpiParams& e, const float* __restrict__ bias_lds, float* ct, f32x16 (&acc)[MT], int64_t pix0, int64_t P, int lw, int lhw) {
     const int l = lane_id(), cg = l & 7, pr = l >> 3, l32 = l & 31, half = l >> 5;
     const int planes = e.Cout / e.out_feat, h2 = e.Hout / 2, w2 = e.Wout / 2;
@@ -1859,13 +1734,9 @@ __device__ __forceinline__ void rgb_output_skip_pipelined(const EpiParams& e, co
     FirRegs fr = {e.fir[0], e.fir[1], e.fir[2], e.fir[3], e.fir[4], e.fir[5], e.fir[6], e.fir[7], e.fir[8], e.fir[9], e.fir[10], e.fir[11], e.fir[12], e.fir[13], e.fir[14], e.fir[15]};
     asm volatile("" : "+s"(fr.f0), "+s"(fr.f1), "+s"(fr.f2), "+s"(fr.f3), "+s"(fr.f4), "+s"(fr.f5), "+s"(fr.f6), "+s"(fr.f7));
     asm volatile("" : "+s"(fr.f8), "+s"(fr.f9), "+s"(fr.f10), "+s"(fr.f11), "+s"(fr.f12), "+s"(fr.f13), "+s"(fr.f14), "+s"(fr.f15));
-#ifndef TDGP_RGB_WS_NSET
-#define TDGP_RGB_WS_NSET 6
-#endif
     // a batch = one pass (8 pixels x 32 channels per wave): 4 tap loads, one store; NSET register sets = NSET - 1 batches of look-ahead (three sets in the one-role
     // kernels, which sit at their register limit; six for the memory waves of the two-role kernel, whose whole stage is these round trips)
-    constexpr int NSET = PARKED ? (B1 - B0 < TDGP_RGB_WS_NSET ? (B1 - B0 > 1 ? B1 - B0 : 2) : TDGP_RGB_WS_NSET) : NSET1, NB = B1;
-    static_assert(PARKED || (B0 == 0 && B1 == 4 * MT), "a batch sub-range needs the parked form");
+    constexpr int NB = 4 * MT, NSET = PARKED ? (NB < RGB_WS_NSET ? NB : RGB_WS_NSET) : NSET1;
     rgb_f32x4 tA[NSET][4];
     // (pixel geometry, tap indices and weights are RECOMPUTED where the batch is finished -- two dozen scalar-ish vector instructions per pass -- instead of
     //  carried beside the taps: registers the kernel does not have)
@@ -1980,9 +1851,9 @@ __device__ __forceinline__ void rgb_output_skip_pipelined(const EpiParams& e, co
     };
     static_assert(NSET >= 2 && NSET <= 6, "wait counts are spelled out for up to five batches of look-ahead");
 #pragma unroll
-    for (int bi = B0; bi < B0 + NSET - 1 && bi < NB; bi++) issue(bi);
+    for (int bi = 0; bi < NSET - 1 && bi < NB; bi++) issue(bi);
 #pragma unroll
-    for (int bi = B0; bi < NB; bi++) {
+    for (int bi = 0; bi < NB; bi++) {
         if (!PARKED && (bi & 3) == 0) {
             // this channel tile's accumulators -> the wave's pixel-major LDS tile (wave-private: a wave barrier orders it against the previous tile's reads)
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -2023,12 +1894,6 @@ struct RgbParams {
     int lw, lhw;        // log2 W, log2 H*W when both are powers of two, else -1
 };
 
-#ifndef TDGP_FIR_ADJ
-#define TDGP_FIR_ADJ 1      // FIR pass of the wide x2 layers: 4 adjacent rows per thread (0: two rows eight apart, the r02 form)
-#endif
-#ifndef TDGP_RGB_ABL
-#define TDGP_RGB_ABL 0     // 16: per-phase cycle counts of one wave, printed; 32: skip taps from LDS (timing experiments only)
-#endif
 // RESIDENT: Cin <= 64 -- the whole weight matrix is one LDS stage, loaded once per block, and the block walks `tpb` consecutive
 // tiles with the activations of tile t+1 in flight while tile t is multiplied and stored.
 // FAST: power-of-two image, no clamp, gain 1 (the generator's ToRGB layers) -- the trimmed output stage.
@@ -2042,22 +1907,13 @@ __global__ __launch_bounds__(256, 2) void torgb_mfma_kernel(RgbParams p) {
     float* side = smem + AS_SZ + XS_SZ;                             // [BM] bias
     const int tid = threadIdx.x, l = tid & 63, wv = TDGP_WAVE_INDEX(tid), l32 = l & 31, half = l >> 5;     // wave index: scalar
     const int64_t ntiles = (p.P + BN - 1) / BN;
-#ifndef TDGP_RGB_XCD_COMPACT
-#define TDGP_RGB_XCD_COMPACT 1          // 0: block b takes tiles b * tpb .. (A/B builds)
-#endif
     // Blocks b, b + 8, ... share an XCD (round-robin dispatch: a locality hint, not a contract).  XCD-compact order: XCD x walks the x-th EIGHTH of the
     // tiles, so blocks that run next to each other in time on one XCD -- one L2 -- take vertically adjacent rows of the image: the two / three skip rows
     // an output row pair blends are then fetched into that L2 once instead of once per XCD that happens to hold a neighbour (round 5 counters: the
     // skip image came through the memory side 4.4 times, fetch 1.93 x the algorithmic bytes).  Same tiles, same arithmetic per tile.
     const int64_t nb_ = gridDim.x;
-    const int64_t lb_ = (TDGP_RGB_XCD_COMPACT && (nb_ & 7) == 0 && nb_ >= 64) ? (int64_t)(blockIdx.x & 7) * (nb_ >> 3) + (blockIdx.x >> 3) : (int64_t)blockIdx.x;
+    const int64_t lb_ = ((nb_ & 7) == 0 && nb_ >= 64) ? (int64_t)(blockIdx.x & 7) * (nb_ >> 3) + (blockIdx.x >> 3) : (int64_t)blockIdx.x;
     const int64_t t_begin = lb_ * p.tpb, t_end = min(t_begin + p.tpb, ntiles);
-#if TDGP_RGB_ABL & 16
-    long long tq[5] = {0, 0, 0, 0, 0}, tprev = __builtin_readcyclecounter();
-#define TR(i) { const long long tn_ = __builtin_readcyclecounter(); tq[i] += tn_ - tprev; tprev = tn_; }
-#else
-#define TR(i)
-#endif
 
     for (int i = tid; i < BM; i += 256) side[i] = (i < p.Cout && p.e.bias) ? p.e.bias[i] : 0.f;
 
@@ -2163,16 +2019,13 @@ __global__ __launch_bounds__(256, 2) void torgb_mfma_kernel(RgbParams p) {
         for (int i = 0; i < NA; i++)
             if (tid + i * 256 < NCH * BM) *(float4*)(As + (tid + i * 256) * 4) = a_reg[i];
     }
-    TR(0)
     for (int64_t t = t_begin; t < t_end; t++) {
         for (int it = 0; it < niter; it++) {
             __syncthreads();                        // the previous stage's fragments (and the previous tile's parked outputs) have been read
             store_stage(!RESIDENT);
             __syncthreads();
-            TR(1)
             // the next stage -- of this tile, or the first one of the next tile -- is in flight during the multiply and the output stage
             if (it + 1 < niter) load_stage(it + 1, true);
-            TR(2)
             f32x2 fa[2][MT], fb[2];
             auto load_frag = [&](int buf, int ch) {
 #pragma unroll
@@ -2190,7 +2043,6 @@ __global__ __launch_bounds__(256, 2) void torgb_mfma_kernel(RgbParams p) {
 #pragma unroll
                     for (int m = 0; m < MT; m++) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cb][m][kk], fb[cb][kk], acc[m], 0, 0, 0);
             }
-            TR(3)
         }
         // the next tile's activations are put in flight here, after the multiply (issued before it, the loads land in registers
         // the fragment reads want and the compiler parks them with a full wait) and ahead of the output stage that hides them
@@ -2216,11 +2068,8 @@ __global__ __launch_bounds__(256, 2) void torgb_mfma_kernel(RgbParams p) {
             }
         }
         const int64_t pix0 = t * BN + wv;
-#ifndef TDGP_RGB_PIPELINED
-#define TDGP_RGB_PIPELINED 1           // 0: the stage per channel tile (rounds 2-6; A/B builds, same bits)
-#endif
-        if (TDGP_RGB_PIPELINED && FAST && has_skip) {
-            rgb_output_skip_pipelined<MT, true, false, RESIDENT ? 3 : TDGP_RGB_NSET_STREAMED, !RESIDENT && TDGP_RGB_PRE_STREAMED>(p.e, side, ct, acc, pix0, p.P, p.lw, p.lhw);
+        if (FAST && has_skip) {
+            rgb_output_skip_pipelined<MT, true, false, RESIDENT ? 3 : RGB_NSET_STREAMED, !RESIDENT>(p.e, side, ct, acc, pix0, p.P, p.lw, p.lhw);
         } else
 #pragma unroll 1
         for (int tile = 0; tile < MT; tile++) {
@@ -2237,7 +2086,7 @@ __global__ __launch_bounds__(256, 2) void torgb_mfma_kernel(RgbParams p) {
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
             constexpr int G = 4;
-            if constexpr (!(TDGP_RGB_PIPELINED && FAST)) {
+            if constexpr (!FAST) {
                 if (has_skip) rgb_output_tile<true, FAST, !LANE_GEOM, G>(p.e, side, ct, tile * 32, pb, poy, pox, pok, pix0, p.P, p.lw, p.lhw);
                 else rgb_output_tile<false, FAST, !LANE_GEOM, G>(p.e, side, ct, tile * 32, pb, poy, pox, pok, pix0, p.P, p.lw, p.lhw);
             } else {
@@ -2246,14 +2095,8 @@ __global__ __launch_bounds__(256, 2) void torgb_mfma_kernel(RgbParams p) {
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
         }
-        TR(4)
         if (!RESIDENT) break;                       // one tile per block (tpb = 1): nothing stays live across the output stage
     }
-#if TDGP_RGB_ABL & 16
-    if (tid == 0 && (blockIdx.x == 5 || blockIdx.x == 1000))
-        printf("torgb blk %d tiles %d iters %d: prologue+issue %lld wait+store %lld issue-next %lld mma %lld epilogue %lld\n", (int)blockIdx.x, (int)(t_end - t_begin), niter, tq[0], tq[1], tq[2], tq[3], tq[4]);
-#endif
-#undef TR
 }
 
 // ---- ToRGB, two roles per block (round 6): Cin <= 64 (weights resident), power-of-two image, gain 1, no clamp, with a skip -- the 512^2 layer of C3 / C4 ----
@@ -2262,12 +2105,8 @@ __global__ __launch_bounds__(256, 2) void torgb_mfma_kernel(RgbParams p) {
 // the layer's 1.05, the MFMAs alone 0.33).  Here a block is 8 waves, one per CU: waves 0..3 MULTIPLY tile t (fragments from LDS, nothing else), waves 4..7 do everything
 // of the output stage of tile t - 1 -- 48 tap loads, 12 stores per wave, from the LDS tile the multipliers parked, with the per-pass geometry computed once per tile --; the
 // multipliers also carry tile t + 1's activations (requested before the multiply, staged into the other X buffer behind it).  One of each role per SIMD, two block barriers per tile.  Same fragments, same K order, same fma chains as torgb_mfma_kernel: same bits.
-#ifndef TDGP_RGB_WS_SHARE
-#define TDGP_RGB_WS_SHARE 0            // batches of a tile's output stage (of 4 MT) the MULTIPLYING waves take, in front of their multiply.  Measured (512^2, B = 16): 0 -> 1.00-1.01 ms, 2 -> 1.03-1.04, 3 -> 1.05-1.06: the memory waves keep all of it
-#endif
-#ifndef TDGP_RGB_WS_ABL
-#define TDGP_RGB_WS_ABL 0              // timing experiments (wrong results): 1 = no output stage, 2 = no multiply
-#endif
+// (Measured, 512^2, B = 16: the MULTIPLYING waves taking 2 / 3 batches of a tile's output stage (of 4 MT) in front of their multiply: 1.00-1.01 ms -> 1.03-1.04 / 1.05-1.06:
+// the memory waves keep all of it.)
 template <int MT>
 __global__ __launch_bounds__(512, 1) void torgb_ws_kernel(RgbParams p) {
     constexpr int BM = 32 * MT, BN = 128, NCH = 16;
@@ -2349,13 +2188,7 @@ __global__ __launch_bounds__(512, 1) void torgb_ws_kernel(RgbParams p) {
     const int n = (int)(t_end - t_begin);
     for (int i = 0; i < n; i++) {
         const int64_t t = t_begin + i;
-        constexpr int NBT = 4 * MT, SPLIT = NBT - (TDGP_RGB_WS_SHARE < MT ? TDGP_RGB_WS_SHARE : MT);       // (at most a quarter of the batches)
         if (role == 0) {
-            // the last batches of tile t - 1's output stage (the memory waves' 0.76 ms against the multipliers' 0.58: the multipliers wait at the barrier otherwise)
-            if (SPLIT < NBT && i > 0 && !(TDGP_RGB_WS_ABL & 1)) {
-                f32x16 none[MT];
-                rgb_output_skip_pipelined<MT, true, true, 3, false, SPLIT, NBT>(p.e, side, ctw, none, (t - 1) * BN + wj, p.P, p.lw, p.lhw);
-            }
             // tile t + 1's activations travel under this tile's multiply (the block's last tile re-reads itself: no load under a condition)
             tile_offsets(t + 1 < t_end ? t + 1 : t);
             load_x();
@@ -2369,7 +2202,7 @@ __global__ __launch_bounds__(512, 1) void torgb_ws_kernel(RgbParams p) {
             };
             load_frag(0, 0);
 #pragma unroll
-            for (int ch = 0; ch < ((TDGP_RGB_WS_ABL & 2) ? 1 : NCH); ch++) {
+            for (int ch = 0; ch < NCH; ch++) {
                 const int cb = ch & 1;
                 if (ch + 1 < NCH) load_frag(cb ^ 1, ch + 1);
                 __builtin_amdgcn_sched_barrier(0);
@@ -2380,9 +2213,9 @@ __global__ __launch_bounds__(512, 1) void torgb_ws_kernel(RgbParams p) {
             }
             store_x((i + 1) & 1);                   // (nobody reads that buffer before the barriers below: tile t - 1's multiply ended an iteration ago)
         } else {
-            if (i > 0 && !(TDGP_RGB_WS_ABL & 1)) {
+            if (i > 0) {
                 f32x16 none[MT];
-                rgb_output_skip_pipelined<MT, true, true, 3, false, 0, SPLIT>(p.e, side, ctw, none, (t - 1) * BN + wj, p.P, p.lw, p.lhw);
+                rgb_output_skip_pipelined<MT, true, true>(p.e, side, ctw, none, (t - 1) * BN + wj, p.P, p.lw, p.lhw);
             }
         }
         __syncthreads();                            // the multipliers are through with X[i & 1] and have written X[(i + 1) & 1]; tile t - 1's parked outputs have been read
@@ -2398,10 +2231,8 @@ __global__ __launch_bounds__(512, 1) void torgb_ws_kernel(RgbParams p) {
         __syncthreads();                            // tile t's outputs are parked
     }
     {
-        constexpr int NBT = 4 * MT, SPLIT = NBT - (TDGP_RGB_WS_SHARE < MT ? TDGP_RGB_WS_SHARE : MT);       // (at most a quarter of the batches)
         f32x16 none[MT];
-        if (role == 1) rgb_output_skip_pipelined<MT, true, true, 3, false, 0, SPLIT>(p.e, side, ctw, none, (t_end - 1) * BN + wj, p.P, p.lw, p.lhw);
-        else if (SPLIT < NBT) rgb_output_skip_pipelined<MT, true, true, 3, false, SPLIT, NBT>(p.e, side, ctw, none, (t_end - 1) * BN + wj, p.P, p.lw, p.lhw);
+        if (role == 1) rgb_output_skip_pipelined<MT, true, true>(p.e, side, ctw, none, (t_end - 1) * BN + wj, p.P, p.lw, p.lhw);
     }
 }
 
@@ -2484,7 +2315,7 @@ __global__ __launch_bounds__(256) void fir_act_kernel(FirParams p) {
             if (nz_vec && oy < p.OH) nzv[hrow] = *(const float4*)(p.noise + b * p.noise_bstride + (int64_t)oy * p.OW + ox0 + lx);
         }
         __syncthreads();
-        if (p.ksplit == 1 && !TDGP_AB_FIR_SERIAL) {
+        if (p.ksplit == 1) {
             // no split-K slices to add: all (at most 3) window vectors of a thread are put in flight before the first is written to
             // LDS.  One load per thread at a time left 8 blocks x 4 KB in flight per CU -- by Little's law ~4 TB/s, which is where
             // the kernel sat.

@@ -3,39 +3,18 @@
 // call takes, decided once and read by the workspace query, the shape queries and the launch --, the workspace layout, one builder per
 // parameter struct, one launcher per path, the exported entry points.
 
-// ---- compile-time defaults of the host side (tools/dev/build_variant.sh -D...) ----
-// F(4x4): the batch goes through the two kernels in sub-batches whose V fits one buffer descriptor (< 4 GiB; TDGP_WINO4_VCAP_MB lowers the cap for
-// experiments): C4's 512^2 x 128 layer at B = 16 has 4.8 GB of V.  The sub-batches share one V buffer (stream order).
-#ifndef TDGP_WINO4_VCAP_MB
-#define TDGP_WINO4_VCAP_MB 4095
-#endif
+// ---- thresholds of the host side ----
+// F(4x4): the batch goes through the two kernels in sub-batches whose V fits one buffer descriptor (< 4 GiB):
+// C4's 512^2 x 128 layer at B = 16 has 4.8 GB of V.  The sub-batches share one V buffer (stream order).
+constexpr int W4_VCAP_MB = 4095;
 // Layers with few channels move 2.25 x their input through V for little arithmetic: there a sub-batch whose V stays inside the 256 MB
-// Infinity Cache between the two kernels (TDGP_WINO4_VSMALL_MB) beats one big launch (measured B = 16: 256^2 x 128 1.38 (one sample per launch) /
+// Infinity Cache between the two kernels (W4_VSMALL_MB) beats one big launch (measured B = 16: 256^2 x 128 1.38 (one sample per launch) /
 // 1.22 (two) / 1.25 (three) ms; 128^2 x 256 0.93 -> 1.03 ms -- hence Cin <= 128 only, and at least two samples per launch).
-#ifndef TDGP_WINO4_VSMALL_MB
-#define TDGP_WINO4_VSMALL_MB 192
-#endif
-#ifndef TDGP_WINO4_VSMALL_MINB
-#define TDGP_WINO4_VSMALL_MINB 2          // fewest samples per launch on that path (1: A/B builds)
-#endif
-#ifndef TDGP_WINO4_SPLITK
-#define TDGP_WINO4_SPLITK 1               // 0: no K split of the F(4x4) launches with too few items (wino4_ksplit_log2)
-#endif
-#ifndef TDGP_WINO4_PAIR
-#define TDGP_WINO4_PAIR 1          // 1: the 8-wave form (a slice x a pair of tile groups per block, three V stages; modconv_wino4.inc)
-#endif
-// Winograd F(2x2) kernel (modconv_wino.inc): below TDGP_WINO_MIN_CIN the direct kernel's staging economy wins (K = Cin per position instead
+constexpr int W4_VSMALL_MB = 192;
+constexpr int W4_VSMALL_MINB = 2;         // fewest samples per launch on that path
+// Winograd F(2x2) kernel (modconv_wino.inc): below WINO_MIN_CIN the direct kernel's staging economy wins (K = Cin per position instead
 // of 9 Cin); measured per layer, see DESIGN.md.
-#ifndef TDGP_WINO_MIN_CIN
-#define TDGP_WINO_MIN_CIN 64
-#endif
-#ifndef TDGP_RGB_WS
-#define TDGP_RGB_WS 1                  // 0: torgb_mfma_kernel for every layer (A/B builds, same bits)
-#endif
-// timing experiment (tools/dev/build_variant.sh): extra dynamic LDS per block = fewer resident blocks per CU.  0 in the shipped library.
-#ifndef TDGP_RGB_LDS_PAD
-#define TDGP_RGB_LDS_PAD 0
-#endif
+constexpr int WINO_MIN_CIN = 64;
 
 namespace {
 
@@ -63,7 +42,7 @@ inline PackInfo pack_info(int Cout, int Cin, int k) {
     pi.nch8 = (Cin + 7) / 8;
     pi.wino_floats = k == 3 ? (int64_t)pi.nch8 * 16 * 2 * pi.CoutP * 4 : 0;          // Winograd-domain weights G g G^T (modconv_wino.inc)
     pi.nch4 = (Cin + 3) / 4; pi.nsl64 = (Cout + 63) / 64;
-    pi.wino4_floats = (k == 3 && Cin >= TDGP_WINO4_MIN_C && Cout >= TDGP_WINO4_MIN_C) ? (int64_t)cdiv(Cout, W4_BM) * pi.nch4 * W4_UCH : 0;      // F(4x4,3x3)-domain weights (modconv_wino4.inc)
+    pi.wino4_floats = (k == 3 && Cin >= W4_MIN_C && Cout >= W4_MIN_C) ? (int64_t)cdiv(Cout, W4_BM) * pi.nch4 * W4_UCH : 0;      // F(4x4,3x3)-domain weights (modconv_wino4.inc)
     pi.wp = 0;
     pi.wsq = pi.wp + pi.wp_floats;
     pi.wsplit = pi.wsq + pi.wsq_floats;
@@ -164,7 +143,7 @@ void launch_upconv(const UpParams& u, hipStream_t s) {
 template <int MT, bool RESIDENT, bool FAST, bool XBF>
 void launch_torgb_v(const RgbParams& r, hipStream_t s) {
     constexpr int BM = 32 * MT;
-    const size_t lds = (size_t)(16 * BM * 4 + 16 * 128 * 4 + BM) * sizeof(float) + TDGP_RGB_LDS_PAD;
+    const size_t lds = (size_t)(16 * BM * 4 + 16 * 128 * 4 + BM) * sizeof(float);
     TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)torgb_mfma_kernel<MT, RESIDENT, FAST, XBF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds););
     // RESIDENT: several consecutive tiles per block once there are more tiles than ~4 rounds of the 512 resident blocks
     RgbParams rr = r;
@@ -172,7 +151,7 @@ void launch_torgb_v(const RgbParams& r, hipStream_t s) {
     if constexpr (RESIDENT && FAST && !XBF) {
         // the two-role form: enough tiles for >= 16 per block on a grid of four blocks per CU (C3 / C4: the 512^2 layer; at B = 1 the 512^2 layer still has 2048 tiles)
         const int cus = tdgp_cu_count();
-        if (TDGP_RGB_WS && r.e.skip && ntiles >= (int64_t)cus * 8) {
+        if (r.e.skip && ntiles >= (int64_t)cus * 8) {
             constexpr size_t lds_ws = (size_t)(16 * BM * 4 + 2 * 16 * 128 * 4 + 4 * MT * 32 * CT_LD + BM) * sizeof(float);
             TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)torgb_ws_kernel<MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ws););
             const int64_t blocks = (int64_t)cus * 4;
@@ -232,17 +211,17 @@ inline int wino4_txl(int H, int W) { return (W & 63) == 0 && (H & 7) == 0 ? 4 : 
 inline int64_t wino4_items(int bs, int Cout, int H, int W) { return (int64_t)bs * ((H * W) >> 9) * cdiv(Cout, 64); }
 inline int wino4_sub_batch(int B, int Cin, int Cout, int H, int W) {
     const int64_t per = wino4_v_bytes(1, Cin, H, W);
-    if (Cin <= 128 && TDGP_WINO4_VSMALL_MB > 0) {
-        const int bs = (int)std::min<int64_t>(B, ((int64_t)TDGP_WINO4_VSMALL_MB << 20) / per);
-        if (bs >= TDGP_WINO4_VSMALL_MINB && wino4_items(bs, Cout, H, W) >= 256) return bs;      // (one sample per launch -- 512^2 x 64: 151 MB of V next to 134 MB of x and y -- does not stay in the cache anyway: 1.84 vs 1.77 ms for the whole batch at once)
+    if (Cin <= 128) {
+        const int bs = (int)std::min<int64_t>(B, ((int64_t)W4_VSMALL_MB << 20) / per);
+        if (bs >= W4_VSMALL_MINB && wino4_items(bs, Cout, H, W) >= 256) return bs;      // (one sample per launch -- 512^2 x 64: 151 MB of V next to 134 MB of x and y -- does not stay in the cache anyway: 1.84 vs 1.77 ms for the whole batch at once)
     }
-    return (int)std::min<int64_t>(B, ((int64_t)TDGP_WINO4_VCAP_MB << 20) / per);
+    return (int)std::min<int64_t>(B, ((int64_t)W4_VCAP_MB << 20) / per);
 }
 // Launches with too few items for the chip (the 32^2 layers at batch 4 .. 8) split the input channels of every item 2 or 4 ways (plain layers
 // only; >= 16 chunks per split; the whole batch in one launch); the splits' raw sums go through the split-K buffer of the direct kernels.
 // 0 = not a split-K shape.  B = 4, 32^2 x 512: direct sums 0.235 ms -> 4 splits (measured, DESIGN.md).
 inline int wino4_ksplit_log2(int B, int Cin, int Cout, int H, int W) {
-    if (!TDGP_WINO4_SPLITK || wino4_v_bytes(B, Cin, H, W) > ((int64_t)TDGP_WINO4_VSMALL_MB << 20)) return 0;
+    if (wino4_v_bytes(B, Cin, H, W) > ((int64_t)W4_VSMALL_MB << 20)) return 0;
     const int64_t base = wino4_items(B, Cout, H, W);
     const int nch = Cin >> 2;
     for (int l = 1; l <= 2; l++)
@@ -250,7 +229,7 @@ inline int wino4_ksplit_log2(int B, int Cin, int Cout, int H, int W) {
     return 0;
 }
 inline bool wino4_shape_ok(int B, int Cin, int Cout, int H, int W, int k, int up, bool plain = false) {
-    if (!(k == 3 && up == 1 && wino4_txl(H, W) != 0 && (Cin & 3) == 0 && Cin >= TDGP_WINO4_MIN_C && Cout >= TDGP_WINO4_MIN_C)) return false;
+    if (!(k == 3 && up == 1 && wino4_txl(H, W) != 0 && (Cin & 3) == 0 && Cin >= W4_MIN_C && Cout >= W4_MIN_C)) return false;
     const int bs = wino4_sub_batch(B, Cin, Cout, H, W);
     if (bs >= 1 && wino4_items(bs, Cout, H, W) >= 256) return true;
     return plain && wino4_items(B, Cout, H, W) < 256 && wino4_ksplit_log2(B, Cin, Cout, H, W) > 0;
@@ -260,7 +239,7 @@ inline bool wino4_shape_ok(int B, int Cin, int Cout, int H, int W, int k, int up
 inline size_t wino_lds_bytes(int) { return (size_t)(2 * 8192 + 2 * 8192 + 2 * 8 * 10 * 48 + 128) * 4; }
 inline bool wino_ok(int B, int Cin, int Cout, int H, int W) {
     // (fewer than one block per CU: the direct kernel's split-K fills the chip better)
-    return (W & 31) == 0 && (H & 7) == 0 && (Cin & 7) == 0 && Cin >= TDGP_WINO_MIN_CIN && wino_lds_bytes(Cin) <= 160 * 1024 &&
+    return (W & 31) == 0 && (H & 7) == 0 && (Cin & 7) == 0 && Cin >= WINO_MIN_CIN && wino_lds_bytes(Cin) <= 160 * 1024 &&
            (int64_t)(W >> 5) * (H >> 3) * B * cdiv(Cout, 64) >= 256;
 }
 
@@ -306,8 +285,8 @@ inline int64_t splitk_floats(int64_t out_elems) {
 enum FirTile { FIR_32x128_ADJ, FIR_16x128_LRELU, FIR_16x128, FIR_32x64 };
 inline int fir_tile(int OH, int OW, int ksplit, int act, float alpha, bool bf16_out) {
     const bool lrelu = act == 3 && alpha >= 0.f && alpha <= 1.f;
-    if (!bf16_out && TDGP_FIR_ADJ && OW >= 128 && (OH & 31) == 0 && ksplit == 1 && lrelu) return FIR_32x128_ADJ;
-    if (OW >= 128 && (bf16_out || !TDGP_AB_FIR_SERIAL)) return lrelu ? FIR_16x128_LRELU : FIR_16x128;
+    if (!bf16_out && OW >= 128 && (OH & 31) == 0 && ksplit == 1 && lrelu) return FIR_32x128_ADJ;
+    if (OW >= 128) return lrelu ? FIR_16x128_LRELU : FIR_16x128;
     return FIR_32x64;
 }
 
@@ -333,7 +312,7 @@ ConvPlan plan_modconv(const ConvCall& c) {
         const bool w4_weights = pack_info(Cout, Cin, k).wino4_floats > 0;
         if (k == 3 && c.arith == 1 && (W >> 5) * cdiv(B * (H + 1), 8) * cdiv(Cout, 64) >= 256 && c.has_styles && (Cin & 15) == 0 && Cin <= 2048 && H >= 16) {
             p.path = TDGP_PATH_SPLIT3;
-        } else if (c.arith == 0 && TDGP_WINO4F_MAXCIN > 0 && c.out_layout == 0 && Cin <= TDGP_WINO4F_MAXCIN && (Cin & 15) == 0 && (Cout & 63) == 0 && wino4_txl(H, W) == 4 &&
+        } else if (c.arith == 0 && c.out_layout == 0 && Cin <= W4F_MAXCIN && (Cin & 15) == 0 && (Cout & 63) == 0 && wino4_txl(H, W) == 4 &&
                    wino4_shape_ok(B, Cin, Cout, H, W, k, up) && w4_weights && (int64_t)B * ((H * W) >> 9) * (Cout >> 6) >= 256 && !c.has_skip && c.aligned16) {
             // few input channels (the 256^2 / 512^2 blocks): the input transform runs inside the GEMM kernel, V never leaves the CU (modconv_wino4f.inc)
             p.path = TDGP_PATH_WINO4F;
@@ -579,11 +558,9 @@ void launch_wino4(const ConvLaunch& L) {
     const PackInfo& pi = L.pi;
     const EpiParams& e = L.e;
     const int B = c.B, Cin = c.Cin, Cout = c.Cout, H = c.H, W = c.W, ksl = L.plan.ksl, bsub = L.plan.bsub;
-    constexpr bool pairk = TDGP_WINO4_PAIR && W4_BM == 32;
-    const int bpc = (W4_BM == 64 || pairk) ? 1 : 2;                 // resident blocks per CU
-    const XcdRect r = xcd_rect(cdiv(Cout, W4_BM) << ksl, bpc, W4_BM, pairk ? 64 : 32);       // (tiles per item: 64 for a pair of tile groups)
-    const size_t lds = pairk ? (size_t)(8 * W4_UCH + 3 * W4_BM + 4) * 4 : (size_t)(2 * W4_STAGE + 2 * W4_BM + 4) * 4;          // the stages, bias + demodulation of the slice, the ticket
-    TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)conv3_wino4_kernel<false, pairk>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); (void)hipFuncSetAttribute((const void*)conv3_wino4_kernel<true, pairk>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds););
+    const XcdRect r = xcd_rect(cdiv(Cout, W4_BM) << ksl, 1, W4_BM, 64);       // (one resident block per CU; tiles per item: 64 for a pair of tile groups)
+    const size_t lds = (size_t)(8 * W4_UCH + 3 * W4_BM + 4) * 4;          // the stages, bias + demodulation of the slice, the ticket
+    TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)conv3_wino4_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); (void)hipFuncSetAttribute((const void*)conv3_wino4_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds););
     float* vbuf = L.vbuf();
     float* partial = L.partial();
     int* ticket = ticket_ptr(L.ws, L.wl);
@@ -604,8 +581,8 @@ void launch_wino4(const ConvLaunch& L) {
         const int ntg = q.gxn * q.gyn * bn;
         TDGP_LAUNCH("wino4_input_kernel", wino4_input_kernel, dim3((unsigned)(ntg * pi.nch4)), dim3(128), 0, L.s, L.x + (int64_t)b0 * Cin * H * W,
                     L.styles ? L.styles + (int64_t)b0 * Cin : nullptr, vbuf, bn, Cin, H, W, q.gxn, q.gyn, pi.nch4, q.txl, ticket);
-        if (q.ups) TDGP_LAUNCH("upconv_wino4_kernel", (conv3_wino4_kernel<true, pairk>), dim3((unsigned)(r.nxcd * r.per)), dim3(pairk ? 512 : W4_NW * 64), lds, L.s, q);
-        else TDGP_LAUNCH("conv_wino4_kernel", (conv3_wino4_kernel<false, pairk>), dim3((unsigned)(r.nxcd * r.per)), dim3(pairk ? 512 : W4_NW * 64), lds, L.s, q);
+        if (q.ups) TDGP_LAUNCH("upconv_wino4_kernel", (conv3_wino4_kernel<true, true>), dim3((unsigned)(r.nxcd * r.per)), dim3(512), lds, L.s, q);
+        else TDGP_LAUNCH("conv_wino4_kernel", (conv3_wino4_kernel<false, true>), dim3((unsigned)(r.nxcd * r.per)), dim3(512), lds, L.s, q);
         if (ksl) TDGP_LAUNCH("splitk_reduce_kernel", splitk_reduce_kernel, dim3((int)min((int64_t)2048, cdiv64(kslice, 256))), dim3(256), 0, L.s, partial, 1 << ksl, e);
     }
 }
@@ -619,12 +596,9 @@ void launch_wino2(const ConvLaunch& L) {
     q.x_bytes = L.x_bytes(); q.u_bytes = (uint32_t)(L.pi.wino_floats * 4);
     const size_t lds = wino_lds_bytes(Cin);
     TDGP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)conv3_wino_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024););
-    if (TDGP_WINO_PERSIST) {
-        const int cus = tdgp_cu_count();
-        const int64_t nitems = (int64_t)(W >> 5) * (H >> 3) * B * cdiv(Cout, 64);
-        TDGP_LAUNCH("conv_wino_kernel", conv3_wino_kernel, dim3((unsigned)min((int64_t)cus, nitems)), dim3(512), lds, L.s, q);
-    } else
-        TDGP_LAUNCH("conv_wino_kernel", conv3_wino_kernel, dim3((W >> 5) * (H >> 3) * B, cdiv(Cout, 64)), dim3(512), lds, L.s, q);
+    const int cus = tdgp_cu_count();
+    const int64_t nitems = (int64_t)(W >> 5) * (H >> 3) * B * cdiv(Cout, 64);
+    TDGP_LAUNCH("conv_wino_kernel", conv3_wino_kernel, dim3((unsigned)min((int64_t)cus, nitems)), dim3(512), lds, L.s, q);
 }
 
 // transposed conv, stride 2, UNFLIPPED weights (conv2d_resample.py:108-125) -> parity-planar Z -> FIR + output stage

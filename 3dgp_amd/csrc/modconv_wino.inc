@@ -23,15 +23,6 @@
 // (e)), so the transform is priced in matrix time: ~100 vector instructions against 32 x 64 cycles per chunk and wave.
 // Staging per FLOP is 3.4x the direct kernel's (K = Cin per position instead of 9 Cin): 47 KB per block and chunk from L2.
 
-// Compile-time ablations for timing experiments (tools/dev/build_variant.sh): 1 = no input transform, 2 = no global loads / stage stores,
-// 4 = no MFMAs.  Always 0 in the shipped library.
-#ifndef TDGP_WINO_PERSIST
-#define TDGP_WINO_PERSIST 1      // 0: one block per (tile, channel slice) item on a 2-D grid (the round-2 launch)
-#endif
-#ifndef TDGP_WINO_PRIO
-#define TDGP_WINO_PRIO 0
-#endif
-
 struct WinoParams {
     const float* x; const float* u; const float* styles;
     EpiParams e;
@@ -132,7 +123,7 @@ __global__ __launch_bounds__(512, 1) void conv3_wino_kernel(WinoParams p) {
             }
         }
     };
-    const int item0 = TDGP_WINO_PERSIST ? (int)blockIdx.x : (int)(blockIdx.y * gridDim.x + blockIdx.x), istep = TDGP_WINO_PERSIST ? (int)gridDim.x : nitems;
+    const int item0 = (int)blockIdx.x, istep = (int)gridDim.x;
     if (item0 < nitems) { setup_item(item0); load_u(0); load_x(0); }
   for (int item = item0; item < nitems; item += istep) {
     const int bx = item % nbx, tx = bx % tilesX, ty = (bx / tilesX) % tilesY, b = bx / (tilesX * tilesY);
@@ -246,13 +237,7 @@ __global__ __launch_bounds__(512, 1) void conv3_wino_kernel(WinoParams p) {
         if (g1) __syncthreads();
         const int cm = c + (g1 ? 1 : 0);
         if (cm < nchunk) {
-#if TDGP_WINO_PRIO
-            __builtin_amdgcn_s_setprio(TDGP_WINO_PRIO);      // the multiplying wave goes first; the staging wave fills its gaps
-#endif
             mma_chunk(cm & 1);
-#if TDGP_WINO_PRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
         }
     }
     if (!g1) __syncthreads();

@@ -18,12 +18,12 @@
 //     exchange, no barrier in the output stage -- and a lane ends up with 4 channels x one 4x4-pixel tile, stored as 16-byte rows
 //     (16 lanes = 64 consecutive pixels).
 //
-// Block shapes (BM = TDGP_WINO4_BM output channels per slice; 32 since the barrier measurements of round 4):
+// Block shapes (BM = W4_BM output channels per slice; 32 since the barrier measurements of round 4):
 //   * 4 waves, two blocks per CU: a slice x one tile group of 32 tiles (2 x 16 tiles = 8 x 64 pixels, or 4 x 8 tiles for the 32-pixel-wide layers); wave w
 //     takes channel half w & 1 of tile half w >> 1.  Per 4-channel chunk the block needs U [9 position quads][4 k][32 channels][4] (18 432 B) and
 //     V [9][4 k][32 tiles][4] (18 432 B), both contiguous in global memory in exactly this order (pack_wino4_kernel / wino4_input_kernel write them so):
 //     36 wave-wide 1-KB LDS-direct loads per chunk, two stages of 36 864 B;
-//   * PAIR (the default, TDGP_WINO4_PAIR in modconv.hip): 8 waves, one block per CU: a slice x a PAIR of tile groups sharing the U stages, V three stages
+//   * PAIR (the form the launcher instantiates): 8 waves, one block per CU: a slice x a PAIR of tile groups sharing the U stages, V three stages
 //     deep (see the kernel).
 // A lane's operands of four positions are ONE ds_read_b128 (conflict-free: the 16-lane groups of a 16-byte read cover 16 distinct 16-byte bank slots);
 // position PAIRS read as ds_read_b64 were merged by the compiler into ds_read2st64_b64, which runs at half the LDS rate.  Persistent blocks; items are
@@ -107,18 +107,14 @@ __device__ __forceinline__ w4_f2 finish_pair(const EpiParams& e, w4_f2 v, w4_f2 
     return x * (w4_f2){e.gain, e.gain};
 }
 
-#ifndef TDGP_WINO4_MIN_C
-#define TDGP_WINO4_MIN_C 64         // (below: the direct / F(2x2) kernels)
-#endif
-#ifndef TDGP_WINO4_BM
-#define TDGP_WINO4_BM 32           // output channels per block: 32 = 4 waves, two blocks per CU (measured: see the kernel); 64 = 8 waves, one block per CU
-#endif
-constexpr int W4_BM = TDGP_WINO4_BM, W4_NW = W4_BM / 8;                 // waves per block = (BM / 16 channel groups) x 2 tile rows
+constexpr int W4_MIN_C = 64;        // fewest input / output channels (below: the direct / F(2x2) kernels)
+constexpr int W4_BM = 32;           // output channels per slice (measured: see the kernel)
+constexpr int W4_NW = W4_BM / 8;    // waves per block of the 4-wave form = (BM / 16 channel groups) x 2 tile rows
 constexpr int W4_UCH = 9 * 4 * W4_BM * 4, W4_VCH = 9 * 4 * 32 * 4;     // floats per chunk
-constexpr int W4_UP = W4_UCH / 256, W4_PAD = W4_BM == 64 ? 2 : 0;       // 1-KB pieces of U; pad pieces so that every wave issues the same number
-constexpr int W4_NPW = (W4_UP + 18 + W4_PAD) / W4_NW;                   // pieces per wave and chunk (7 / 9)
-constexpr int W4_STAGE = W4_UCH + W4_VCH + W4_PAD * 256;
-static_assert((W4_UP + 18 + W4_PAD) % W4_NW == 0 && (W4_BM == 32 || W4_BM == 64), "wino4: piece count");
+constexpr int W4_UP = W4_UCH / 256;                                     // 1-KB pieces of U
+constexpr int W4_NPW = (W4_UP + 18) / W4_NW;                            // pieces per wave and chunk (9)
+constexpr int W4_STAGE = W4_UCH + W4_VCH;
+static_assert((W4_UP + 18) % W4_NW == 0, "wino4: piece count");
 
 // weight [Cout,Cin,3,3] -> U [slice][chunk][xi4 9][k 4][cp BM][4]: U_xi = (G g G^T)[i][j], xi = 6 i + j = 4 xi4 + e, channel = 4 chunk + k,
 // out-channel = BM slice + cp; zero beyond Cout / Cin.  Computed in double, rounded once.
@@ -196,7 +192,7 @@ __global__ __launch_bounds__(128) void wino4_input_kernel(const float* __restric
 // (tools/dev/ubench_ldsdma3.hip: a second chunk of look-ahead for V is worth 12-15 % when V comes from beyond the L2).  LDS: U [2][4608] floats,
 // V [3][2 tile groups][4608], side: bias [BM], demodulation [2][BM], the ticket.  The waits count on LDS-direct loads completing in issue order.
 template <bool UPS, bool PAIR = false>
-__global__ __launch_bounds__(PAIR ? 512 : W4_NW * 64, PAIR ? 1 : (W4_BM == 64 ? 1 : 2)) void conv3_wino4_kernel(Wino4Params p) {
+__global__ __launch_bounds__(PAIR ? 512 : W4_NW * 64, PAIR ? 1 : 2) void conv3_wino4_kernel(Wino4Params p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const uint32_t lds0 = TDGP_LDS_BASE(smem);
     float* side = smem + (PAIR ? 8 * W4_UCH : 2 * W4_STAGE);     // [0..BM) bias, [BM..2 BM) demodulation coefficients (PAIR: [BM .. 3 BM): one set per tile group)
@@ -228,7 +224,7 @@ __global__ __launch_bounds__(PAIR ? 512 : W4_NW * 64, PAIR ? 1 : (W4_BM == 64 ? 
     auto dma = [&](const w4_u32x4& d, uint32_t lds_dst, uint32_t voff, uint32_t soff) {
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(lds_dst), "v"(voff), "s"(d), "s"(soff) : "memory");
     };
-    // the pieces of a chunk (BM = 64: 36 of U, 18 of V, 2 pad pieces that re-read V's last one; BM = 32: 18 + 18): wave w issues pieces
+    // the pieces of a chunk (18 of U + 18 of V): wave w issues pieces
     // q = w + NW i.  Pieces i <= 3 are U, i >= 5 are V, i = 4 is U for the first half of the waves and V for the second: the descriptor / chunk
     // offset of that one are selected once.
     uint32_t pv[W4_NPW];                            // per-lane global offsets inside the chunk
@@ -279,20 +275,13 @@ __global__ __launch_bounds__(PAIR ? 512 : W4_NW * 64, PAIR ? 1 : (W4_BM == 64 ? 
         vo1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(v_base1 + (uint32_t)cv * (W4_VCH * 4u)));
     };
     const uint32_t ldsU = lds0, ldsV = lds0 + 2u * (W4_UCH * 4u);
-#ifndef TDGP_W4_EARLY_BARRIER
-#define TDGP_W4_EARLY_BARRIER 0        // A/B builds of the pair form's K loop (same bits), see there.  0 = the shipped form
-#endif
-    auto pair_first = [&](int nck) {                // an item's first chunks at once: U(0), V(0), V(1) (form 3: U(1) as well)
+    auto pair_first = [&](int nck) {                // an item's first chunks at once: U(0), V(0), V(1)
         pair_offsets(0, 0);
 #pragma unroll
         for (int i = 0; i < 3; i++) if (i < 2 || wvx < 2) pairU(i, ldsU);
 #pragma unroll
         for (int i = 0; i < 5; i++) if (i < 4 || wvx < 4) pairV(i, ldsV);
         pair_offsets(nck > 1 ? 1 : 0, nck > 1 ? 1 : 0);
-        if (TDGP_W4_EARLY_BARRIER == 3) {
-#pragma unroll
-            for (int i = 0; i < 3; i++) if (i < 2 || wvx < 2) pairU(i, ldsU + (W4_UCH * 4u));
-        }
 #pragma unroll
         for (int i = 0; i < 5; i++) if (i < 4 || wvx < 4) pairV(i, ldsV + 2u * (W4_VCH * 4u));
     };
@@ -334,12 +323,6 @@ __global__ __launch_bounds__(PAIR ? 512 : W4_NW * 64, PAIR ? 1 : (W4_BM == 64 ? 
         set_bases(sl, tg);
         if (PAIR) pair_first(nchk); else issue(0, 0);
     }
-#ifndef TDGP_W4_TRACE
-#define TDGP_W4_TRACE 0                // development: cycles per phase of the item loop (wave 0), written over the first floats of y when the block is done (tools/dev/trace_w4.py)
-#endif
-    uint64_t tr_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tr_last = 0;
-    auto tr_mark = [&](int i) { if (TDGP_W4_TRACE) { const uint64_t n = __builtin_amdgcn_s_memtime(); tr_t[i] += n - tr_last; tr_last = n; } };
-    if (TDGP_W4_TRACE) tr_last = __builtin_amdgcn_s_memtime();
     while (have) {
         const int tgw = PAIR ? min(2 * tg + hsel, ntg1 - 1) : tg;     // this wave's tile group
         const bool tg_ok = !PAIR || 2 * tg + hsel < ntg1;
@@ -358,13 +341,11 @@ __global__ __launch_bounds__(PAIR ? 512 : W4_NW * 64, PAIR ? 1 : (W4_BM == 64 ? 
         f32x4 acc[36];
 #pragma unroll
         for (int i = 0; i < 36; i++) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        tr_mark(0);
         wait_loads();
         lds_barrier();
-        tr_mark(1);
         if constexpr (PAIR) {
             // Round 6 asked whether the 0.3 k cycles a chunk takes beyond its 2.30 k of MFMAs (cycle counters) are the LDS round trip of the next chunk's first fragments behind
-            // the barrier.  TDGP_W4_EARLY_BARRIER builds run the fragment pipeline THROUGH the chunk boundary: the wait + barrier stand in front of group 7 (2) or 8 (1) -- the
+            // the barrier.  Three A/B forms ran the fragment pipeline THROUGH the chunk boundary: the wait + barrier stand in front of group 7 (2) or 8 (1) -- the
             // chunk's last fragments are in registers by then, nobody reads its stages any more -- and the groups behind it prefetch groups 0, 1 of the next chunk under their
             // own MFMAs; the wait's arithmetic is unchanged (4 V pieces of groups 3..6 may fly).  Measured (x2 and plain layers of C3, interleaved A/B): form 2 is 3-5 % SLOWER
             // -- the U pieces requested at groups 0..2 have not landed by group 7: a chunk is about as long as an LDS-direct load takes --, form 1 +1 %; form 3 (form 2 with
@@ -376,59 +357,34 @@ __global__ __launch_bounds__(PAIR ? 512 : W4_NW * 64, PAIR ? 1 : (W4_BM == 64 ? 
                 fa[q] = *(const float4*)(ust_ + g * (16 * W4_BM) + a_lane);
                 fb[q] = *(const float4*)(vst_ + g * 512 + b_lane);
             };
-            if (TDGP_W4_EARLY_BARRIER) {
-                frags_at(smem, smem + 2 * W4_UCH + hsel * W4_VCH, 0, 0);
-                frags_at(smem, smem + 2 * W4_UCH + hsel * W4_VCH, 1, 1);
-            }
             for (int c = 0; c < nchk; c++) {
                 const float* ust = smem + (c & 1) * W4_UCH;
                 const float* vst = smem + 2 * W4_UCH + (vs * 2 + hsel) * W4_VCH;
                 const uint32_t nus = ldsU + (uint32_t)((c + 1) & 1) * (W4_UCH * 4u);
                 const int vs1 = vs == 2 ? 0 : vs + 1;     // (c + 1) % 3
                 const int vs2 = vs == 0 ? 2 : vs - 1;     // (c + 2) % 3
-                const float* ust1 = smem + ((c + 1) & 1) * W4_UCH;
-                const float* vst1 = smem + 2 * W4_UCH + (vs1 * 2 + hsel) * W4_VCH;
                 const uint32_t nvs = ldsV + (uint32_t)vs2 * (2u * W4_VCH * 4u);
-                const uint32_t cus = ldsU + (uint32_t)(c & 1) * (W4_UCH * 4u);       // form 3: this chunk's own U stage, free behind its barrier, takes U(c + 2)
-                if (TDGP_W4_EARLY_BARRIER == 3) pair_offsets(c + 2 < nchk ? c + 2 : nchk - 1, c + 2 < nchk ? c + 2 : nchk - 1);
-                else pair_offsets(c + 1 < nchk ? c + 1 : c, c + 2 < nchk ? c + 2 : nchk - 1);
-                if (!TDGP_W4_EARLY_BARRIER) {
-                    frags_at(ust, vst, 0, 0);
-                    frags_at(ust, vst, 1, 1);
-                }
+                pair_offsets(c + 1 < nchk ? c + 1 : c, c + 2 < nchk ? c + 2 : nchk - 1);
+                frags_at(ust, vst, 0, 0);
+                frags_at(ust, vst, 1, 1);
 #pragma unroll
                 for (int g = 0; g < 9; g++) {
-                    if (TDGP_W4_EARLY_BARRIER && g == (TDGP_W4_EARLY_BARRIER == 3 ? 7 : 9 - TDGP_W4_EARLY_BARRIER)) {
-                        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");      // U(c + 1) and the older V(c + 1) have landed; the four V(c + 2) pieces of groups 3..6 may be in flight
-                        lds_barrier();
-                    }
                     if (g + 2 < 9) frags_at(ust, vst, g + 2, (g + 2) % 3);
-                    else if (TDGP_W4_EARLY_BARRIER >= 2) frags_at(ust1, vst1, g + 2 - 9, (g + 2) % 3);     // (the last chunk reads a stage nobody needs: no branch in the loop)
-                    else if (TDGP_W4_EARLY_BARRIER == 1 && g == 8) { frags_at(ust1, vst1, 0, 0); frags_at(ust1, vst1, 1, 1); }
                     __builtin_amdgcn_sched_barrier(0);
                     const float4 a = fa[g % 3], bb = fb[g % 3];
                     acc[4 * g + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, bb.x, acc[4 * g + 0], 0, 0, 0);
                     acc[4 * g + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, bb.y, acc[4 * g + 1], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                     // U of the next chunk first, then V of the chunk after: the wait lets exactly the V pieces fly
-                    if (TDGP_W4_EARLY_BARRIER == 3) {
-                        // V(c + 2) pieces 0..3 in front of the barrier (the four the wait lets fly), piece 4 and the U(c + 2) pieces behind it: U has a whole chunk to land again
-                        if (g >= 3 && (g < 7 || (g == 7 && wvx < 4))) pairV(g - 3, nvs);
-                        if (g == 7) pairU(0, cus);
-                        if (g == 8) { pairU(1, cus); if (wvx < 2) pairU(2, cus); }
-                    } else {
-                        if (g < 2 || (g == 2 && wvx < 2)) pairU(g, nus);
-                        if (g >= 3 && (g < 7 || (g == 7 && wvx < 4))) pairV(g - 3, nvs);
-                    }
+                    if (g < 2 || (g == 2 && wvx < 2)) pairU(g, nus);
+                    if (g >= 3 && (g < 7 || (g == 7 && wvx < 4))) pairV(g - 3, nvs);
                     __builtin_amdgcn_sched_barrier(0);
                     acc[4 * g + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, bb.z, acc[4 * g + 2], 0, 0, 0);
                     acc[4 * g + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, bb.w, acc[4 * g + 3], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                if (!TDGP_W4_EARLY_BARRIER) {
-                    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");      // U(c + 1) and the older V(c + 1) have landed; the four (five: then one more) V(c + 2) pieces may be in flight
-                    lds_barrier();
-                }
+                asm volatile("s_waitcnt vmcnt(4)" ::: "memory");      // U(c + 1) and the older V(c + 1) have landed; the four (five: then one more) V(c + 2) pieces may be in flight
+                lds_barrier();
                 vs = vs1;
             }
             wait_loads();
@@ -467,12 +423,11 @@ __global__ __launch_bounds__(PAIR ? 512 : W4_NW * 64, PAIR ? 1 : (W4_BM == 64 ? 
             wait_loads();
             lds_barrier();
         }
-        tr_mark(2);
         // the next item's first chunk travels under the output stage (both stages are free: the loop ended on a barrier)
         // The item's noise, fetched HERE -- before the ticket hand-over and the next item's requests -- and complete before those requests are issued.  Why: on
         // this ISA stores count in vmcnt and may complete out of order with loads, so a load between two stores is answered with `vmcnt(0)`: the x2 output stage
         // (per output row: two noise loads, two stores) ran as EIGHT full round trips per item, each also waiting for the next item's first chunks (cycle
-        // counters, tools/dev/trace_w4.py: 11-12 k cycles per item, 11 % of the 256^2 -> 512^2 layer).  Plain layers: 4 rows in registers.  x2 layers, pair form:
+        // counters: 11-12 k cycles per item, 11 % of the 256^2 -> 512^2 layer).  Plain layers: 4 rows in registers.  x2 layers, pair form:
         // the lane fetches rows 2 kq, 2 kq + 1 of its tile's 8 x 8 block (the four lanes kq of a tile share it) and parks them in the wave's 4 KB of V stage 2
         // -- free from the K loop's last barrier until the next item's third chunk is requested --, [row 8][tile 16][8 floats]; the output stage reads rows from LDS
         // and holds no vector-memory load at all.
@@ -496,7 +451,6 @@ __global__ __launch_bounds__(PAIR ? 512 : W4_NW * 64, PAIR ? 1 : (W4_BM == 64 ? 
         }
         int nsl_ = 0, ntg_ = 0;
         const bool more = acquire(t_next, true, nsl_, ntg_);
-        tr_mark(3);
         // (UNCONDITIONAL, zeros when the layer has no noise: under a second `if (noise)` the compiler cannot pair the loads with their use and guards every later
         //  reuse of their registers with `vmcnt(3)` -- behind the requests below, i.e. waiting for them; seen in the first build's ISA)
         if constexpr (NZ_LDS) {
@@ -512,7 +466,6 @@ __global__ __launch_bounds__(PAIR ? 512 : W4_NW * 64, PAIR ? 1 : (W4_BM == 64 ? 
             set_bases(nsl_, ntg_);
             if (PAIR) pair_first(nchk); else issue(0, 0);
         }
-        tr_mark(4);
         // ---- output transform Y = A^T M A in registers; lane = (4 channels 16 cg + 4 kq + r, tile (tr, l15)) ----
         {
             // noise of output row r (0..7) of the lane's 8 x 8 block, x2 layers
@@ -676,23 +629,16 @@ __global__ __launch_bounds__(PAIR ? 512 : W4_NW * 64, PAIR ? 1 : (W4_BM == 64 ? 
                     }
                 }
             };
-#ifndef TDGP_WINO4_PACKED_EPI
-#define TDGP_WINO4_PACKED_EPI 1        // 0: the per-channel output stage of rounds 4-5 (A/B builds; same bits)
-#endif
             const int evar = epi_variant(p.e);
             if (!UPS && p.ksl > 0) write_partial();
             else
             if constexpr (UPS) {
-                if (TDGP_WINO4_PACKED_EPI && evar == 3) write_up_pk(std::integral_constant<int, 3>{});
-                else if (TDGP_WINO4_PACKED_EPI && evar == 1) write_up_pk(std::integral_constant<int, 1>{});
-                else if (evar == 3) write_up(std::integral_constant<int, 3>{});
-                else if (evar == 1) write_up(std::integral_constant<int, 1>{});
+                if (evar == 3) write_up_pk(std::integral_constant<int, 3>{});
+                else if (evar == 1) write_up_pk(std::integral_constant<int, 1>{});
                 else write_up(std::integral_constant<int, 0>{});
             } else {
-                if (TDGP_WINO4_PACKED_EPI && evar == 3) write_outputs_pk(std::integral_constant<int, 3>{});
-                else if (TDGP_WINO4_PACKED_EPI && evar == 1) write_outputs_pk(std::integral_constant<int, 1>{});
-                else if (evar == 3) write_outputs(std::integral_constant<int, 3>{});
-                else if (evar == 1) write_outputs(std::integral_constant<int, 1>{});
+                if (evar == 3) write_outputs_pk(std::integral_constant<int, 3>{});
+                else if (evar == 1) write_outputs_pk(std::integral_constant<int, 1>{});
                 else write_outputs(std::integral_constant<int, 0>{});
             }
             // the noise rows are USED here whatever path ran: a load still pending at the loop's back edge makes the compiler guard its destination registers with
@@ -700,13 +646,7 @@ __global__ __launch_bounds__(PAIR ? 512 : W4_NW * 64, PAIR ? 1 : (W4_BM == 64 ? 
             // also wait for the V pieces the hand-counted vmcnt(4) lets fly)
             asm volatile("" :: "v"(nz[0].x), "v"(nz[0].w), "v"(nz[1].x), "v"(nz[1].w), "v"(nz[2].x), "v"(nz[2].w), "v"(nz[3].x), "v"(nz[3].w));
         }
-        tr_mark(5);
         lds_barrier();                               // `side` is free for the next item
-        tr_mark(6);
-        if (TDGP_W4_TRACE) tr_t[7] += 1;
         have = more; sl = nsl_; tg = ntg_;
-    }
-    if (TDGP_W4_TRACE && tid == 0) {
-        for (int i = 0; i < 8; i++) ((uint32_t*)p.e.y)[blockIdx.x * 8 + i] = (uint32_t)tr_t[i];
     }
 }

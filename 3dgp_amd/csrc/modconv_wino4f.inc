@@ -36,13 +36,7 @@ struct Wino4fParams {
     int* ticket;                   // [nxcd] item counters, zeroed by the launcher (a memset node on the stream)
 };
 
-#ifndef TDGP_WINO4F_MAXCIN
-#define TDGP_WINO4F_MAXCIN 128     // 0 switches the fused kernel off (A/B builds)
-#endif
-#ifndef TDGP_W4F_ABL
-#define TDGP_W4F_ABL 0             // timing experiments (wrong results), bits: 1 = no transform / window requests in the K loop, 2 = window requests only, 4 = no U pieces in the K loop,
-                                   // 8 = no output stage, 16 = no barrier at the end of a chunk
-#endif
+constexpr int W4F_MAXCIN = 128;    // most input channels the fused kernel takes (the styles table of W4F_SIDE)
 static_assert(W4_BM == 32, "wino4f: two BM = 32 slices of the U pack per block");
 constexpr int W4F_UST = 2 * W4_UCH;            // floats per U stage: two slices
 constexpr int W4F_NV = 4;                      // V ring slots (chunks)
@@ -50,7 +44,7 @@ constexpr int W4F_SIDE = 64 + 64 + 128 + 4;    // bias, demodulation coefficient
 constexpr int W4F_HALO = 8 * 256;              // per wave 1 KB: the windows' left / right neighbour columns that belong to other tile groups
 constexpr int W4F_NOISE = 2 * 8 * 64;           // two 8 x 64-pixel noise patches (the item being multiplied and the next one)
 constexpr int W4F_LDS_FLOATS = 2 * W4F_UST + W4F_NV * W4_VCH + W4F_SIDE + W4F_HALO + W4F_NOISE;
-static_assert(W4F_LDS_FLOATS * 4 <= 160 * 1024 && TDGP_WINO4F_MAXCIN <= 128, "wino4f: LDS layout");
+static_assert(W4F_LDS_FLOATS * 4 <= 160 * 1024 && W4F_MAXCIN <= 128, "wino4f: LDS layout");
 
 __global__ __launch_bounds__(512, 1) void conv3_wino4f_kernel(Wino4fParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -164,7 +158,6 @@ __global__ __launch_bounds__(512, 1) void conv3_wino4f_kernel(Wino4fParams p) {
             st[r * 6 + 1] = mid[0]; st[r * 6 + 2] = mid[1]; st[r * 6 + 3] = mid[2]; st[r * 6 + 4] = mid[3];
             st[r * 6 + 5] = *(lds_f1p)lds_ptr(ra + (uint32_t)r * rs_);
         }
-        if (!(TDGP_W4F_ABL & 64)) {                  // (timing experiment 64: the transform's LDS traffic without its arithmetic)
 #pragma unroll
         for (int cc = 0; cc < 6; cc++) {            // d = x * style;  B^T d along rows, column by column
             const float col[6] = {st[0 + cc] * sty, st[6 + cc] * sty, st[12 + cc] * sty, st[18 + cc] * sty, st[24 + cc] * sty, st[30 + cc] * sty};
@@ -180,7 +173,6 @@ __global__ __launch_bounds__(512, 1) void conv3_wino4f_kernel(Wino4fParams p) {
             wino4_bt(rw, o);
 #pragma unroll
             for (int j = 0; j < 6; j++) st[i * 6 + j] = o[j];
-        }
         }
         // V[xi4 9][k 4][tile 32][4]: the lane's nine slots (every read of this wave -- its own rows and its neighbours' -- was issued above: LDS runs a
         // wave's instructions in order)
@@ -208,13 +200,6 @@ __global__ __launch_bounds__(512, 1) void conv3_wino4f_kernel(Wino4fParams p) {
             have_t = false;
         }
     };
-#ifndef TDGP_W4F_STAGGER
-#define TDGP_W4F_STAGGER 0             // experiment: blocks of one XCD start up to 7/8 of an item apart, so that the output stages (128 KB of stores per block, which the next
-#endif                                 // item's first wait has to see acknowledged) do not hit the memory system all at once
-    if (TDGP_W4F_STAGGER > 0) {
-        const int ph = ((int)blockIdx.x / p.nxcd) & 7;
-        for (int i = 0; i < ph * TDGP_W4F_STAGGER; i++) __builtin_amdgcn_s_sleep(127);
-    }
     int item_par = 0;                                // parity of the NEXT item to begin (its noise patch buffer)
     int sl = 0, tg = 0;
     bool have = acquire(0, false, sl, tg);
@@ -247,15 +232,8 @@ __global__ __launch_bounds__(512, 1) void conv3_wino4f_kernel(Wino4fParams p) {
         item_par ^= 1;
     };
     if (have) begin_item(sl, tg);
-#ifndef TDGP_W4F_TRACE
-#define TDGP_W4F_TRACE 0               // development: cycles per phase of the item loop (wave 0), written over the first floats of y when the block is done
-#endif
-    uint64_t tr_t[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tr_last = 0;
-    auto tr_mark = [&](int i) { if (TDGP_W4F_TRACE) { const uint64_t n = __builtin_amdgcn_s_memtime(); tr_t[i] += n - tr_last; tr_last = n; } };
-    if (TDGP_W4F_TRACE) tr_last = __builtin_amdgcn_s_memtime();
     while (have) {
         const int m0 = sl * 64, gx = tg % p.gxn, gy = (tg / p.gxn) % p.gyn, b = tg / (p.gxn * p.gyn);
-        tr_mark(5);
         // prologue of the item: the windows of chunks 0..3 (requested by begin_item), one chunk per wave pair, transformed at once
         {
             int tgx = tg;
@@ -266,9 +244,7 @@ __global__ __launch_bounds__(512, 1) void conv3_wino4f_kernel(Wino4fParams p) {
 #pragma unroll
         for (int i = 0; i < 36; i++) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
         wait_loads();
-        tr_mark(6);
         lds_barrier();                               // (the styles are in place for every wave)
-        tr_mark(7);
         // the next ticket (a returning atomic) and the slice's bias / demodulation values are REQUESTED here and used behind the transform: their round trip
         // (1.8 k cycles exposed at the item top, cycle counters of the first build) runs under its ~2 k cycles of arithmetic
         // (the atomic by hand: `atomicAdd` under `tid == 0` becomes the wave-aggregated form, whose `v_readfirstlane` of the result waits for it on the spot.  The
@@ -282,9 +258,7 @@ __global__ __launch_bounds__(512, 1) void conv3_wino4f_kernel(Wino4fParams p) {
         transform(pairw);
         __builtin_amdgcn_sched_barrier(0);
         if (tid < 128) side[tid] = side_v;
-        tr_mark(8);
         lds_barrier();
-        tr_mark(0);
         // one chunk: 36 MFMAs on U stage c & 1 / V slot c & 3, the U pieces of chunk c + 1 issued one per group behind the first MFMA pair
         auto mfma_chunk = [&](int c) {
             // Stage / slot bases as OPAQUE per-chunk scalars + immediate offsets (g * 2 KB): with the loop unrolled by four the slot of a chunk is a
@@ -298,8 +272,7 @@ __global__ __launch_bounds__(512, 1) void conv3_wino4f_kernel(Wino4fParams p) {
             f32x4 fa[3], fb[3];
             auto frags = [&](int g, int q) {
                 fa[q] = *(lds_f4p)lds_ptr(ua_ + (uint32_t)g * 2048u);
-                if (TDGP_W4F_ABL & 128) fb[q] = fa[q];         // (timing experiment 128: half the fragment reads)
-                else fb[q] = *(lds_f4p)lds_ptr(vb_ + (uint32_t)g * 2048u);
+                fb[q] = *(lds_f4p)lds_ptr(vb_ + (uint32_t)g * 2048u);
             };
             frags(0, 0);
             frags(1, 1);
@@ -311,14 +284,14 @@ __global__ __launch_bounds__(512, 1) void conv3_wino4f_kernel(Wino4fParams p) {
                 acc[4 * g + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], bb[0], acc[4 * g + 0], 0, 0, 0);
                 acc[4 * g + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], bb[1], acc[4 * g + 1], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
-                if (!(TDGP_W4F_ABL & 4) && (g < 4 || (g == 4 && wvx < 4))) pieceU(g, cn, nus);
+                if (g < 4 || (g == 4 && wvx < 4)) pieceU(g, cn, nus);
                 __builtin_amdgcn_sched_barrier(0);
                 acc[4 * g + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], bb[2], acc[4 * g + 2], 0, 0, 0);
                 acc[4 * g + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], bb[3], acc[4 * g + 3], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
             wait_loads();
-            if (!(TDGP_W4F_ABL & 16)) lds_barrier();
+            lds_barrier();
             __builtin_amdgcn_sched_barrier(0);
         };
         // The K loop, unrolled by four.  Chunk n >= 4 (slot n & 3, prepared by pair n & 3): its slot is free once chunk n - 4 has been multiplied, so its
@@ -327,24 +300,21 @@ __global__ __launch_bounds__(512, 1) void conv3_wino4f_kernel(Wino4fParams p) {
         // of the next round, pairs 2, 3 (waves 4..7) at the top of iteration 1 for this round's chunks 2, 3.
         for (int c4 = 0; c4 < nch; c4 += 4) {
             const bool more_v = c4 + 4 < nch, later = c4 > 0;
-            if (!(TDGP_W4F_ABL & 1) && pairw == 3 && later) request(c4 + 3);
+            if (pairw == 3 && later) request(c4 + 3);
             mfma_chunk(c4);
-            if (!(TDGP_W4F_ABL & 1) && pairw == 0 && more_v) request(c4 + 4);
-            if (!(TDGP_W4F_ABL & 3) && pairw >= 2 && later) transform(c4 + pairw);
+            if (pairw == 0 && more_v) request(c4 + 4);
+            if (pairw >= 2 && later) transform(c4 + pairw);
             mfma_chunk(c4 + 1);
-            if (!(TDGP_W4F_ABL & 1) && pairw == 1 && more_v) request(c4 + 5);
+            if (pairw == 1 && more_v) request(c4 + 5);
             mfma_chunk(c4 + 2);
-            if (!(TDGP_W4F_ABL & 1) && pairw == 2 && more_v) request(c4 + 6);
-            if (!(TDGP_W4F_ABL & 3) && pairw < 2 && more_v) transform(c4 + 4 + pairw);
+            if (pairw == 2 && more_v) request(c4 + 6);
+            if (pairw < 2 && more_v) transform(c4 + 4 + pairw);
             mfma_chunk(c4 + 3);
         }
-        tr_mark(1);
         // the next item: its ticket was drawn at the start; its first U chunk travels under the output stage (both U stages are free)
         int nsl_ = 0, ntg_ = 0;
         const bool more = acquire(t_next, true, nsl_, ntg_);
-        tr_mark(9);
         if (more) begin_item(nsl_, ntg_);
-        tr_mark(2);
         int lo = l;
         asm volatile("" : "+v"(lo));                 // (the output stage's lane constants from an opaque copy of the lane id: not live through the K loop)
         const int kq = lo >> 4, l15 = lo & 15;
@@ -401,33 +371,20 @@ __global__ __launch_bounds__(512, 1) void conv3_wino4f_kernel(Wino4fParams p) {
                         w4_f2 f[4];
 #pragma unroll
                         for (int i = 0; i < 4; i++) f[i] = finish_pair<ACT>(p.e, yy[a][i], d2, nq[i], b2);
-                        if (TDGP_W4F_ABL & 32) {       // timing experiment: the whole output stage but its stores
-                            asm volatile("" :: "v"(f[0].x), "v"(f[1].x), "v"(f[2].x), "v"(f[3].x), "v"(f[0].y), "v"(f[1].y), "v"(f[2].y), "v"(f[3].y), "v"(yp));
-                        } else {
                         *(float4*)(yp + (int64_t)a * p.W) = make_float4(f[0].x, f[1].x, f[2].x, f[3].x);
                         *(float4*)(yp + cs + (int64_t)a * p.W) = make_float4(f[0].y, f[1].y, f[2].y, f[3].y);
-                        }
                     }
                 }
             };
-            const int evar = (TDGP_W4F_ABL & 8) ? -1 : epi_variant(p.e);
-            if (evar == -1) { if (acc[0][0] == 12345.678f) p.e.y[tid] = acc[35][3]; }
-            else if (TDGP_WINO4_PACKED_EPI && evar == 3) write_outputs_pk(std::integral_constant<int, 3>{});
-            else if (TDGP_WINO4_PACKED_EPI && evar == 1) write_outputs_pk(std::integral_constant<int, 1>{});
-            else if (evar == 3) write_outputs(std::integral_constant<int, 3>{});
-            else if (evar == 1) write_outputs(std::integral_constant<int, 1>{});
+            const int evar = epi_variant(p.e);
+            if (evar == 3) write_outputs_pk(std::integral_constant<int, 3>{});
+            else if (evar == 1) write_outputs_pk(std::integral_constant<int, 1>{});
             else write_outputs(std::integral_constant<int, 0>{});
             // the noise rows are USED here whatever path ran: a load still pending at the loop's back edge makes the compiler guard its destination registers with
             // vmcnt waits inside the K loop (seen in the ISA of the first packed build: vmcnt(2) / vmcnt(0) at the loop head -- they would also wait for the pieces in flight)
             asm volatile("" :: "v"(nz[0].x), "v"(nz[0].w), "v"(nz[1].x), "v"(nz[1].w), "v"(nz[2].x), "v"(nz[2].w), "v"(nz[3].x), "v"(nz[3].w));
         }
-        tr_mark(3);
         lds_barrier();                               // `side` and the V ring are free for the next item
-        tr_mark(4);
-        if (TDGP_W4F_TRACE) tr_t[11] += 1;
         have = more; sl = nsl_; tg = ntg_;
-    }
-    if (TDGP_W4F_TRACE && tid == 0) {
-        for (int i = 0; i < 12; i++) ((uint32_t*)p.e.y)[blockIdx.x * 16 + i] = (uint32_t)tr_t[i];
     }
 }

@@ -34,101 +34,12 @@ struct MarchGradParams {
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-template <int C>
-__global__ __launch_bounds__(64) void ray_march_grad_kernel(MarchGradParams p) {
-    const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (r >= p.rays) return;
-    const int S = p.S;
-    const bool mip = p.marcher == 1, inf = p.flags & 1, last_back = (p.flags & 2) && !mip, white = (p.flags & 4) && mip, relu = p.flags & 8;
-    const int M = mip ? (inf ? S : S - 1) : S;              // intervals
-    const float* col = p.colors + r * S * C;
-    const float* den = p.dens + r * S;
-    const float* dep = p.depths + r * S;
-    float drgb[C];
-#pragma unroll
-    for (int c = 0; c < C; c++) drgb[c] = p.d_rgb[r * C + c] * (mip ? 2.0f : 1.0f);      // mip: rgb * 2 - 1
-    const float ddep = p.d_depth ? p.d_depth[r] : 0.f;
-    float drgb_sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; c++) drgb_sum += drgb[c];
-
-    float a[RG_MAXS], T[RG_MAXS];
-    // ---- forward sweep ------------------------------------------------------------------------------------------------------
-    float Tc = 1.f, wsum = 0.f;
-    for (int i = 0; i < M; i++) {
-        const bool tail = i == S - 1;                                           // the appended far interval
-        const float delta = tail ? (inf ? 1e10f : 1e-3f) : dep[i + 1] - dep[i];
-        float s = mip ? (tail ? den[i] : (den[i] + den[i + 1]) * 0.5f) + p.density_bias : den[i];
-        const float sigma = relu ? fmaxf(s, 0.f) : softplus20(s);
-        const float ai = 1.0f - expf(-delta * sigma);
-        a[i] = ai; T[i] = Tc;
-        wsum += ai * Tc;
-        Tc *= (1.0f - ai) + 1e-10f;
-    }
-    // ---- backward sweep -----------------------------------------------------------------------------------------------------
-    // G_i = dL/dw_i; last_back: w'_{S-1} = 1 - sum_{j<S-1} w_j, so G_j -= G_{S-1} (and the last weight itself has no gradient);
-    // white_back: rgb += 1 - sum w  ->  G_i -= sum_c d_rgb_c
-    auto g_of = [&](int i) {
-        const bool tail = i == S - 1;
-        float g = 0.f;
-        if (mip) {
-#pragma unroll
-            for (int c = 0; c < C; c++) g += drgb[c] * (tail ? col[i * C + c] : (col[i * C + c] + col[(i + 1) * C + c]) * 0.5f);
-            g += ddep * (tail ? dep[i] : (dep[i] + dep[i + 1]) * 0.5f);
-            if (white) g -= drgb_sum;
-        } else {
-#pragma unroll
-            for (int c = 0; c < C; c++) g += drgb[c] * col[i * C + c];
-            g += ddep * dep[i];
-        }
-        if (p.d_weights) g += p.d_weights[r * M + i];
-        return g;
-    };
-    const float g_last = last_back ? g_of(S - 1) : 0.f;
-    const float w_last_extra = last_back ? 1.0f - wsum : 0.f;
-    for (int i = 0; i < S; i++) {
-        p.d_dens[r * S + i] = 0.f;
-#pragma unroll
-        for (int c = 0; c < C; c++) p.d_colors[(r * S + i) * C + c] = 0.f;
-    }
-    float U = 0.f;                     // U_i of the interval being visited
-    for (int i = M - 1; i >= 0; i--) {
-        const bool tail = i == S - 1;
-        float G = g_of(i);
-        if (last_back) G = (i == S - 1) ? 0.f : G - g_last;
-        const float ai = a[i], Ti = T[i];
-        const float w = ai * Ti + ((last_back && i == S - 1) ? w_last_extra : 0.f);
-        // colours
-        if (mip) {
-#pragma unroll
-            for (int c = 0; c < C; c++) {
-                const float dc = w * drgb[c];
-                if (tail) p.d_colors[(r * S + i) * C + c] += dc;
-                else { p.d_colors[(r * S + i) * C + c] += 0.5f * dc; p.d_colors[(r * S + i + 1) * C + c] += 0.5f * dc; }
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < C; c++) p.d_colors[(r * S + i) * C + c] = w * drgb[c];
-        }
-        // densities
-        const float da = Ti * (G - U);
-        const float delta = tail ? (inf ? 1e10f : 1e-3f) : dep[i + 1] - dep[i];
-        const float dsigma = da * delta * (1.0f - ai);
-        const float s = mip ? (tail ? den[i] : (den[i] + den[i + 1]) * 0.5f) + p.density_bias : den[i];
-        const float ds = relu ? (s > 0.f ? dsigma : 0.f) : (s > 20.f ? dsigma : dsigma * sigmoidf_(s));
-        if (mip && !tail) { p.d_dens[r * S + i] += 0.5f * ds; p.d_dens[r * S + i + 1] += 0.5f * ds; }
-        else p.d_dens[r * S + i] += ds;
-        U = G * ai + ((1.0f - ai) + 1e-10f) * U;            // U_{i-1}
-    }
-}
-
-
-// The same gradients with one WAVE per ray (round 4; the thread-per-ray kernel above walks S samples with a stride of S floats between
-// lanes and keeps two S-long arrays in scratch: 5.6 ms for 262 k rays x 128 samples, 0.6 GB of traffic).  lane l owns the EPL consecutive
+// One WAVE per ray (round 4; the thread-per-ray kernel it replaced walked S samples with a stride of S floats between
+// lanes and kept two S-long arrays in scratch: 5.6 ms for 262 k rays x 128 samples, 0.6 GB of traffic).  lane l owns the EPL consecutive
 // intervals i = l EPL + e.  T_i is an exclusive prefix product (in-lane, then a 6-step wave scan of the lane totals); the backward
 // recurrence U_{i-1} = G_i a_i + q_i U_i is a suffix composition of affine maps u -> B + A u (in-lane, then a 6-step wave scan of (A, B)
 // pairs: (A1, B1) o (A2, B2) = (A1 A2, B1 + A1 B2)); the half-and-half deposits of the mip marcher take the left neighbour's interval from
-// the previous element / lane.  Same formulas as above; only the association of the products / sums differs (tests: the reference's
+// the previous element / lane.  Same formulas as that kernel; only the association of the products / sums differs (tests: the reference's
 // autograd goldens and the double-precision oracle, same bounds as before).  Loads and stores are EPL (x C) consecutive floats per lane.
 template <int C, int EPL>
 __global__ __launch_bounds__(256) void ray_march_grad_wave_kernel(MarchGradParams p) {
@@ -282,23 +193,13 @@ TDGP_API int tdgp_ray_march_grad(const float* colors, const float* densities, co
     p.d_colors = d_colors; p.d_dens = d_densities; p.rays = rays; p.S = S; p.C = C; p.marcher = marcher; p.flags = flags; p.density_bias = density_bias;
     hipStream_t s = (hipStream_t)stream;
     TDGP_CHECK(C == 1 || C == 3 || C == 4, TDGP_EUNSUPPORTED, "ray_march_grad: C=%d (1, 3 or 4 colour channels)", C);
-#ifndef TDGP_MARCH_GRAD_WAVE
-#define TDGP_MARCH_GRAD_WAVE 1      // 0: the thread-per-ray kernel (A/B builds)
-#endif
-    if (TDGP_MARCH_GRAD_WAVE) {
-        // a wave per ray, 4 waves per block, persistent over the rays (a few blocks per CU's worth of waves cover the load latencies)
-        const dim3 grid((unsigned)std::min<int64_t>(cdiv64(rays, 4), (int64_t)tdgp_cu_count() * 8)), block(256);
+    // a wave per ray, 4 waves per block, persistent over the rays (a few blocks per CU's worth of waves cover the load latencies)
+    const dim3 grid((unsigned)std::min<int64_t>(cdiv64(rays, 4), (int64_t)tdgp_cu_count() * 8)), block(256);
 #define TDGP_MG(CC, EE) TDGP_LAUNCH("ray_march_grad_kernel", (ray_march_grad_wave_kernel<CC, EE>), grid, block, 0, s, p)
 #define TDGP_MG_C(EE) do { if (C == 3) TDGP_MG(3, EE); else if (C == 1) TDGP_MG(1, EE); else TDGP_MG(4, EE); } while (0)
-        if (S <= 64) TDGP_MG_C(1); else if (S <= 128) TDGP_MG_C(2); else TDGP_MG_C(4);
+    if (S <= 64) TDGP_MG_C(1); else if (S <= 128) TDGP_MG_C(2); else TDGP_MG_C(4);
 #undef TDGP_MG_C
 #undef TDGP_MG
-    } else {
-        const dim3 grid((unsigned)cdiv64(rays, 64)), block(64);
-        if (C == 3) TDGP_LAUNCH("ray_march_grad_kernel", ray_march_grad_kernel<3>, grid, block, 0, s, p);
-        else if (C == 1) TDGP_LAUNCH("ray_march_grad_kernel", ray_march_grad_kernel<1>, grid, block, 0, s, p);
-        else TDGP_LAUNCH("ray_march_grad_kernel", ray_march_grad_kernel<4>, grid, block, 0, s, p);
-    }
     TDGP_LAUNCH_CHECK();
     return TDGP_OK;
 }

@@ -16,10 +16,6 @@
 // so for given weights the searchsorted indices and the fine samples equal the reference's bit for bit (the stage-level tests).
 #include "common.h"
 
-#ifndef TDGP_RAY_ABL
-#define TDGP_RAY_ABL 0      // 1: per-phase cycle counts of one wave, printed (timing experiments only)
-#endif
-
 namespace {
 
 constexpr int MAXS = 256;          // capacity of the short-ray kernels: samples per ray in one pass (2*S for the merged pass)
@@ -522,12 +518,6 @@ __global__ __launch_bounds__(256) void importance_from_coarse_kernel(const float
     const int64_t r = (int64_t)blockIdx.x * RAYS_PER_BLOCK + wv;
     if (r >= rays) return;
     WaveScratchT<MS>& sc = scratch[wv];
-#if TDGP_RAY_ABL & 1
-    long long tph[6], t0_ = __builtin_readcyclecounter();
-#define TPH(i) { const long long t_ = __builtin_readcyclecounter(); tph[i] = t_ - t0_; t0_ = t_; }
-#else
-#define TPH(i)
-#endif
     for (int i = l; i < S; i += 64) { sc.z[i] = sdist[r * S + i]; sc.sig[i] = rgbs[(r * S + i) * 4 + 3]; }
     // the draws are not needed before the cdf exists: their loads go out now and land during the march
     float upre[MS / 64];
@@ -538,7 +528,6 @@ __global__ __launch_bounds__(256) void importance_from_coarse_kernel(const float
     for (int c = 0; c < MS / 64; c++) upre[c] = (l + 64 * c < N) ? u_fine[r * N + l + 64 * c] : 0.f;
     }
     wave_sync();
-    TPH(0)
     float fT, wagg;
     int Wn = S;
     if (MS > MAXS && S > MAXS) {    // the coarse list marched as tdgp_ray_march marches a list of that length
@@ -547,7 +536,6 @@ __global__ __launch_bounds__(256) void importance_from_coarse_kernel(const float
     } else
     if (marcher == 0) march_classical_lds(sc.z, sc.sig, sc.w, S, flags, cut_thr, fT, wagg);
     else { march_mip_lds(sc.z, sc.sig, sc.w, S, flags, density_bias, cut_thr, fT, wagg); Wn = (flags & 1) ? S : S - 1; }
-    TPH(1)
     float* tkey = sc.col[0];
     if constexpr (MS > MAXS)
         // inlined here (the short forms inline it on their own): a call would pass the lambdas' captures through private scratch
@@ -566,7 +554,6 @@ __global__ __launch_bounds__(256) void importance_from_coarse_kernel(const float
         if (inds) inds[r * N + j] = ind;
     });
     wave_sync();
-    TPH(2)
     if (N <= 64) {                  // one sample per lane: sort across the lanes, store coalesced
         float key = l < N ? tkey[l] : INFINITY;
         // Distinct keys (all but measure-zero rays): the sorted slot of a key is the number of smaller keys -- 16 broadcast LDS reads
@@ -597,15 +584,10 @@ __global__ __launch_bounds__(256) void importance_from_coarse_kernel(const float
         }
         int idx = l;
         wave_bitonic_sort(key, idx);
-        TPH(3)
         if (l < N) {
             tfine[r * N + l] = key;
             if (fine_perm) fine_perm[r * N + l] = idx;
         }
-        TPH(4)
-#if TDGP_RAY_ABL & 1
-        if (l == 0 && (r == 1000 || r == 200000)) printf("importance ray %lld: load %lld march %lld importance %lld sort %lld store %lld\n", (long long)r, tph[0], tph[1], tph[2], tph[3], tph[4]);
-#endif
         return;
     }
     if (N <= 128) {                 // two samples per lane
@@ -724,9 +706,6 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(const float* __res
     if (r >= rays) return;
     WaveScratchT<MS>& sc = scratch[wv];
     const int M = S1 + S2;
-#if TDGP_RAY_ABL & 1
-    long long tph[6], t0_ = __builtin_readcyclecounter();
-#endif
     // keys -> sc.cdf (scratch), ranks, scatter into sorted sc.z / sc.sig / sc.col.  The colours do not depend on the ranks: their
     // loads go out with the keys' and land while the ranks are searched.
     float4 cval[MS / 64];
@@ -742,7 +721,6 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(const float* __res
     // both lists already ascending (stratified coarse samples; fine samples sorted by importance_from_coarse)?  Then the
     // stable merge position is the element's own index plus a binary search in the OTHER list; otherwise (arbitrary caller
     // data, or the ~1e-10-probability ulp inversion of s -> t) fall back to the brute-force stable rank.
-    TPH(0)
     bool bad = false;
     for (int i = l; i < M; i += 64)
         if (i + 1 < M && i + 1 != S1 && sc.cdf[i + 1] < sc.cdf[i]) bad = true;
@@ -809,7 +787,6 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(const float* __res
             }
         }
     }
-    TPH(1)
 #pragma unroll
     for (int cc = 0; cc < MS / 64; cc++) {
         const int i = l + 64 * cc;
@@ -821,7 +798,6 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(const float* __res
         if (perm) perm[r * M + pos] = i < S1 ? i : S1 + (perm2 ? perm2[r * S2 + (i - S1)] : i - S1);
     }
     wave_sync();
-    TPH(2)
     float fT, wagg;
     const int Mm = (marcher == 0) ? M : ((flags & 1) ? M : M - 1);
     if (MS > MAXS && M > MAXS) {
@@ -830,7 +806,6 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(const float* __res
     } else
     if (marcher == 0) march_classical_lds(sc.z, sc.sig, sc.w, M, flags, cut_thr, fT, wagg);
     else march_mip_lds(sc.z, sc.sig, sc.w, M, flags, density_bias, cut_thr, fT, wagg);
-    TPH(3)
     float acc[4] = {0.f, 0.f, 0.f, 0.f}, wacc = 0.f;
     for (int i = l; i < Mm; i += 64) {
         const float wi = sc.w[i];
@@ -853,10 +828,6 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(const float* __res
             out[c] = out[c] * 2.0f - 1.0f;
         }
     }
-    TPH(4)
-#if TDGP_RAY_ABL & 1
-    if (l == 0 && (r == 1000 || r == 200000)) printf("merge ray %lld: load %lld rank %lld gather %lld march %lld composite %lld\n", (long long)r, tph[0], tph[1], tph[2], tph[3], tph[4]);
-#endif
     if (l == 0) {
         rgb[r * 3 + 0] = out[0]; rgb[r * 3 + 1] = out[1]; rgb[r * 3 + 2] = out[2];
         depth_o[r] = out[3];

@@ -1,5 +1,5 @@
 """Renderer-only timing at the C3 shape (random planes): per-kernel min/max ms through the library's event hooks.
-   python tools/dev/bench_field.py [B]            (variant libraries: python tools/dev/with_lib.py <so> tools/dev/bench_field.py ...)"""
+   python tools/dev/bench_field.py [B]"""
 import importlib
 import os
 import sys
