@@ -25,7 +25,8 @@ class GraphedGenerator:
         self.kw = dict(noise_mode=noise_mode, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff)
         if render_opts:
             if float(render_opts.get('cut_quantile', 0.0)) > 0.0:
-                raise NotImplementedError('cut_quantile reads a threshold back to the host (torch.quantile -> float): not capturable')
+                raise NotImplementedError('cut_quantile reads its threshold back to the host (tdgp_quantile_select -> the float argument of the march kernels): '
+                                          'not capturable')
             self.kw['render_opts'] = dict(render_opts)
         syn = G.synthesis                              # the resolution the forward renders at (inference.configure_for_inference may have set it)
         res = syn.train_resolution if syn.training else syn.test_resolution

@@ -329,3 +329,89 @@ def compute_flattened_depth_maps(G, max_items, batch_size=64, batch_gen=None, ca
             depths.append(out.depth)
         stats.append_torch(torch.cat(depths).flatten(start_dim=1), num_gpus=num_gpus, rank=rank, gatherer=gatherer)
     return torch.from_numpy(stats.get_all())
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# non-flatness score (src/metrics/non_flatness_score.py; metric 'nfs256', metric_main.py:118-120)
+# ----------------------------------------------------------------------------------------------------------------------
+def _depth_histc(depth_maps, bins, lo, hi):
+    """[N, pixels] fp32 on the GPU -> [N, bins] int32 counts on the GPU (tdgp_depth_histc: clamp + torch.histc's CPU arithmetic, product before division); no check, no
+    read-back."""
+    from . import _lib
+    _lib.require_cuda(depth_maps, 'depth_maps')
+    d = _lib.f32c(depth_maps.flatten(start_dim=1))
+    hist = torch.empty([d.shape[0], int(bins)], dtype=torch.int32, device=d.device)
+    if d.shape[0]:
+        with torch.cuda.device(d.device):
+            _lib.call('tdgp_depth_histc', d.data_ptr(), d.shape[0], d.shape[1], float(lo), float(hi), int(bins), hist.data_ptr(), _lib.stream_of(d))
+    return hist
+
+
+def _check_histogram_rows(histograms, pixels, shape):
+    """non_flatness_score.py:32-33 with its message: every row must account for every pixel (a NaN or out-of-range depth is in no bin)."""
+    counts = histograms.sum(dim=1)
+    assert counts.min() == counts.max() == pixels, f"Histograms countain OOB values: {counts.min(), counts.max(), shape}"
+
+
+@torch.no_grad()
+def convert_depth_maps_to_histograms(depth_maps, bins, min, max):       # noqa: A002 (the reference's argument names)
+    """non_flatness_score.py:26-35: depth maps [N, pixels] -> fp32 histograms [N, bins] over [min, max], every row checked to sum to `pixels`.
+    A CPU tensor takes the reference's own route, one torch.histc per row.  A GPU tensor goes through tdgp_depth_histc in one launch and the
+    histograms stay on the device; the kernel applies the score's clamp to [min, max] (non_flatness_score.py:12) itself, so there depths
+    outside the range count in the end bins instead of failing the check -- on the clamped maps the score feeds in, the two routes agree
+    count for count for any range and bin count the kernel takes (it restates the CPU histc's (x - min) * bins / (max - min) in fp32)."""
+    assert depth_maps.ndim == 2, f'Wrong shape: {depth_maps.shape}'
+    if depth_maps.is_cuda:
+        histograms = _depth_histc(depth_maps, bins, min, max).float()
+    else:
+        histograms = torch.stack([torch.histc(d, bins, min=min, max=max) for d in depth_maps.float()], dim=0)
+    _check_histogram_rows(histograms, depth_maps[0].numel(), depth_maps.shape)
+    return histograms
+
+
+def compute_histogram_entropy(histograms):
+    """non_flatness_score.py:39-42, the same three tensor ops on the small [N, bins] fp32 tensor."""
+    assert histograms.ndim == 2, f'Wrong shape: {histograms.shape}'
+    probs = histograms / histograms.sum(dim=1, keepdim=True)
+    return -1.0 * (torch.log(probs + 1e-12) * probs).sum(dim=1)
+
+
+def _device_of(G):
+    params = getattr(G, 'parameters', None)
+    p = next(iter(params()), None) if callable(params) else None
+    return p.device if p is not None else torch.device(getattr(G, 'device', 'cpu'))
+
+
+def compute_flatness_score(G, num_gen, min_depth, max_depth, num_bins=64, cut_quantile=0.5, batch_size=64, batch_gen=None, camera_cfg=None, c_sampler=None,
+                           dataset=None, num_gpus=1, rank=0, gatherer=None, G_kwargs=None):
+    """non_flatness_score.py:9-21: exp(entropy) of the depth histogram of `num_gen` frontal-camera samples rendered with `cut_quantile`, averaged.
+    The loop of `compute_flattened_depth_maps` with the same draws in the same order; per batch the depth maps are clamped and reduced to
+    histograms where they are (on the GPU: one tdgp_depth_histc launch), and only the [batch, num_bins] block of counts (exact in fp32:
+    fewer than 2^24 pixels per map) goes through `FeatureStats.append_torch` -- the rank gather and the host copy."""
+    batch_gen = resolve_batch_gen(batch_size, batch_gen)
+    G_kwargs = {} if G_kwargs is None else G_kwargs
+    device = _device_of(G)
+    stats = FeatureStats(max_items=num_gen, capture_all=True)
+    batches = _generator_batches(G, batch_gen, camera_cfg, c_sampler, dataset, device, frontal_camera=True)
+    pixels = shape = None
+    while not stats.is_full():
+        depths = []
+        for _ in range(batch_size // batch_gen):
+            z, c, camera_params = next(batches)
+            out = G(z, c, camera_params, render_opts=dict(return_depth=True, cut_quantile=cut_quantile), **G_kwargs)
+            depths.append(out.depth)
+        depths = torch.cat(depths).flatten(start_dim=1)
+        pixels, shape = depths.shape[1], depths.shape
+        if depths.is_cuda:
+            block = _depth_histc(depths, num_bins, min_depth, max_depth).float()
+        else:
+            block = torch.stack([torch.histc(d, num_bins, min=min_depth, max=max_depth) for d in depths.float().clamp(min_depth, max_depth)], dim=0)
+        stats.append_torch(block, num_gpus=num_gpus, rank=rank, gatherer=gatherer)
+    histograms = torch.from_numpy(stats.get_all())
+    _check_histogram_rows(histograms, pixels, (histograms.shape[0],) + tuple(shape[1:]))
+    return float(compute_histogram_entropy(histograms).exp().mean().item())
+
+
+def nfs256(G, **kw):
+    """The registry entry 'nfs256' (metric_main.py:118-120): 256 samples, depth range = the generator's ray range."""
+    return dict(nfs256=compute_flatness_score(G, num_gen=256, min_depth=G.cfg.ray_start, max_depth=G.cfg.ray_end, **kw))

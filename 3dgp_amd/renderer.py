@@ -83,6 +83,57 @@ def _quantile(x, q):
     return torch.lerp(xs[lo], xs[min(lo + 1, n - 1)], pos - lo)
 
 
+def quantile_ranks(q, n):
+    """(k_lo, k_hi, weight) such that `_quantile(x, q)` over n elements is torch.lerp(sorted(x)[k_lo], sorted(x)[k_hi], weight), bit for bit:
+    the host half of tdgp_quantile_select.  The two branches restate `_quantile`'s and must stay apart (the double-precision rank of the
+    second differs from torch.quantile's fp32 one in the last place, and with it the weight):
+    n <= 2^24, torch.quantile (ATen Sorting.cpp, quantile_compute): rank = fp32(q) * fp32(n - 1) as ONE fp32 product, floor / ceil of it,
+    weight = rank - floor in fp32; above, `_quantile`'s own Python-double arithmetic, the weight rounded to fp32 where torch.lerp takes it."""
+    n = int(n)
+    assert n >= 1 and 0.0 <= q <= 1.0
+    if n <= (1 << 24):
+        rank = np.float32(q) * np.float32(n - 1)
+        k_lo = int(np.floor(rank))
+        return k_lo, min(int(np.ceil(rank)), n - 1), float(rank - np.float32(k_lo))
+    pos = float(q) * (n - 1)
+    k_lo = int(pos)
+    return k_lo, min(k_lo + 1, n - 1), float(np.float32(pos - k_lo))
+
+
+_QS_WORKSPACE = {}            # (device, stream) -> the select's 48 KiB workspace: work on one stream is ordered, so its calls can share one
+
+
+def _qs_workspace(device, stream, need):
+    key = (device.index, stream)
+    ws = _QS_WORKSPACE.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _QS_WORKSPACE[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
+
+
+def quantile_select(x, q):
+    """`_quantile(x, q)` of a GPU tensor without the sort: exact order statistics by radix select (tdgp_quantile_select, csrc/metrics.hip).
+    -> [3] fp32 on the device: sorted(x)[k_lo], sorted(x)[k_hi] and their torch.lerp, the quantile.  Nothing is read back here."""
+    _lib.require_cuda(x, 'quantile_select: x')
+    x = _lib.f32c(x.reshape(-1))
+    n = x.numel()
+    k_lo, k_hi, weight = quantile_ranks(q, n)
+    with torch.cuda.device(x.device):
+        need = int(_lib.load().tdgp_quantile_select_workspace_bytes(n))
+        if need < 0:
+            raise RuntimeError(f'quantile_select: {n} elements outside [1, 2^31 - 1]')
+        stream = _lib.stream_of(x)
+        ws = _qs_workspace(x.device, stream, need)
+        out = torch.empty(3, dtype=torch.float32, device=x.device)      # a fresh result per call: an earlier call's tensor is never overwritten
+        _lib.call('tdgp_quantile_select', x.data_ptr(), n, k_lo, k_hi, weight, out.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+    return out
+
+
+def _select_threshold(dens, q):
+    """The threshold as the float the march kernels take: one 4-byte read-back per quantile."""
+    return float(quantile_select(dens, q)[2])
+
+
 def _cut_threshold(sigma, opts, marcher, flags):
     """The `cut_quantile` option of both marchers (tri_plane_renderer.py:324-326, 366-368; used by the non-flatness score with
     0.5): activated densities below the GLOBAL quantile -- over every ray and sample of the call -- are zeroed before alpha.
@@ -102,7 +153,7 @@ def _cut_threshold(sigma, opts, marcher, flags):
     dens = torch.empty_like(sigma)
     with torch.cuda.device(sigma.device):
         _lib.call('tdgp_density_activation', sigma.data_ptr(), dens.data_ptr(), sigma.numel(), flags, bias, _lib.stream_of(sigma))
-    return float(_quantile(dens, q))
+    return _select_threshold(dens, q)
 
 
 # ------------------------------------------------------------------------------------------------ camera + rays

@@ -423,6 +423,29 @@ int     tdgp_mcubes_count(const float* volume, int D, int H, int W, float thresh
 int     tdgp_mcubes_emit(const float* volume, int D, int H, int W, float thresh, void* workspace, int64_t workspace_bytes,
                          float* vertices, int64_t V, int32_t* triangles, int64_t T, tdgp_stream_t stream);
 
+/* Exact order statistics without a sort: the quantile behind the marchers' `cut_quantile` option (tri_plane_renderer.py:324-326, 366-368:
+ * torch.quantile of the activated densities; the non-flatness score renders with 0.5, non_flatness_score.py:9-11).
+ * out3[0] = sorted(x)[k_lo] and out3[1] = sorted(x)[k_hi], exact bits; out3[2] = torch.lerp(out3[0], out3[1], weight), i.e.
+ * a + w (b - a) for |w| < 0.5 and b - (b - a)(1 - w) otherwise, each as ONE fused multiply-add on the rounded difference (and 1 - w): the
+ * way torch's GPU lerp kernel is compiled, which is what makes out3[2] the float torch.quantile returns on the device.  The caller turns (q, n) into
+ * (k_lo, k_hi, weight) -- renderer.quantile_ranks restates torch.quantile's fp32 rank arithmetic.
+ * -0.0 counts as +0.0; if any element is NaN all three outputs are NaN (as torch.quantile); every other value orders as a float.
+ * Radix select over an order-preserving key in three passes of 11 / 11 / 10 bits (csrc/metrics.hip): x is read three times, nothing is
+ * written but 48 KiB of histograms, nothing is read back, integer counts only: identical bytes from run to run.
+ * 1 <= n <= 2^31 - 1; 0 <= k_lo <= k_hi <= k_lo + 1, k_hi < n; x and out3 4-byte aligned (any offset into a buffer works).
+ * workspace: tdgp_quantile_select_workspace_bytes(n) bytes (-1 for an n it refuses), 16-byte aligned, caller-owned. */
+int64_t tdgp_quantile_select_workspace_bytes(int64_t n);
+int     tdgp_quantile_select(const float* x, int64_t n, int64_t k_lo, int64_t k_hi, float weight, float* out3, void* workspace,
+                             int64_t workspace_bytes, tdgp_stream_t stream);
+
+/* Depth maps [images, pixels] fp32 -> histograms [images, bins] int32: steps 1b and 2 of the non-flatness score on the device
+ * (non_flatness_score.py:12 `clamp(min_depth, max_depth)`, :15 / :30 one torch.histc per depth map on a host tensor).
+ * Per element in fp32, nothing fused: x = clamp(depth, lo, hi); bin = min((int)((x - lo) * bins / (hi - lo)), bins - 1), the product
+ * rounded before the division -- torch.histc's arithmetic on a CPU tensor (dividing first differs next to bin edges unless `bins` or
+ * `hi - lo` is a power of two).  A NaN depth is counted in no bin (the caller's row-sum check, :32-33, reports it).
+ * 2 <= bins <= 1024, 1 <= pixels < 2^24 (a count stays exact as fp32), 1 <= images <= 65535, lo < hi finite.  `hist` is overwritten. */
+int tdgp_depth_histc(const float* depth, int64_t images, int64_t pixels, float lo, float hi, int bins, int32_t* hist, tdgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

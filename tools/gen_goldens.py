@@ -1645,6 +1645,7 @@ def main():
     gen_adaptors()
     gen_camera_regs()
     gen_metrics()
+    gen_nfs()
     gen_trajectories()
     gen_harness()
     gen_synthesis_grad()
@@ -1759,6 +1760,56 @@ def gen_geometry():
     arrays.update(z=inp['z'], c=inp['c'], ws=npy(ws), seed=np.array([seed, 1], dtype=np.int64), density_spec=np.array([res], dtype=np.int64),
                   density_cube=np.array(cube, dtype=np.float64), sigma=npy(sigma).reshape(res, res, res), sigma_f64=npy(sigma64).reshape(res, res, res))
     save('geometry', **arrays)
+
+
+NFS_GOLDEN = dict(seed=21, samples=16, draw_seed=71, planted_rows=8)
+
+
+def gen_nfs():
+    """tests/golden/nfs.npz: the reference's non-flatness score (src/metrics/non_flatness_score.py) on 16 depth maps of the e2e_tiny generator
+    rendered by the reference with cut_quantile = 0.5, plus 8 planted rows that sit on and one ulp either side of every edge of the 64-bin grid
+    (and of lo / hi).  Histograms, entropies and the score for 64 and 16 bins, all from the reference's own functions: the score through its
+    compute_flatness_score with the depth-map loop (metric_utils.compute_flattened_depth_maps, which needs its dataset / options objects)
+    replaced by these rows.    python tools/gen_goldens.py nfs"""
+    from src.metrics import non_flatness_score as ref_nfs
+    gg = NFS_GOLDEN
+    cfg = tdgp.config.config_tiny()
+    sd = tdgp.weights.random_state_dict(cfg, seed=gg['seed'], exercise_all=True)
+    G = build_ref_generator(cfg, sd)
+    inp = tdgp.weights.synthetic_inputs(cfg, batch=gg['samples'], seed=gg['seed'] + 1)
+    cam = TensorGroup(**{k: T(v) for k, v in inp['camera'].items()})
+    lo, hi = float(cfg.ray_start), float(cfg.ray_end)
+    torch.manual_seed(gg['draw_seed'])                   # the renderer's own stratified / importance draws
+    with torch.no_grad():
+        ws = G.mapping(T(inp['z']), T(inp['c']))
+        out = G.synthesis(ws, camera_params=cam, noise_mode='const', render_opts=dict(return_depth=True, cut_quantile=0.5))
+    depth = npy(out.depth).reshape(gg['samples'], -1).astype(np.float32)
+    pixels = depth.shape[1]
+    lo32, hi32 = np.float32(lo), np.float32(hi)
+    edges = (lo32 + np.arange(65, dtype=np.float32) * (hi32 - lo32) / np.float32(64)).astype(np.float32)
+    pts = np.concatenate([edges, np.nextafter(edges, np.float32(np.inf)), np.nextafter(edges, np.float32(-np.inf))])
+    pts = np.clip(pts, lo32, hi32).astype(np.float32)
+    fill = np.random.RandomState(gg['draw_seed']).uniform(lo, hi, gg['planted_rows'] * pixels).astype(np.float32)
+    fill[:pts.size] = pts
+    planted = np.random.RandomState(gg['draw_seed'] + 1).permutation(fill).reshape(gg['planted_rows'], pixels)
+    rows = np.concatenate([depth, planted]).astype(np.float32)
+    near_edge = np.abs(depth[..., None].astype(np.float64) - edges[None, None].astype(np.float64)).min(-1) <= 1e-5 * np.abs(depth).max()
+    print(f'nfs: {int(near_edge.sum())} of {depth.size} rendered pixels within the depth tolerance of a bin edge')
+    arrays = dict(depth_maps=rows, range=np.array([lo, hi], dtype=np.float64), rendered_rows=np.array(gg['samples'], dtype=np.int64),
+                  meta=np.array(['source=reference:src/metrics/non_flatness_score.py', f'torch={torch.__version__}']))
+    o_maps = ref_nfs.metric_utils.compute_flattened_depth_maps
+    ref_nfs.metric_utils.compute_flattened_depth_maps = lambda **kw: T(rows).clone()
+    try:
+        for bins in (64, 16):
+            clamped = T(rows).clamp(lo, hi)
+            hist = ref_nfs.convert_depth_maps_to_histograms(clamped, bins=bins, min=lo, max=hi)
+            arrays[f'hist_{bins}'] = npy(hist).astype(np.int32)
+            assert (arrays[f'hist_{bins}'] == npy(hist)).all()
+            arrays[f'entropy_{bins}'] = npy(ref_nfs.compute_histogram_entropy(hist))
+            arrays[f'score_{bins}'] = np.array(ref_nfs.compute_flatness_score(None, num_gen=rows.shape[0], min_depth=lo, max_depth=hi, num_bins=bins), dtype=np.float64)
+    finally:
+        ref_nfs.metric_utils.compute_flattened_depth_maps = o_maps
+    save('nfs', **arrays)
 
 
 def gen_e2e_all():
