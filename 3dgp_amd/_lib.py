@@ -69,6 +69,11 @@ _PROTOTYPES = {
     'tdgp_quantile_select_workspace_bytes': (c_int64, [c_int64]),
     'tdgp_quantile_select': (c_int, [P, c_int64, c_int64, c_int64, c_float, P, P, c_int64, P]),
     'tdgp_depth_histc': (c_int, [P, c_int64, c_int64, c_float, c_float, c_int, P, P]),
+    'tdgp_pr_pack': (c_int, [P, c_int64, c_int, P, c_int, P, P]),
+    'tdgp_pr_kth_workspace_bytes': (c_int64, [c_int64, c_int64, c_int]),
+    'tdgp_pr_kth': (c_int, [P, P, c_int64, P, P, c_int64, c_int, c_int, P, P, c_int64, P]),
+    'tdgp_pr_member_workspace_bytes': (c_int64, [c_int64, c_int64]),
+    'tdgp_pr_member': (c_int, [P, P, c_int64, P, P, P, c_int64, c_int, P, P, c_int64, P]),
 }
 EXPORTS = tuple(_PROTOTYPES)
 

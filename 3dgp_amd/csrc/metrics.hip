@@ -270,3 +270,357 @@ TDGP_API int tdgp_depth_histc(const float* depth, int64_t images, int64_t pixels
     TDGP_LAUNCH_CHECK();
     return TDGP_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------- precision / recall k-NN
+// The two distance passes of src/metrics/precision_recall.py (torch.cdist in fp16 over 10 000 x 10 000 blocks, every block copied to the
+// host, kthvalue / <= there) as ONE tile loop with two epilogues; the distance matrix exists only in accumulator registers.
+//
+// Contract (include/tdgp.h): features rounded to fp16; d2(i,j) = max(|a_i|^2 + |b_j|^2 - 2 a_i.b_j, 0) with the dot product on
+// v_mfma_f32_32x32x16_f16 (fp32 accumulation) and the norms summed in fp32 from the rounded values; d = sqrtf(d2), correctly rounded;
+// d rounded once to fp16 (RNE, overflow -> +inf); everything downstream compares those fp16 values; NaN sorts last and compares false.
+//
+// x -> h(x) = fp16(sqrtf(x)) is monotone, so the tile loop never takes a root: the (k+1)-th smallest h(d2) IS h((k+1)-th smallest d2),
+// and h(d2) <= kth[j] IS d2 <= thr[j] with thr[j] the largest fp32 whose h is <= kth[j] (pr_thr_kernel finds it by bisection over the
+// bit patterns with the very sqrtf / conversion of the contract).  d2 >= +0 as fp32 bits is an order-preserving uint32 key; a NaN of
+// either sign keys above +inf.
+//
+//   pr_pack_kernel          one wave per row: fp32 -> fp16 (zero padded to Fpad), the row's fp32 norm
+//   pr_tile_kernel<EPI,LS>  block = 128 rows x up to PR_JT tiles of 128 columns; 4 waves as 2 x 2, each 64 x 64 = 2 x 2 MFMA tiles.
+//                           The COLUMN set is the A operand and the row set the B operand, so a lane holds one row (lane & 31) and 16
+//                           columns per tile in its registers: its running state is per row.  K loop: 32 halves per step, register
+//                           staged into two LDS buffers (80-byte rows: conflict-free ds_read_b128), one barrier per step.
+//       EPI 0 (kth)         per lane and row a sorted list of the LS (4 or 8) smallest keys, one min/max chain per element; at the end
+//                           of the block the 4 lists of a row (2 lane halves x 2 column waves) are merged through LDS and the block
+//                           writes its list to workspace[split][row][LS]
+//       EPI 1 (member)      per lane one bit, any(d2 <= thr[j]); OR-ed through LDS; workspace[split][row] one byte
+//   pr_kth_merge_kernel     one thread per row: the lists of all splits -> the (k+1)-th key -> sqrtf -> fp16
+//   pr_member_merge_kernel  one thread per probe: OR over the splits
+// No atomics, no kernel waits on another block, every partial has one writer: identical bytes from run to run, independent of block order.
+namespace {
+
+constexpr int PR_BM = 128;                           // tile side, rows and columns
+constexpr int PR_BK = 32;                            // halves per K step (two 32x32x16 MFMA steps)
+constexpr int PR_LDK = 40;                           // halves per LDS row: 80 bytes, 5 16-byte slots -> 16 consecutive rows hit 16 distinct slots
+constexpr int PR_JT = 8;                             // column tiles per block
+constexpr int PR_THREADS = 256;
+constexpr int PR_MAX_K1 = 8;
+constexpr int64_t PR_MAX_ROWS = (int64_t)1 << 24;
+constexpr int PR_MAX_FPAD = 1 << 16;
+constexpr uint32_t PR_KEY_LAST = 0xffffffffu;
+constexpr int PR_TILE_HALVES = PR_BM * PR_LDK;
+
+typedef _Float16 pr_f16x8 __attribute__((ext_vector_type(8)));
+typedef float pr_f32x16 __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ float pr_nan() { return __uint_as_float(0x7fc00000u); }
+
+// fp16 bits of the contract's distance for a clamped d2 (NaN canonical)
+__device__ __forceinline__ uint16_t pr_dist_bits(float d2) {
+    const float d = sqrtf(d2);
+    const uint16_t b = __half_as_ushort(__float2half_rn(d));
+    return d != d ? (uint16_t)0x7e00u : b;
+}
+
+template <int LS>
+__device__ __forceinline__ void pr_insert(uint32_t (&l)[LS], uint32_t x) {
+#pragma unroll
+    for (int t = LS - 1; t > 0; t--) l[t] = max(l[t - 1], min(l[t], x));       // the median of (l[t-1] <= l[t], x)
+    l[0] = min(l[0], x);
+}
+
+__global__ __launch_bounds__(PR_THREADS) void pr_pack_kernel(const float* __restrict__ x, int64_t n, int F, int Fpad, uint16_t* __restrict__ out,
+                                                             float* __restrict__ norms) {
+    const int64_t row = (int64_t)blockIdx.x * (PR_THREADS / 64) + (threadIdx.x >> 6);
+    if (row >= n) return;                                                       // wave-uniform
+    const float* __restrict__ src = x + row * F;
+    uint16_t* __restrict__ dst = out + row * Fpad;
+    float s = 0.f;
+    for (int c = lane_id(); c < Fpad; c += 64) {
+        const __half h = __float2half_rn(c < F ? src[c] : 0.f);
+        const float v = __half2float(h);
+        s += v * v;
+        dst[c] = __half_as_ushort(h);
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
+    if (lane_id() == 0) norms[row] = s;
+}
+
+// kth [n] fp16 bits -> thr [n] fp32: the largest d2 with fp16(sqrtf(d2)) <= kth (NaN where none: a NaN or negative kth)
+__global__ __launch_bounds__(PR_THREADS) void pr_thr_kernel(const uint16_t* __restrict__ kth, int64_t n, float* __restrict__ thr) {
+    const int64_t j = (int64_t)blockIdx.x * PR_THREADS + threadIdx.x;
+    if (j >= n) return;
+    const float T = __half2float(__ushort_as_half(kth[j]));
+    auto pred = [T](uint32_t key) { return __half2float(__ushort_as_half(pr_dist_bits(__uint_as_float(key)))) <= T; };
+    uint32_t lo = 0u, hi = 0x7f800000u;
+    float r;
+    if (!pred(lo)) {
+        r = pr_nan();
+    } else if (pred(hi)) {
+        r = __uint_as_float(hi);
+    } else {
+        while (hi - lo > 1u) {                                                  // pred(lo) holds, pred(hi) does not: 31 steps
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (pred(mid)) lo = mid; else hi = mid;
+        }
+        r = __uint_as_float(lo);
+    }
+    thr[j] = r;
+}
+
+// EPI 0: out = uint32 lists [splits][nr][LS].  EPI 1: out = bytes [splits][nr]; cthr = thr of the columns.
+template <int EPI, int LS>
+__global__ __launch_bounds__(PR_THREADS) void pr_tile_kernel(const uint16_t* __restrict__ rows, const float* __restrict__ rnorm, int64_t nr,
+                                                             const uint16_t* __restrict__ cols, const float* __restrict__ cnorm,
+                                                             const float* __restrict__ cthr, int64_t nc, int Fpad, void* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) uint16_t stage[2][2][PR_TILE_HALVES];      // [buffer][0 columns (A) / 1 rows (B)]
+    __shared__ __attribute__((aligned(16))) float cn[PR_BM];                            // norms of the tile's columns, NaN past nc
+    __shared__ __attribute__((aligned(16))) float ct[PR_BM];                            // EPI 1: their thresholds, NaN past nc
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int wi = w & 1, wj = w >> 1, r = lane & 31, h = lane >> 5;
+    const int64_t i0 = (int64_t)blockIdx.x * PR_BM;
+    const int64_t jtiles = (nc + PR_BM - 1) / PR_BM;
+    const int64_t jt0 = (int64_t)blockIdx.y * PR_JT, jt1 = min(jtiles, jt0 + PR_JT);
+    const int ksteps = Fpad / PR_BK;
+
+    // staging: thread t moves 16-byte chunk (t & 3) of rows (t >> 2) and 64 + (t >> 2) of each operand
+    const int srow = t >> 2, schunk = (t & 3) * 8;
+    const uint16_t* const bsrc0 = rows + min(i0 + srow, nr - 1) * Fpad + schunk;
+    const uint16_t* const bsrc1 = rows + min(i0 + srow + 64, nr - 1) * Fpad + schunk;
+    const int soff0 = srow * PR_LDK + schunk, soff1 = (srow + 64) * PR_LDK + schunk;
+    float na[2];
+#pragma unroll
+    for (int it = 0; it < 2; it++) na[it] = rnorm[min(i0 + wi * 64 + it * 32 + r, nr - 1)];
+
+    uint32_t list[2][LS];
+#pragma unroll
+    for (int it = 0; it < 2; it++)
+#pragma unroll
+        for (int e = 0; e < LS; e++) list[it][e] = PR_KEY_LAST;
+    uint32_t hit[2] = {0u, 0u};
+
+    for (int64_t jt = jt0; jt < jt1; jt++) {
+        const int64_t j0 = jt * PR_BM;
+        const uint16_t* const asrc0 = cols + min(j0 + srow, nc - 1) * Fpad + schunk;
+        const uint16_t* const asrc1 = cols + min(j0 + srow + 64, nc - 1) * Fpad + schunk;
+        if (t < PR_BM) {
+            const bool in = j0 + t < nc;
+            cn[t] = in ? cnorm[j0 + t] : pr_nan();
+            if (EPI == 1) ct[t] = in ? cthr[j0 + t] : pr_nan();
+        }
+        pr_f32x16 acc[2][2];
+#pragma unroll
+        for (int a = 0; a < 2; a++)
+#pragma unroll
+            for (int b = 0; b < 2; b++)
+#pragma unroll
+                for (int e = 0; e < 16; e++) acc[a][b][e] = 0.f;
+
+        auto ld = [](const uint16_t* p) { return *reinterpret_cast<const uint4*>(p); };
+        auto st = [](uint16_t* p, const uint4& v) { *reinterpret_cast<uint4*>(p) = v; };
+        uint4 ga0 = ld(asrc0), ga1 = ld(asrc1), gb0 = ld(bsrc0), gb1 = ld(bsrc1);
+        st(&stage[0][0][soff0], ga0);
+        st(&stage[0][0][soff1], ga1);
+        st(&stage[0][1][soff0], gb0);
+        st(&stage[0][1][soff1], gb1);
+        __syncthreads();
+        for (int ks = 0; ks < ksteps; ks++) {
+            const int cur = ks & 1;
+            const bool more = ks + 1 < ksteps;                                  // block-uniform
+            if (more) {
+                const int ko = (ks + 1) * PR_BK;
+                ga0 = ld(asrc0 + ko);
+                ga1 = ld(asrc1 + ko);
+                gb0 = ld(bsrc0 + ko);
+                gb1 = ld(bsrc1 + ko);
+            }
+#pragma unroll
+            for (int kk = 0; kk < PR_BK / 16; kk++) {
+                pr_f16x8 fa[2], fb[2];
+#pragma unroll
+                for (int s = 0; s < 2; s++) {
+                    fa[s] = *reinterpret_cast<const pr_f16x8*>(&stage[cur][0][(wj * 64 + s * 32 + r) * PR_LDK + kk * 16 + h * 8]);
+                    fb[s] = *reinterpret_cast<const pr_f16x8*>(&stage[cur][1][(wi * 64 + s * 32 + r) * PR_LDK + kk * 16 + h * 8]);
+                }
+#pragma unroll
+                for (int a = 0; a < 2; a++)
+#pragma unroll
+                    for (int b = 0; b < 2; b++) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[a], fb[b], acc[a][b], 0, 0, 0);
+            }
+            if (more) {
+                st(&stage[cur ^ 1][0][soff0], ga0);
+                st(&stage[cur ^ 1][0][soff1], ga1);
+                st(&stage[cur ^ 1][1][soff0], gb0);
+                st(&stage[cur ^ 1][1][soff1], gb1);
+            }
+            __syncthreads();
+        }
+        // accumulator element e of tile (a, b): column j0 + wj*64 + a*32 + 8*(e >> 2) + 4*h + (e & 3), row i0 + wi*64 + b*32 + r
+#pragma unroll
+        for (int a = 0; a < 2; a++)
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const int jl = wj * 64 + a * 32 + 8 * g + 4 * h;
+                const float4 nb = *reinterpret_cast<const float4*>(&cn[jl]);
+                float4 th = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (EPI == 1) th = *reinterpret_cast<const float4*>(&ct[jl]);
+#pragma unroll
+                for (int b = 0; b < 2; b++) {
+                    auto element = [&](float dot, float nbe, float the) {
+                        const float d2 = fmaf_(-2.0f, dot, na[b] + nbe);                            // 2 * dot is exact: one rounding
+                        if (EPI == 0) pr_insert<LS>(list[b], d2 < 0.f ? 0u : __float_as_uint(d2));   // the sum of two norms is never -0
+                        else hit[b] |= d2 <= the ? 1u : 0u;                                          // a negative d2 clamps to 0 <= thr
+                    };
+                    element(acc[a][b][4 * g + 0], nb.x, th.x);
+                    element(acc[a][b][4 * g + 1], nb.y, th.y);
+                    element(acc[a][b][4 * g + 2], nb.z, th.z);
+                    element(acc[a][b][4 * g + 3], nb.w, th.w);
+                }
+            }
+        __syncthreads();                                                        // cn / ct and the staging buffers are rewritten next
+    }
+
+    if (EPI == 0) {
+        uint32_t* lds = reinterpret_cast<uint32_t*>(&stage[0][0][0]);           // [128 rows][4 sources][LS]: 16 KiB at LS = 8
+#pragma unroll
+        for (int b = 0; b < 2; b++)
+#pragma unroll
+            for (int e = 0; e < LS; e++) lds[((wi * 64 + b * 32 + r) * 4 + wj * 2 + h) * LS + e] = list[b][e];
+        __syncthreads();
+        if (t < PR_BM && i0 + t < nr) {
+            uint32_t m[LS];
+#pragma unroll
+            for (int e = 0; e < LS; e++) m[e] = PR_KEY_LAST;
+#pragma unroll
+            for (int s = 0; s < 4 * LS; s++) pr_insert<LS>(m, lds[t * 4 * LS + s]);
+            uint32_t* dst = reinterpret_cast<uint32_t*>(out) + ((int64_t)blockIdx.y * nr + i0 + t) * LS;
+#pragma unroll
+            for (int e = 0; e < LS; e++) dst[e] = m[e];
+        }
+    } else {
+        uint32_t* lds = reinterpret_cast<uint32_t*>(&stage[0][0][0]);           // [128 rows][4 sources]
+#pragma unroll
+        for (int b = 0; b < 2; b++) lds[(wi * 64 + b * 32 + r) * 4 + wj * 2 + h] = hit[b];
+        __syncthreads();
+        if (t < PR_BM && i0 + t < nr) {
+            const uint32_t any = lds[t * 4] | lds[t * 4 + 1] | lds[t * 4 + 2] | lds[t * 4 + 3];
+            reinterpret_cast<uint8_t*>(out)[(int64_t)blockIdx.y * nr + i0 + t] = (uint8_t)any;
+        }
+    }
+}
+
+template <int LS>
+__global__ __launch_bounds__(PR_THREADS) void pr_kth_merge_kernel(const uint32_t* __restrict__ lists, int64_t nr, int splits, int k1,
+                                                                  uint16_t* __restrict__ kth) {
+    const int64_t i = (int64_t)blockIdx.x * PR_THREADS + threadIdx.x;
+    if (i >= nr) return;
+    uint32_t m[LS];
+#pragma unroll
+    for (int e = 0; e < LS; e++) m[e] = PR_KEY_LAST;
+    for (int s = 0; s < splits; s++) {
+        const uint32_t* src = lists + ((int64_t)s * nr + i) * LS;
+#pragma unroll
+        for (int e = 0; e < LS; e++) pr_insert<LS>(m, src[e]);
+    }
+    uint32_t key = m[0];
+#pragma unroll
+    for (int e = 1; e < LS; e++) key = e == k1 - 1 ? m[e] : key;
+    kth[i] = pr_dist_bits(__uint_as_float(key));
+}
+
+__global__ __launch_bounds__(PR_THREADS) void pr_member_merge_kernel(const uint8_t* __restrict__ part, int64_t np, int splits, uint8_t* __restrict__ member) {
+    const int64_t i = (int64_t)blockIdx.x * PR_THREADS + threadIdx.x;
+    if (i >= np) return;
+    uint8_t any = 0;
+    for (int s = 0; s < splits; s++) any |= part[(int64_t)s * np + i];
+    member[i] = any ? 1 : 0;
+}
+
+inline int64_t pr_splits(int64_t nc) { return cdiv64(cdiv64(nc, PR_BM), PR_JT); }
+inline int pr_list_size(int k1) { return k1 <= 4 ? 4 : 8; }
+inline int64_t pr_align16(int64_t b) { return (b + 15) & ~(int64_t)15; }
+inline bool pr_shape_ok(int64_t n) { return n >= 1 && n <= PR_MAX_ROWS; }
+
+}  // namespace
+
+TDGP_API int tdgp_pr_pack(const float* x, int64_t n, int F, uint16_t* packed, int Fpad, float* norms, tdgp_stream_t stream) {
+    TDGP_CHECK(x && packed && norms, TDGP_EINVAL, "pr_pack: null pointer");
+    TDGP_CHECK(pr_shape_ok(n), TDGP_EINVAL, "pr_pack: %lld rows outside [1, %lld]", (long long)n, (long long)PR_MAX_ROWS);
+    TDGP_CHECK(F >= 1 && Fpad >= F && Fpad % PR_BK == 0 && Fpad <= PR_MAX_FPAD, TDGP_EINVAL,
+               "pr_pack: F = %d, Fpad = %d need 1 <= F <= Fpad <= %d and Fpad a multiple of %d", F, Fpad, PR_MAX_FPAD, PR_BK);
+    TDGP_CHECK(((uintptr_t)packed & 15) == 0, TDGP_EINVAL, "pr_pack: the packed rows must be 16-byte aligned");
+    TDGP_LAUNCH("pr_pack_kernel", pr_pack_kernel, dim3((unsigned)cdiv64(n, PR_THREADS / 64)), dim3(PR_THREADS), 0, (hipStream_t)stream, x, n, F, Fpad,
+                packed, norms);
+    TDGP_LAUNCH_CHECK();
+    return TDGP_OK;
+}
+
+TDGP_API int64_t tdgp_pr_kth_workspace_bytes(int64_t nr, int64_t nc, int k1) {
+    if (!pr_shape_ok(nr) || !pr_shape_ok(nc) || k1 < 1 || k1 > PR_MAX_K1) return -1;
+    return pr_align16(pr_splits(nc) * nr * pr_list_size(k1) * 4);
+}
+
+TDGP_API int tdgp_pr_kth(const uint16_t* rows, const float* row_norms, int64_t nr, const uint16_t* cols, const float* col_norms, int64_t nc, int Fpad,
+                         int k1, uint16_t* kth, void* workspace, int64_t workspace_bytes, tdgp_stream_t stream) {
+    TDGP_CHECK(rows && row_norms && cols && col_norms && kth && workspace, TDGP_EINVAL, "pr_kth: null pointer");
+    TDGP_CHECK(pr_shape_ok(nr) && pr_shape_ok(nc), TDGP_EINVAL, "pr_kth: %lld rows x %lld columns outside [1, %lld]", (long long)nr, (long long)nc,
+               (long long)PR_MAX_ROWS);
+    TDGP_CHECK(k1 >= 1 && k1 <= PR_MAX_K1, TDGP_EINVAL, "pr_kth: k + 1 = %d outside [1, %d]", k1, PR_MAX_K1);
+    TDGP_CHECK(k1 <= nc, TDGP_EINVAL, "pr_kth: k + 1 = %d exceeds the %lld columns (k + 1 > Nc)", k1, (long long)nc);
+    TDGP_CHECK(Fpad >= PR_BK && Fpad % PR_BK == 0 && Fpad <= PR_MAX_FPAD, TDGP_EINVAL, "pr_kth: Fpad = %d must be a multiple of %d in [%d, %d]", Fpad, PR_BK,
+               PR_BK, PR_MAX_FPAD);
+    TDGP_CHECK((((uintptr_t)rows | (uintptr_t)cols | (uintptr_t)workspace) & 15) == 0 && ((uintptr_t)kth & 1) == 0, TDGP_EINVAL,
+               "pr_kth: packed rows and workspace must be 16-byte aligned");
+    const int64_t need = tdgp_pr_kth_workspace_bytes(nr, nc, k1);
+    TDGP_CHECK(workspace_bytes >= need, TDGP_EINVAL, "pr_kth: workspace of %lld bytes, %lld needed (workspace too small)", (long long)workspace_bytes,
+               (long long)need);
+    hipStream_t st = (hipStream_t)stream;
+    const int splits = (int)pr_splits(nc);
+    const dim3 grid((unsigned)cdiv64(nr, PR_BM), (unsigned)splits);
+    const float* none = nullptr;
+    if (pr_list_size(k1) == 4) {
+        TDGP_LAUNCH("pr_tile_kernel_kth", (pr_tile_kernel<0, 4>), grid, dim3(PR_THREADS), 0, st, rows, row_norms, nr, cols, col_norms, none, nc, Fpad, workspace);
+        TDGP_LAUNCH_CHECK();
+        TDGP_LAUNCH("pr_kth_merge_kernel", pr_kth_merge_kernel<4>, dim3((unsigned)cdiv64(nr, PR_THREADS)), dim3(PR_THREADS), 0, st,
+                    (const uint32_t*)workspace, nr, splits, k1, kth);
+    } else {
+        TDGP_LAUNCH("pr_tile_kernel_kth", (pr_tile_kernel<0, 8>), grid, dim3(PR_THREADS), 0, st, rows, row_norms, nr, cols, col_norms, none, nc, Fpad, workspace);
+        TDGP_LAUNCH_CHECK();
+        TDGP_LAUNCH("pr_kth_merge_kernel", pr_kth_merge_kernel<8>, dim3((unsigned)cdiv64(nr, PR_THREADS)), dim3(PR_THREADS), 0, st,
+                    (const uint32_t*)workspace, nr, splits, k1, kth);
+    }
+    TDGP_LAUNCH_CHECK();
+    return TDGP_OK;
+}
+
+TDGP_API int64_t tdgp_pr_member_workspace_bytes(int64_t np, int64_t nc) {
+    if (!pr_shape_ok(np) || !pr_shape_ok(nc)) return -1;
+    return pr_align16(nc * 4) + pr_align16(pr_splits(nc) * np);
+}
+
+TDGP_API int tdgp_pr_member(const uint16_t* probes, const float* probe_norms, int64_t np, const uint16_t* cols, const float* col_norms,
+                            const uint16_t* kth, int64_t nc, int Fpad, uint8_t* member, void* workspace, int64_t workspace_bytes, tdgp_stream_t stream) {
+    TDGP_CHECK(probes && probe_norms && cols && col_norms && kth && member && workspace, TDGP_EINVAL, "pr_member: null pointer");
+    TDGP_CHECK(pr_shape_ok(np) && pr_shape_ok(nc), TDGP_EINVAL, "pr_member: %lld probes x %lld columns outside [1, %lld]", (long long)np, (long long)nc,
+               (long long)PR_MAX_ROWS);
+    TDGP_CHECK(Fpad >= PR_BK && Fpad % PR_BK == 0 && Fpad <= PR_MAX_FPAD, TDGP_EINVAL, "pr_member: Fpad = %d must be a multiple of %d in [%d, %d]", Fpad,
+               PR_BK, PR_BK, PR_MAX_FPAD);
+    TDGP_CHECK((((uintptr_t)probes | (uintptr_t)cols | (uintptr_t)workspace) & 15) == 0 && ((uintptr_t)kth & 1) == 0, TDGP_EINVAL,
+               "pr_member: packed rows and workspace must be 16-byte aligned");
+    const int64_t need = tdgp_pr_member_workspace_bytes(np, nc);
+    TDGP_CHECK(workspace_bytes >= need, TDGP_EINVAL, "pr_member: workspace of %lld bytes, %lld needed (workspace too small)", (long long)workspace_bytes,
+               (long long)need);
+    hipStream_t st = (hipStream_t)stream;
+    const int splits = (int)pr_splits(nc);
+    float* thr = (float*)workspace;
+    uint8_t* part = (uint8_t*)workspace + pr_align16(nc * 4);
+    TDGP_LAUNCH("pr_thr_kernel", pr_thr_kernel, dim3((unsigned)cdiv64(nc, PR_THREADS)), dim3(PR_THREADS), 0, st, kth, nc, thr);
+    TDGP_LAUNCH_CHECK();
+    TDGP_LAUNCH("pr_tile_kernel_member", (pr_tile_kernel<1, 4>), dim3((unsigned)cdiv64(np, PR_BM), (unsigned)splits), dim3(PR_THREADS), 0, st, probes,
+                probe_norms, np, cols, col_norms, (const float*)thr, nc, Fpad, (void*)part);
+    TDGP_LAUNCH_CHECK();
+    TDGP_LAUNCH("pr_member_merge_kernel", pr_member_merge_kernel, dim3((unsigned)cdiv64(np, PR_THREADS)), dim3(PR_THREADS), 0, st, (const uint8_t*)part, np,
+                splits, member);
+    TDGP_LAUNCH_CHECK();
+    return TDGP_OK;
+}

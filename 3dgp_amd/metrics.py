@@ -1,4 +1,5 @@
-"""FID-side aggregation and camera priors of the generator harness (host side).
+"""FID-side aggregation, the feature-space metrics (precision / recall, KID, IS) and camera priors of the generator harness
+(host side).
 
 Reference: `src/metrics/metric_utils.py:104-169` (FeatureStats), `:288-320` (compute_feature_stats_for_generator),
 `src/metrics/frechet_inception_distance.py:20-39` (compute_fid), `src/training/rendering_utils.py:72-156` (camera priors).
@@ -6,7 +7,8 @@ Reference: `src/metrics/metric_utils.py:104-169` (FeatureStats), `:288-320` (com
 These are host-side pieces: fp64 mean / covariance accumulation in numpy, `scipy.linalg.sqrtm` for the Frechet distance, the
 camera prior samplers (torch RNG in the reference's draw order, scipy for the truncated normal).  The device work they drive is
 the generator forward (HIP) and ONE all-gather per feature block (`distributed.FeatureGatherer`, RCCL) instead of the
-reference's `world` sequential broadcasts.  The Inception detector itself is a URL-fetched TorchScript pickle
+reference's `world` sequential broadcasts.  Precision / recall (`src/metrics/precision_recall.py`) is the exception: its k-NN distance
+passes run on the fp16 matrix pipe (`tdgp_pr_kth` / `tdgp_pr_member`, csrc/metrics.hip) and no distance leaves the device.  The Inception detector itself is a URL-fetched TorchScript pickle
 (`frechet_inception_distance.py:22`) and is not reproduced: `detector` is any callable `uint8 images [N,3,H,W] -> features [N,F]`.
 """
 import numpy as np
@@ -329,6 +331,217 @@ def compute_flattened_depth_maps(G, max_items, batch_size=64, batch_gen=None, ca
             depths.append(out.depth)
         stats.append_torch(torch.cat(depths).flatten(start_dim=1), num_gpus=num_gpus, rank=rank, gatherer=gatherer)
     return torch.from_numpy(stats.get_all())
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# feature-space metrics: precision / recall, KID, IS (src/metrics/{precision_recall,kernel_inception_distance,inception_score}.py;
+# registry entries pr50k3[_full], kid50k[_full], is50k of metric_main.py) on captured feature rows
+# ----------------------------------------------------------------------------------------------------------------------
+PR_K_STEP = 32                          # halves per K step of the tile loop (csrc/metrics.hip PR_BK): packed rows are padded to a multiple
+PR_MAX_NHOOD = 7                        # k + 1 <= 8 sorted entries per lane
+
+
+class _PackedRows:
+    """Feature rows as the k-NN kernels read them: fp16 [N, Fpad] (zero padded) and the fp32 norms of the rounded rows (tdgp_pr_pack)."""
+    __slots__ = ('half', 'norms', 'n', 'features')
+
+    def __init__(self, x, what):
+        from . import _lib
+        _check_rows(x, what)
+        _lib.require_cuda(x, what)
+        x = _lib.f32c(x)
+        self.n, self.features = int(x.shape[0]), int(x.shape[1])
+        fpad = -(-self.features // PR_K_STEP) * PR_K_STEP
+        self.half = torch.empty([self.n, fpad], dtype=torch.float16, device=x.device)
+        self.norms = torch.empty([self.n], dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.call('tdgp_pr_pack', x.data_ptr(), self.n, self.features, self.half.data_ptr(), fpad, self.norms.data_ptr(), _lib.stream_of(x))
+
+
+def _check_rows(x, what):
+    if not isinstance(x, torch.Tensor) or x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f'{what}: expected a non-empty [N, F] tensor of feature rows, got {getattr(x, "shape", type(x))}')
+
+
+def _check_nhood(nhood_size, num_cols):
+    nhood_size = int(nhood_size)
+    if not 0 <= nhood_size <= PR_MAX_NHOOD:
+        raise ValueError(f'nhood_size = {nhood_size} outside [0, {PR_MAX_NHOOD}]')
+    if nhood_size + 1 > num_cols:
+        raise ValueError(f'nhood_size + 1 = {nhood_size + 1} exceeds the {num_cols} manifold rows (k + 1 > Nc)')
+    return nhood_size
+
+
+def _width(x):
+    return x.features if isinstance(x, _PackedRows) else x.shape[1]
+
+
+def _check_same_width(a, b, what_a, what_b):
+    if _width(a) != _width(b):
+        raise ValueError(f'feature width mismatch (F): {what_a} has {_width(a)} features, {what_b} has {_width(b)}')
+
+
+def pack_feature_rows(x, what='features'):
+    """Feature rows [N, F] on the GPU -> the packed form the k-NN passes read (fp16 rows and fp32 norms, tdgp_pr_pack).  `compute_distances_kth`
+    and `compute_manifold_membership` take it in place of a tensor, so a set used by several calls is packed once."""
+    return x if isinstance(x, _PackedRows) else _PackedRows(x, what)
+
+
+def _pr_kth(manifold, k1):
+    from . import _lib
+    h = manifold.half
+    kth = torch.empty([manifold.n], dtype=torch.float16, device=h.device)
+    need = int(_lib.load().tdgp_pr_kth_workspace_bytes(manifold.n, manifold.n, k1))
+    if need < 0:
+        raise RuntimeError(f'tdgp_pr_kth refuses {manifold.n} rows with k + 1 = {k1}')
+    ws = torch.empty([need], dtype=torch.uint8, device=h.device)
+    with torch.cuda.device(h.device):
+        _lib.call('tdgp_pr_kth', h.data_ptr(), manifold.norms.data_ptr(), manifold.n, h.data_ptr(), manifold.norms.data_ptr(), manifold.n, h.shape[1], k1,
+                  kth.data_ptr(), ws.data_ptr(), need, _lib.stream_of(h))
+    return kth
+
+
+def _pr_member(probes, manifold, kth):
+    from . import _lib
+    h = probes.half
+    member = torch.empty([probes.n], dtype=torch.uint8, device=h.device)
+    need = int(_lib.load().tdgp_pr_member_workspace_bytes(probes.n, manifold.n))
+    if need < 0:
+        raise RuntimeError(f'tdgp_pr_member refuses {probes.n} probes x {manifold.n} manifold rows')
+    ws = torch.empty([need], dtype=torch.uint8, device=h.device)
+    with torch.cuda.device(h.device):
+        _lib.call('tdgp_pr_member', h.data_ptr(), probes.norms.data_ptr(), probes.n, manifold.half.data_ptr(), manifold.norms.data_ptr(), kth.data_ptr(),
+                  manifold.n, h.shape[1], member.data_ptr(), ws.data_ptr(), need, _lib.stream_of(h))
+    return member.bool()
+
+
+def compute_distances_kth(manifold, nhood_size):
+    """precision_recall.py:50-54: for every manifold row the (nhood_size + 1)-th smallest fp16 distance to ALL manifold rows (the row itself
+    is one of them, duplicates count separately; `dist.kthvalue(nhood_size + 1)`), fp16 [N] on the device.  tdgp_pr_kth: the distances
+    live in MFMA accumulators only (contract in include/tdgp.h).  `manifold`: a tensor or `pack_feature_rows` of one."""
+    if not isinstance(manifold, _PackedRows):
+        _check_rows(manifold, 'manifold')
+    nhood_size = _check_nhood(nhood_size, manifold.n if isinstance(manifold, _PackedRows) else manifold.shape[0])
+    return _pr_kth(pack_feature_rows(manifold, 'manifold'), nhood_size + 1)
+
+
+def compute_manifold_membership(probes, manifold, kth):
+    """precision_recall.py:55-58: for every probe row whether some manifold row j lies within kth[j] of it, `(dist <= kth).any(dim=1)`;
+    bool [Np] on the device (tdgp_pr_member).  `probes` / `manifold`: tensors or `pack_feature_rows` of them."""
+    for x, what in ((probes, 'probes'), (manifold, 'manifold')):
+        if not isinstance(x, _PackedRows):
+            _check_rows(x, what)
+    _check_same_width(probes, manifold, 'probes', 'manifold')
+    num_cols = manifold.n if isinstance(manifold, _PackedRows) else manifold.shape[0]
+    if not isinstance(kth, torch.Tensor) or kth.shape != (num_cols,):
+        raise ValueError(f'kth: expected one value per manifold row [{num_cols}], got {getattr(kth, "shape", type(kth))}')
+    from . import _lib
+    _lib.require_cuda(kth, 'kth')
+    return _pr_member(pack_feature_rows(probes, 'probes'), pack_feature_rows(manifold, 'manifold'), kth.to(torch.float16).contiguous())
+
+
+def compute_pr(real_features, gen_features, nhood_size=3, row_batch_size=None, col_batch_size=None, num_gpus=1, rank=0):
+    """precision_recall.py:36-60 on captured feature rows -> (precision, recall): precision is the share of generated rows inside the manifold
+    of the real ones (every real row's ball reaches its nhood_size-th neighbour), recall the converse.  GPU only: four tile passes on the
+    fp16 matrix pipe, two bytes per row and one byte per probe come out of them, one read-back per value at the end.  `row_batch_size` /
+    `col_batch_size` are accepted for the reference's signature and ignored (nothing is materialised, so nothing needs batching).  Rank 0
+    computes; the other ranks return NaN as the reference's do."""
+    _check_rows(real_features, 'real_features')
+    _check_rows(gen_features, 'gen_features')
+    _check_same_width(real_features, gen_features, 'real_features', 'gen_features')
+    nhood_size = _check_nhood(nhood_size, min(real_features.shape[0], gen_features.shape[0]))
+    assert 0 <= rank < num_gpus
+    if rank != 0:
+        return float('nan'), float('nan')
+    real, gen = _PackedRows(real_features, 'real_features'), _PackedRows(gen_features, 'gen_features')
+    results = []
+    for manifold, probes in ((real, gen), (gen, real)):
+        member = _pr_member(probes, manifold, _pr_kth(manifold, nhood_size + 1))
+        results.append(member.to(torch.float32).mean())
+    precision, recall = (float(v) for v in torch.stack(results).cpu())
+    return precision, recall
+
+
+def _rows_tensor(x, what):
+    x = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x, dtype=np.float32))
+    _check_rows(x, what)
+    return x.float()
+
+
+def compute_kid(real_features, gen_features, num_subsets=100, max_subset_size=1000):
+    """kernel_inception_distance.py:34-43 on captured feature rows.  The subsets are drawn with `np.random.choice` in the reference's order
+    (generated first, then real, per subset), so a seeded host RNG gives the reference's subsets; the three Gram products and the cube are
+    fp32 torch ops on the features' device, every sum is taken in fp64, and the total is read back once."""
+    real, gen = _rows_tensor(real_features, 'real_features'), _rows_tensor(gen_features, 'gen_features')
+    _check_same_width(real, gen, 'real_features', 'gen_features')
+    gen = gen.to(real.device)
+    n = real.shape[1]
+    m = min(min(real.shape[0], gen.shape[0]), int(max_subset_size))
+    if m < 2:
+        raise ValueError(f'subset size m = {m}: the unbiased estimate divides by m - 1')
+    t = torch.zeros([], dtype=torch.float64, device=real.device)
+    for _ in range(int(num_subsets)):
+        x = gen[torch.from_numpy(np.random.choice(gen.shape[0], m, replace=False)).to(real.device)]
+        y = real[torch.from_numpy(np.random.choice(real.shape[0], m, replace=False)).to(real.device)]
+        a = (x @ x.T / n + 1) ** 3 + (y @ y.T / n + 1) ** 3
+        b = (x @ y.T / n + 1) ** 3
+        t += (a.sum(dtype=torch.float64) - a.diagonal().sum(dtype=torch.float64)) / (m - 1) - b.sum(dtype=torch.float64) * 2 / m
+    return float(t.item() / num_subsets / m)
+
+
+def compute_is(gen_probs, num_splits=10):
+    """inception_score.py:30-36 on captured class probabilities [N, classes] -> (mean, std) of exp(mean KL(p(y|x) || p(y))) over `num_splits`
+    consecutive parts; the reference's operations in fp64 on the probabilities' device."""
+    probs = _rows_tensor(gen_probs, 'gen_probs').double()
+    num_gen = probs.shape[0]
+    scores = []
+    for i in range(int(num_splits)):
+        part = probs[i * num_gen // num_splits: (i + 1) * num_gen // num_splits]
+        kl = part * (torch.log(part) - torch.log(part.mean(dim=0, keepdim=True)))
+        scores.append(torch.exp(kl.sum(dim=1).mean()))
+    scores = torch.stack(scores).cpu().numpy()
+    return float(np.mean(scores)), float(np.std(scores))
+
+
+def _real_rows(real):
+    """Real-side features of the generator-side wrappers: an [N, F] array / tensor, a FeatureStats with capture_all, or the path of a saved one."""
+    if isinstance(real, (str, bytes)) or hasattr(real, '__fspath__'):
+        real = FeatureStats.load(real)
+    if isinstance(real, FeatureStats):
+        real = real.get_all()
+    return real if isinstance(real, torch.Tensor) else torch.from_numpy(np.asarray(real, dtype=np.float32))
+
+
+def _generated_rows(G, detector, num_gen, kw):
+    kw.setdefault('device', _device_of(G))           # the draws are made where the generator lives
+    stats = compute_feature_stats_for_generator(G, detector, max_items=num_gen, capture_all=True, **kw)
+    return torch.from_numpy(stats.get_all())
+
+
+def pr_for_generator(G, detector, real, num_gen=50000, nhood_size=3, **kw):
+    """'pr50k3[_full]' (metric_main.py) for a generator: features of `num_gen` generated images (`compute_feature_stats_for_generator`, whose
+    keywords `kw` are) against the captured real features `real` -> (precision, recall).  Datasets are out of scope: `real` is an array or
+    a saved FeatureStats."""
+    gen = _generated_rows(G, detector, num_gen, kw)
+    device = _device_of(G)
+    return compute_pr(_real_rows(real).to(device), gen.to(device), nhood_size=nhood_size, num_gpus=kw.get('num_gpus', 1), rank=kw.get('rank', 0))
+
+
+def kid_for_generator(G, detector, real, num_gen=50000, num_subsets=100, max_subset_size=1000, **kw):
+    """'kid50k[_full]' for a generator -> the KID estimate; NaN on ranks other than 0 as in the reference."""
+    gen = _generated_rows(G, detector, num_gen, kw)
+    if kw.get('rank', 0) != 0:
+        return float('nan')
+    device = _device_of(G)
+    return compute_kid(_real_rows(real).to(device), gen.to(device), num_subsets=num_subsets, max_subset_size=max_subset_size)
+
+
+def is_for_generator(G, detector, num_gen=50000, num_splits=10, **kw):
+    """'is50k' for a generator whose `detector` returns class probabilities -> (mean, std); NaN on ranks other than 0."""
+    probs = _generated_rows(G, detector, num_gen, kw)
+    if kw.get('rank', 0) != 0:
+        return float('nan'), float('nan')
+    return compute_is(probs.to(_device_of(G)), num_splits=num_splits)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

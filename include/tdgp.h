@@ -446,6 +446,33 @@ int     tdgp_quantile_select(const float* x, int64_t n, int64_t k_lo, int64_t k_
  * 2 <= bins <= 1024, 1 <= pixels < 2^24 (a count stays exact as fp32), 1 <= images <= 65535, lo < hi finite.  `hist` is overwritten. */
 int tdgp_depth_histc(const float* depth, int64_t images, int64_t pixels, float lo, float hi, int bins, int32_t* hist, tdgp_stream_t stream);
 
+/* Precision / recall (src/metrics/precision_recall.py): the k-NN distance passes without a distance matrix in memory.  The reference
+ * takes torch.cdist in fp16 over 10 000 x 10 000 blocks, copies every block to the host and runs kthvalue / <= there.
+ * The distance, fixed so that a CPU check can be bit exact: features rounded to fp16 (RNE, as `.to(torch.float16)`);
+ *   d2(i,j) = max(|a_i|^2 + |b_j|^2 - 2 a_i.b_j, 0): the dot product on v_mfma_f32_32x32x16_f16 (fp16 operands, fp32 accumulation), the
+ *             norms summed in fp32 from the ROUNDED values, fl(fl(|a_i|^2 + |b_j|^2) - 2 dot);
+ *   d = sqrtf(d2) correctly rounded, then rounded once to fp16 (RNE; overflow -> +inf).  Everything downstream compares these fp16 values;
+ *   a NaN distance sorts last and compares false (torch.kthvalue / <=).
+ * tdgp_pr_pack: x [n,F] fp32 -> packed [n,Fpad] fp16 bits, columns F..Fpad-1 zero, and norms [n] fp32.  Fpad: a multiple of 32 (the K step
+ *   of the tile loop, two MFMA steps), F <= Fpad <= 65536; packed 16-byte aligned.
+ * tdgp_pr_kth: kth[i] = the k1-th smallest (k1 = k + 1) of d(i, j) over ALL nc columns as fp16 bits [nr], i.e.
+ *   dist.kthvalue(nhood_size + 1): when rows == cols the self distance is one of the candidates, duplicates count separately; fewer than k1
+ *   non-NaN distances -> NaN (0x7e00).  1 <= k1 <= 8 and k1 <= nc.
+ * tdgp_pr_member: member[i] = 1 if some column j has d(probe i, j) <= kth[j], else 0; uint8 [np].  kth: fp16 bits [nc] (a NaN entry admits
+ *   nobody).
+ * Both sets of a call must have been packed with the SAME Fpad (one Fpad argument serves both; the calls cannot check it).
+ * Both run one tile kernel (128 x 128 tiles, each block a run of 8 column tiles) that leaves a partial per (run, row) in the workspace --
+ * a sorted list of squared distances / one byte -- and a small merge kernel: no atomics, no kernel waits on another block, one writer per
+ * partial, so the same bytes on every run whatever the block order.  1 <= nr, np, nc <= 2^24.
+ * workspace: tdgp_pr_{kth,member}_workspace_bytes bytes (-1 for a shape they refuse), 16-byte aligned, caller-owned. */
+int     tdgp_pr_pack(const float* x, int64_t n, int F, uint16_t* packed, int Fpad, float* norms, tdgp_stream_t stream);
+int64_t tdgp_pr_kth_workspace_bytes(int64_t nr, int64_t nc, int k1);
+int     tdgp_pr_kth(const uint16_t* rows, const float* row_norms, int64_t nr, const uint16_t* cols, const float* col_norms, int64_t nc, int Fpad,
+                    int k1, uint16_t* kth, void* workspace, int64_t workspace_bytes, tdgp_stream_t stream);
+int64_t tdgp_pr_member_workspace_bytes(int64_t np, int64_t nc);
+int     tdgp_pr_member(const uint16_t* probes, const float* probe_norms, int64_t np, const uint16_t* cols, const float* col_norms,
+                       const uint16_t* kth, int64_t nc, int Fpad, uint8_t* member, void* workspace, int64_t workspace_bytes, tdgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,65 @@
+#!/usr/bin/env python3
+"""Feature-space metrics from two saved feature sets (the reference's 'pr50k3', 'kid50k', 'is50k', src/metrics/metric_main.py): one JSON line.
+
+    python tools/calc_feature_metrics.py --real REAL.npz --gen GEN.npz --metrics pr,kid,is [--nhood-size 3] [--seed 0]
+
+`--real` / `--gen` are `FeatureStats.save` files written with capture_all (the detector that produced them is the caller's: the reference
+fetches its own from a URL).  `pr` and `kid` compare the two sets; `is` reads `--gen` as class probabilities.  Precision / recall runs on the
+GPU (its k-NN passes have no CPU path); KID and IS run where the features are put: on the GPU when there is one.
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+METRICS = ('pr', 'kid', 'is')
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    p.add_argument('--real', metavar='STATS.npz', help='FeatureStats.save file of the real features (pr, kid)')
+    p.add_argument('--gen', required=True, metavar='STATS.npz', help='FeatureStats.save file of the generated features (or probabilities, for is)')
+    p.add_argument('--metrics', default='pr,kid,is', help='comma-separated subset of pr,kid,is')
+    p.add_argument('--nhood-size', type=int, default=3)
+    p.add_argument('--num-subsets', type=int, default=100)
+    p.add_argument('--max-subset-size', type=int, default=1000)
+    p.add_argument('--num-splits', type=int, default=10)
+    p.add_argument('--seed', type=int, default=0, help='numpy seed of the KID subsets')
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    names = [m for m in args.metrics.split(',') if m]
+    unknown = sorted(set(names) - set(METRICS))
+    if unknown or not names:
+        raise SystemExit(f'--metrics: unknown {unknown}; choose from {",".join(METRICS)}')
+    if ({'pr', 'kid'} & set(names)) and not args.real:
+        raise SystemExit('--real is needed for pr and kid')
+    if REPO not in sys.path:
+        sys.path.insert(0, REPO)
+    import torch
+    tdgp = importlib.import_module('3dgp_amd')
+    M = tdgp.metrics
+    device = 'cuda' if torch.cuda.is_available() else 'cpu'
+    gen = torch.from_numpy(M.FeatureStats.load(args.gen).get_all()).to(device)
+    real = torch.from_numpy(M.FeatureStats.load(args.real).get_all()).to(device) if args.real else None
+    out = {}
+    if 'pr' in names:
+        out['precision'], out['recall'] = M.compute_pr(real, gen, nhood_size=args.nhood_size)
+        out['nhood_size'] = args.nhood_size
+    if 'kid' in names:
+        np.random.seed(args.seed)
+        out['kid'] = M.compute_kid(real, gen, num_subsets=args.num_subsets, max_subset_size=args.max_subset_size)
+    if 'is' in names:
+        out['is_mean'], out['is_std'] = M.compute_is(gen, num_splits=args.num_splits)
+    out.update(num_real=None if real is None else int(real.shape[0]), num_gen=int(gen.shape[0]), seed=args.seed, real=args.real, gen=args.gen)
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()

@@ -1646,6 +1646,7 @@ def main():
     gen_camera_regs()
     gen_metrics()
     gen_nfs()
+    gen_feature_metrics()
     gen_trajectories()
     gen_harness()
     gen_synthesis_grad()
@@ -1810,6 +1811,86 @@ def gen_nfs():
     finally:
         ref_nfs.metric_utils.compute_flattened_depth_maps = o_maps
     save('nfs', **arrays)
+
+
+FEATURE_METRICS_GOLDEN = dict(seed=0, rows=600, sets=((16, 0.3, 0.8), (32, 0.25, 0.85), (64, 0.2, 0.9)), nhood_size=3, row_batch_size=256, col_batch_size=200,
+                              kid_set=2, kid_seed=7, kid_num_subsets=10, kid_max_subset_size=100, is_seed=1, is_rows=500, is_classes=10, is_splits=5)
+
+
+def feature_metrics_rows(seed, rows, F, shift, scale):
+    """The synthetic feature rows of tests/golden/feature_metrics.npz (fp32): regenerated from the recipe on both sides, never stored."""
+    rs = np.random.RandomState(seed)
+    real = rs.randn(rows, F).astype(np.float32)
+    gen = (rs.randn(rows, F) * scale + shift).astype(np.float32)
+    return real, gen
+
+
+def feature_metrics_probs(seed, rows, classes):
+    """Synthetic class probabilities for the inception score: positive rows that sum to one, no transcendental in the recipe."""
+    u = np.random.RandomState(seed).rand(rows, classes) + 0.05
+    return (u / u.sum(axis=1, keepdims=True)).astype(np.float32)
+
+
+def gen_feature_metrics():
+    """tests/golden/feature_metrics.npz: the reference's own compute_pr / compute_kid / compute_is (src/metrics/precision_recall.py,
+    kernel_inception_distance.py, inception_score.py), unmodified, with metric_utils.compute_feature_stats_for_{dataset,generator} replaced by
+    FeatureStats filled with synthetic rows (the detector is a URL-fetched pickle).  num_gpus = 1, device 'cpu'.  Precision / recall once as
+    shipped (fp16 features and distances) and once with every `.to(torch.float16)` a no-op: the gap is the reference's own sensitivity to
+    the distance rounding.  Only the recipe and the results are stored.    python tools/gen_goldens.py feature_metrics"""
+    from src.metrics import metric_utils as ref_mu
+    from src.metrics import precision_recall as ref_pr
+    from src.metrics import kernel_inception_distance as ref_kid
+    from src.metrics import inception_score as ref_is
+    gg = FEATURE_METRICS_GOLDEN
+    opts = EasyDict(num_gpus=1, rank=0, device=torch.device('cpu'))
+
+    class KeepDtype(torch.Tensor):                      # `.to(torch.float16)` does nothing, everything else as usual
+        def to(self, *args, **kwargs):
+            if args and args[0] is torch.float16:
+                return self
+            return super().to(*args, **kwargs)
+
+    def filled(rows):
+        st = ref_mu.FeatureStats(capture_all=True, max_items=rows.shape[0])
+        st.append(rows)
+        return st
+
+    saved = (ref_mu.compute_feature_stats_for_dataset, ref_mu.compute_feature_stats_for_generator, ref_mu.FeatureStats.get_all_torch)
+    arrays = dict(recipe=np.array(repr(gg)), sets=np.array(gg['sets'], dtype=np.float64),
+                  meta=np.array(['source=reference:src/metrics/{precision_recall,kernel_inception_distance,inception_score}.py', f'torch={torch.__version__}',
+                                 f'numpy={np.__version__}']))
+    try:
+        pr_half, pr_float = [], []
+        for F, shift, scale in gg['sets']:
+            real, gen = feature_metrics_rows(gg['seed'], gg['rows'], F, shift, scale)
+            ref_mu.compute_feature_stats_for_dataset = lambda **kw: filled(real)
+            ref_mu.compute_feature_stats_for_generator = lambda **kw: filled(gen)
+            call = lambda: ref_pr.compute_pr(opts, max_real=gg['rows'], num_gen=gg['rows'], nhood_size=gg['nhood_size'],     # noqa: E731
+                                             row_batch_size=gg['row_batch_size'], col_batch_size=gg['col_batch_size'])
+            ref_mu.FeatureStats.get_all_torch = saved[2]
+            pr_half.append(call())
+            ref_mu.FeatureStats.get_all_torch = lambda self: torch.from_numpy(self.get_all()).as_subclass(KeepDtype)
+            pr_float.append(call())
+            ref_mu.FeatureStats.get_all_torch = saved[2]
+            print(f'feature_metrics: F = {F}: precision / recall {pr_half[-1]} in half, {pr_float[-1]} in float')
+        arrays['pr_half'] = np.array(pr_half, dtype=np.float64)
+        arrays['pr_float'] = np.array(pr_float, dtype=np.float64)
+        F, shift, scale = gg['sets'][gg['kid_set']]
+        real, gen = feature_metrics_rows(gg['seed'], gg['rows'], F, shift, scale)
+        ref_mu.compute_feature_stats_for_dataset = lambda **kw: filled(real)
+        ref_mu.compute_feature_stats_for_generator = lambda **kw: filled(gen)
+        np.random.seed(gg['kid_seed'])
+        arrays['kid'] = np.array(ref_kid.compute_kid(opts, max_real=gg['rows'], num_gen=gg['rows'], num_subsets=gg['kid_num_subsets'],
+                                                     max_subset_size=gg['kid_max_subset_size']), dtype=np.float64)
+        probs = feature_metrics_probs(gg['is_seed'], gg['is_rows'], gg['is_classes'])
+        ref_mu.compute_feature_stats_for_generator = lambda **kw: filled(probs)
+        arrays['inception_score'] = np.array(ref_is.compute_is(opts, num_gen=gg['is_rows'], num_splits=gg['is_splits']), dtype=np.float64)
+        print(f"feature_metrics: kid {float(arrays['kid'])!r}, is {arrays['inception_score']}")
+    finally:
+        ref_mu.compute_feature_stats_for_dataset, ref_mu.compute_feature_stats_for_generator, ref_mu.FeatureStats.get_all_torch = saved
+    for k in ('seed', 'rows', 'nhood_size', 'kid_set', 'kid_seed', 'kid_num_subsets', 'kid_max_subset_size', 'is_seed', 'is_rows', 'is_classes', 'is_splits'):
+        arrays[k] = np.array(gg[k], dtype=np.int64)
+    save('feature_metrics', **arrays)
 
 
 def gen_e2e_all():
