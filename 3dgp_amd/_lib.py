@@ -74,6 +74,8 @@ _PROTOTYPES = {
     'tdgp_pr_kth': (c_int, [P, P, c_int64, P, P, c_int64, c_int, c_int, P, P, c_int64, P]),
     'tdgp_pr_member_workspace_bytes': (c_int64, [c_int64, c_int64]),
     'tdgp_pr_member': (c_int, [P, P, c_int64, P, P, P, c_int64, c_int, P, P, c_int64, P]),
+    'tdgp_moments_workspace_bytes': (c_int64, [c_int64, c_int]),
+    'tdgp_moments_add': (c_int, [P, c_int64, c_int, P, P, P, c_int64, P]),
 }
 EXPORTS = tuple(_PROTOTYPES)
 

@@ -624,3 +624,256 @@ TDGP_API int tdgp_pr_member(const uint16_t* probes, const float* probe_norms, in
     TDGP_LAUNCH_CHECK();
     return TDGP_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------- FID feature moments
+// The raw moments behind the Frechet distance (src/metrics/metric_utils.py:128-161: per feature block `x.sum(0)` and `x.T @ x` in fp64 on
+// HOST arrays): s1 += sum of rows, s2 += rows^T rows, for fp32 rows on the device.
+//
+// Contract (include/tdgp.h): every row value widened fp32 -> fp64 (exact), every product formed in fp64 (exact: 24 + 24 <= 53 bits), only the
+// additions round; the Gram part on v_mfma_f64_16x16x4_f64; s2 symmetric bit for bit; no atomics; the partition a function of (n, F) alone.
+//
+//   mom_tile_kernel<DIRECT>  block = one 64 x 64 tile of s2 ON OR ABOVE the diagonal x one run of rows; 4 waves as 2 x 2, each 32 x 32 = 2 x 2
+//                            MFMA tiles (32 accumulator registers).  K loop: 32 rows per step, the two column strips of the rows staged as
+//                            fp32 through registers into two LDS buffers (80-float rows: the 4 x 16 fragment reads of a wave half fall on 32
+//                            distinct banks), widened at the fragment read, one barrier per step.  A diagonal block stages one strip, skips the
+//                            wave below the diagonal and also sums its strip's columns (s1).  Values past n or F are staged as zeros.
+//       DIRECT (one run)     adds the tile to s2 in place and writes it to both sides of the diagonal (transposed through LDS, so both
+//                            stores are row-contiguous); of a diagonal tile only the elements on or above the diagonal are used
+//       otherwise            writes the tile and the column sums to workspace[run]
+//   mom_merge_kernel         block = one tile: s2 + the runs' partials in run order, then the same two-sided store; s1 likewise
+namespace {
+
+constexpr int MOM_T = 64;                            // tile edge of s2
+constexpr int MOM_C = 32;                            // rows per K step
+constexpr int MOM_LD = 80;                           // floats per staged LDS row
+constexpr int MOM_THREADS = 256;
+constexpr int MOM_RUN_MIN = 512;                     // a run of rows is at least this long ...
+constexpr int MOM_BLOCKS = 2048;                     // ... and tiles x runs stays within this many blocks
+constexpr int MOM_MAX_F = 16384;
+constexpr int64_t MOM_MAX_N = (int64_t)1 << 31;
+constexpr int MOM_TLD = MOM_T + 1;                   // doubles per row of the epilogue tile
+constexpr int MOM_LDS_BYTES = 2 * 2 * MOM_C * MOM_LD * 4;
+static_assert(MOM_LDS_BYTES >= MOM_T * MOM_TLD * 8, "the epilogue tile reuses the staging buffers");
+
+typedef double mom_f64x4 __attribute__((ext_vector_type(4)));
+
+struct MomPlan { int t1; int64_t tiles; int64_t run_rows; int64_t runs; };
+
+inline MomPlan mom_plan(int64_t n, int F) {
+    MomPlan p;
+    p.t1 = cdiv(F, MOM_T);
+    p.tiles = (int64_t)p.t1 * (p.t1 + 1) / 2;
+    const int64_t max_runs = std::max<int64_t>(1, MOM_BLOCKS / p.tiles);
+    p.run_rows = cdiv64(std::max<int64_t>(MOM_RUN_MIN, cdiv64(n, max_runs)), MOM_C) * MOM_C;
+    p.runs = std::max<int64_t>(1, cdiv64(n, p.run_rows));
+    return p;
+}
+inline bool mom_shape_ok(int64_t n, int F) { return n >= 0 && n < MOM_MAX_N && F >= 1 && F <= MOM_MAX_F; }
+
+// linear index over the tiles on or above the diagonal, row by row -> (ti <= tj)
+__device__ __forceinline__ void mom_tile_of(int idx, int t1, int& ti, int& tj) {
+    int i = 0;
+    while (idx >= t1 - i) { idx -= t1 - i; i++; }
+    ti = i;
+    tj = i + idx;
+}
+
+// the finished tile in LDS (`tile[r][c]` = s2[f0 + r][g0 + c]) -> both sides of the diagonal; a diagonal tile is read on or above its diagonal only
+__device__ __forceinline__ void mom_store_tile(const double* tile, double* __restrict__ s2, int F, int f0, int g0, bool diag) {
+    for (int idx = threadIdx.x; idx < MOM_T * MOM_T; idx += MOM_THREADS) {
+        const int r = idx >> 6, c = idx & 63;
+        if (diag) {
+            if (f0 + r < F && f0 + c < F) s2[(int64_t)(f0 + r) * F + f0 + c] = r <= c ? tile[r * MOM_TLD + c] : tile[c * MOM_TLD + r];
+        } else {
+            if (f0 + r < F && g0 + c < F) s2[(int64_t)(f0 + r) * F + g0 + c] = tile[r * MOM_TLD + c];
+            if (g0 + r < F && f0 + c < F) s2[(int64_t)(g0 + r) * F + f0 + c] = tile[c * MOM_TLD + r];
+        }
+    }
+}
+
+template <bool DIRECT>
+__global__ __launch_bounds__(MOM_THREADS) void mom_tile_kernel(const float* __restrict__ rows, int64_t n, int F, int t1, int64_t run_rows,
+                                                               double* __restrict__ s1, double* __restrict__ s2, double* __restrict__ ws2,
+                                                               double* __restrict__ ws1) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[MOM_LDS_BYTES];
+    __shared__ double red[MOM_THREADS / 64][MOM_T];
+    float* const stage = reinterpret_cast<float*>(lds_raw);                     // [buffer][0 strip f / 1 strip g][MOM_C][MOM_LD]
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int wi = w >> 1, wj = w & 1, lc = lane & 15, lk = lane >> 4;
+    int ti, tj;
+    mom_tile_of((int)blockIdx.x, t1, ti, tj);
+    const bool diag = ti == tj;
+    const int f0 = ti * MOM_T, g0 = tj * MOM_T;
+    const int64_t k0 = (int64_t)blockIdx.y * run_rows, k1 = min(n, k0 + run_rows);
+    const int ksteps = (int)((k1 - k0 + MOM_C - 1) / MOM_C);
+    const bool work = !diag || wi <= wj;                                         // wave-uniform
+
+    // staging: thread t moves column (t & 63) of rows (t >> 6) + 4 i of each strip
+    const int sc = t & 63, sr = t >> 6;
+    const bool fin = f0 + sc < F, gin = !diag && g0 + sc < F;
+    const float* const fsrc = rows + f0 + sc;
+    const float* const gsrc = rows + g0 + sc;
+    float rf[MOM_C / 4], rg[MOM_C / 4];
+    auto fetch = [&](int ks) {
+        const int64_t kb = k0 + (int64_t)ks * MOM_C + sr;
+#pragma unroll
+        for (int i = 0; i < MOM_C / 4; i++) {
+            const int64_t k = kb + 4 * i;
+            rf[i] = fin && k < k1 ? fsrc[k * F] : 0.f;
+            rg[i] = gin && k < k1 ? gsrc[k * F] : 0.f;
+        }
+    };
+    auto put = [&](int buf) {
+        float* const a = stage + (buf * 2 + 0) * MOM_C * MOM_LD + sr * MOM_LD + sc;
+        float* const b = stage + (buf * 2 + 1) * MOM_C * MOM_LD + sr * MOM_LD + sc;
+#pragma unroll
+        for (int i = 0; i < MOM_C / 4; i++) {
+            a[4 * i * MOM_LD] = rf[i];
+            if (!diag) b[4 * i * MOM_LD] = rg[i];
+        }
+    };
+
+    mom_f64x4 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int b = 0; b < 2; b++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) acc[a][b][e] = 0.0;
+    double colsum = 0.0;
+
+    fetch(0);
+    put(0);
+    __syncthreads();
+    for (int ks = 0; ks < ksteps; ks++) {
+        const int cur = ks & 1;
+        const bool more = ks + 1 < ksteps;                                      // block-uniform
+        if (more) fetch(ks + 1);
+        const float* const A = stage + (cur * 2 + 0) * MOM_C * MOM_LD;
+        const float* const B = diag ? A : stage + (cur * 2 + 1) * MOM_C * MOM_LD;
+        if (work) {
+#pragma unroll
+            for (int kk = 0; kk < MOM_C / 4; kk++) {
+                const int kr = (kk * 4 + lk) * MOM_LD;
+                double fa[2], fb[2];
+#pragma unroll
+                for (int s = 0; s < 2; s++) {
+                    fa[s] = (double)A[kr + wi * 32 + s * 16 + lc];
+                    fb[s] = (double)B[kr + wj * 32 + s * 16 + lc];
+                }
+#pragma unroll
+                for (int a = 0; a < 2; a++)
+#pragma unroll
+                    for (int b = 0; b < 2; b++) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a], fb[b], acc[a][b], 0, 0, 0);
+            }
+        }
+        if (diag) {
+#pragma unroll
+            for (int i = 0; i < MOM_C / 4; i++) colsum += (double)A[(sr * (MOM_C / 4) + i) * MOM_LD + sc];
+        }
+        if (more) put(cur ^ 1);
+        __syncthreads();
+    }
+
+    // column sums of a diagonal block: the four row groups in a fixed order
+    if (diag) {
+        red[sr][sc] = colsum;
+        __syncthreads();
+        if (t < MOM_T && f0 + t < F) {
+            const double v = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+            if (DIRECT) s1[f0 + t] += v;
+            else ws1[((int64_t)blockIdx.y * t1 + ti) * MOM_T + t] = v;
+        }
+    }
+
+    // accumulator element e of MFMA tile (a, b): row (feature f) f0 + wi*32 + a*16 + lk + 4 e, column (feature g) g0 + wj*32 + b*16 + lc
+    if (DIRECT) {
+        double* const tile = reinterpret_cast<double*>(lds_raw);                // the K loop's last barrier is behind every read of `stage`
+        if (work) {
+#pragma unroll
+            for (int a = 0; a < 2; a++)
+#pragma unroll
+                for (int b = 0; b < 2; b++)
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        const int r = wi * 32 + a * 16 + lk + 4 * e, c = wj * 32 + b * 16 + lc;
+                        const bool in = f0 + r < F && g0 + c < F;
+                        const double old = in ? s2[(int64_t)(f0 + r) * F + g0 + c] : 0.0;
+                        tile[r * MOM_TLD + c] = old + acc[a][b][e];
+                    }
+        }
+        __syncthreads();
+        mom_store_tile(tile, s2, F, f0, g0, diag);
+    } else if (work) {
+        double* const dst = ws2 + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (MOM_T * MOM_T);
+#pragma unroll
+        for (int a = 0; a < 2; a++)
+#pragma unroll
+            for (int b = 0; b < 2; b++)
+#pragma unroll
+                for (int e = 0; e < 4; e++) dst[(wi * 32 + a * 16 + lk + 4 * e) * MOM_T + wj * 32 + b * 16 + lc] = acc[a][b][e];
+    }
+}
+
+__global__ __launch_bounds__(MOM_THREADS) void mom_merge_kernel(const double* __restrict__ ws2, const double* __restrict__ ws1, int runs, int F, int t1,
+                                                                double* __restrict__ s1, double* __restrict__ s2) {
+    __shared__ double tile[MOM_T * MOM_TLD];
+    const int t = threadIdx.x;
+    int ti, tj;
+    mom_tile_of((int)blockIdx.x, t1, ti, tj);
+    const bool diag = ti == tj;
+    const int f0 = ti * MOM_T, g0 = tj * MOM_T;
+    for (int idx = t; idx < MOM_T * MOM_T; idx += MOM_THREADS) {
+        const int r = idx >> 6, c = idx & 63;
+        if (f0 + r < F && g0 + c < F && (!diag || (r >> 5) <= (c >> 5))) {      // a diagonal block's wave below the diagonal wrote nothing
+            double v = s2[(int64_t)(f0 + r) * F + g0 + c];
+            for (int s = 0; s < runs; s++) v += ws2[((int64_t)s * gridDim.x + blockIdx.x) * (MOM_T * MOM_T) + idx];
+            tile[r * MOM_TLD + c] = v;
+        }
+    }
+    if (diag && t < MOM_T && f0 + t < F) {
+        double v = s1[f0 + t];
+        for (int s = 0; s < runs; s++) v += ws1[((int64_t)s * t1 + ti) * MOM_T + t];
+        s1[f0 + t] = v;
+    }
+    __syncthreads();
+    mom_store_tile(tile, s2, F, f0, g0, diag);
+}
+
+}  // namespace
+
+TDGP_API int64_t tdgp_moments_workspace_bytes(int64_t n, int F) {
+    if (!mom_shape_ok(n, F)) return -1;
+    const MomPlan p = mom_plan(n, F);
+    if (p.runs == 1) return 16;                                                 // one run adds in place: the workspace is not touched
+    return p.runs * (p.tiles * MOM_T * MOM_T + (int64_t)p.t1 * MOM_T) * 8;
+}
+
+TDGP_API int tdgp_moments_add(const float* rows, int64_t n, int F, double* s1, double* s2, void* workspace, int64_t workspace_bytes,
+                              tdgp_stream_t stream) {
+    TDGP_CHECK(mom_shape_ok(n, F), TDGP_EINVAL, "moments_add: n = %lld, F = %d outside 0 <= n < 2^31, 1 <= F <= %d", (long long)n, F, MOM_MAX_F);
+    if (n == 0) return TDGP_OK;                                                  // nothing to add, whatever the pointers
+    TDGP_CHECK(rows && s1 && s2 && workspace, TDGP_EINVAL, "moments_add: null pointer");
+    TDGP_CHECK(((uintptr_t)rows & 3) == 0 && (((uintptr_t)s1 | (uintptr_t)s2 | (uintptr_t)workspace) & 7) == 0, TDGP_EINVAL,
+               "moments_add: rows must be 4-byte aligned, s1 / s2 / workspace 8-byte aligned");
+    const int64_t need = tdgp_moments_workspace_bytes(n, F);
+    TDGP_CHECK(workspace_bytes >= need, TDGP_EINVAL, "moments_add: workspace of %lld bytes, %lld needed (workspace too small)", (long long)workspace_bytes,
+               (long long)need);
+    const MomPlan p = mom_plan(n, F);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)p.tiles, (unsigned)p.runs);
+    if (p.runs == 1) {
+        double* none = nullptr;
+        TDGP_LAUNCH("mom_tile_kernel_direct", mom_tile_kernel<true>, grid, dim3(MOM_THREADS), 0, st, rows, n, F, p.t1, p.run_rows, s1, s2, none, none);
+        TDGP_LAUNCH_CHECK();
+        return TDGP_OK;
+    }
+    double* ws2 = (double*)workspace;
+    double* ws1 = ws2 + p.runs * p.tiles * MOM_T * MOM_T;
+    TDGP_LAUNCH("mom_tile_kernel_runs", mom_tile_kernel<false>, grid, dim3(MOM_THREADS), 0, st, rows, n, F, p.t1, p.run_rows, s1, s2, ws2, ws1);
+    TDGP_LAUNCH_CHECK();
+    TDGP_LAUNCH("mom_merge_kernel", mom_merge_kernel, dim3((unsigned)p.tiles), dim3(MOM_THREADS), 0, st, (const double*)ws2, (const double*)ws1, (int)p.runs,
+                F, p.t1, s1, s2);
+    TDGP_LAUNCH_CHECK();
+    return TDGP_OK;
+}

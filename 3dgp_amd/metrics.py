@@ -1,10 +1,13 @@
-"""FID-side aggregation, the feature-space metrics (precision / recall, KID, IS) and camera priors of the generator harness
+"""FID (feature statistics, Frechet distance), the other feature-space metrics (precision / recall, KID, IS) and camera priors of the generator harness
 (host side).
 
 Reference: `src/metrics/metric_utils.py:104-169` (FeatureStats), `:288-320` (compute_feature_stats_for_generator),
 `src/metrics/frechet_inception_distance.py:20-39` (compute_fid), `src/training/rendering_utils.py:72-156` (camera priors).
 
-These are host-side pieces: fp64 mean / covariance accumulation in numpy, `scipy.linalg.sqrtm` for the Frechet distance, the
+`FeatureStats(device=None)` and `frechet_distance` are the host-side pieces: fp64 mean / covariance accumulation in numpy and
+`scipy.linalg.sqrtm`, bit for bit what the golden pins.  `FeatureStats(device=gpu)` keeps the same statistics on the device (fp64 raw moments
+on the fp64 matrix pipe, `tdgp_moments_add`, csrc/metrics.hip) and `frechet_distance_eigh` takes the distance from two symmetric eigenproblems
+there.  Also here: the
 camera prior samplers (torch RNG in the reference's draw order, scipy for the truncated normal).  The device work they drive is
 the generator forward (HIP) and ONE all-gather per feature block (`distributed.FeatureGatherer`, RCCL) instead of the
 reference's `world` sequential broadcasts.  Precision / recall (`src/metrics/precision_recall.py`) is the exception: its k-NN distance
@@ -121,6 +124,39 @@ class _RawMoments:
         return mu, self.s2 / count - np.outer(mu, mu)
 
 
+def _moments_add(rows, s1, s2):
+    """s1 += rows.sum(0), s2 += rows^T rows in fp64 for fp32 rows [n, F] on the GPU (tdgp_moments_add: fp64 matrix pipe, contract in
+    include/tdgp.h); no read-back, no synchronisation."""
+    from . import _lib
+    n, width = int(rows.shape[0]), int(rows.shape[1])
+    if n == 0:
+        return
+    need = int(_lib.load().tdgp_moments_workspace_bytes(n, width))
+    if need < 0:
+        raise RuntimeError(f'tdgp_moments_add refuses {n} rows of {width} features')
+    ws = torch.empty([need], dtype=torch.uint8, device=rows.device)
+    with torch.cuda.device(rows.device):
+        _lib.call('tdgp_moments_add', rows.data_ptr(), n, width, s1.data_ptr(), s2.data_ptr(), ws.data_ptr(), need, _lib.stream_of(rows))
+
+
+class _DeviceMoments:
+    """`_RawMoments` resident on a GPU: the totals are fp64 tensors there and a block is added by tdgp_moments_add."""
+    __slots__ = ('s1', 's2')
+
+    def __init__(self, width, device):
+        self.s1 = torch.zeros([width], dtype=torch.float64, device=device)
+        self.s2 = torch.zeros([width, width], dtype=torch.float64, device=device)
+
+    def add_block(self, rows32):
+        _moments_add(rows32, self.s1, self.s2)
+
+    def central(self, count):
+        """The three element-wise fp64 operations of `_RawMoments.central`, one torch op each (nothing fused): equal raw moments give equal bits."""
+        count = torch.full([], float(count), dtype=torch.float64, device=self.s1.device)      # a tensor: a Python divisor becomes a multiplication by 1 / count on the GPU
+        mu = self.s1 / count
+        return mu, self.s2 / count - torch.outer(mu, mu)
+
+
 class FeatureStats:
     """Feature accumulator of the FID loop; public surface of `metric_utils.py:104-169` (`append`, `append_torch`, `is_full`,
     `get_all`, `get_mean_cov`, `num_items`, `num_features`, `max_items`), written from its behaviour:
@@ -130,16 +166,24 @@ class FeatureStats:
     * `capture_all` keeps the accepted rows (in arrival order), `capture_mean_cov` keeps fp64 raw moments (`_RawMoments`);
     * multi-rank: one all-gather per block, rows interleaved rank-major (`distributed.FeatureGatherer`), so that every rank
       accumulates the same sequence and row i of the gathered block came from rank i % world (`metric_utils.py:145-155`).
+
+    `device=None` keeps everything on the host (numpy).  With a GPU device the object lives there: accepted blocks stay device tensors, the raw
+    moments are fp64 tensors fed by tdgp_moments_add, and `append_torch` neither copies to the host nor synchronises -- truncation is a slice and
+    the counts come from shapes.  The read-outs (`get_all`, `get_mean_cov`, `save`) copy back once; `get_all_torch` / `get_mean_cov_torch`
+    return the device tensors.
     """
 
-    def __init__(self, capture_all=False, capture_mean_cov=False, max_items=None):
+    def __init__(self, capture_all=False, capture_mean_cov=False, max_items=None, device=None):
         self.capture_all = bool(capture_all)
         self.capture_mean_cov = bool(capture_mean_cov)
         self.max_items = None if max_items is None else int(max_items)
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type != 'cuda':
+            raise ValueError(f'FeatureStats(device={device!r}): device statistics need a GPU (the moments kernel has no CPU path); device=None is the host object')
         self.num_items = 0
         self.num_features = None
-        self._kept = []                  # accepted fp32 blocks (capture_all)
-        self._moments = None             # _RawMoments (capture_mean_cov), made when F is known
+        self._kept = []                  # accepted fp32 blocks (capture_all): numpy arrays, or tensors on `device`
+        self._moments = None             # _RawMoments / _DeviceMoments, made when F is known
 
     # -- bookkeeping --------------------------------------------------------------------------------------------------
     def set_num_features(self, num_features):
@@ -147,7 +191,10 @@ class FeatureStats:
         num_features = int(num_features)
         if self.num_features is None:
             self.num_features = num_features
-            self._moments = _RawMoments(num_features)
+            if self.device is None:
+                self._moments = _RawMoments(num_features)
+            elif self.capture_mean_cov:
+                self._moments = _DeviceMoments(num_features, self.device)
         elif self.num_features != num_features:
             raise AssertionError(f'feature width changed: {self.num_features} -> {num_features}')
 
@@ -161,7 +208,34 @@ class FeatureStats:
     raw_cov = property(lambda self: None if self._moments is None else self._moments.s2)
 
     # -- accumulation -------------------------------------------------------------------------------------------------
+    def _append_device(self, rows):
+        """`append` for a tensor on `device`: the same cut, count and capture, as a slice and launches on the current stream."""
+        if rows.ndim != 2:
+            raise AssertionError(f'expected [n, F] feature rows, got shape {tuple(rows.shape)}')
+        room = self._room()
+        if room is not None and rows.shape[0] > room:
+            if room == 0:
+                return
+            rows = rows[:room]
+        source = rows
+        rows = rows.to(device=self.device, dtype=torch.float32).contiguous()
+        self.set_num_features(rows.shape[1])
+        self.num_items += int(rows.shape[0])
+        if self.capture_all:
+            self._kept.append(rows.clone() if rows.data_ptr() == source.data_ptr() else rows)      # the object owns what it keeps, as the host path's copy does
+        if self.capture_mean_cov:
+            self._moments.add_block(rows)
+
+    def add_rows(self, x):
+        """Accumulate an [N, F] tensor in one call of the moments kernel (real-side statistics from saved features); device statistics only."""
+        if self.device is None:
+            raise AssertionError('add_rows needs device statistics: FeatureStats(..., device=...)')
+        assert isinstance(x, torch.Tensor) and x.ndim == 2
+        self._append_device(x)
+
     def append(self, x):
+        if self.device is not None:
+            return self._append_device(torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float32))))
         rows = np.asarray(x, dtype=np.float32)
         if rows.ndim != 2:
             raise AssertionError(f'expected [n, F] feature rows, got shape {rows.shape}')
@@ -187,6 +261,8 @@ class FeatureStats:
                 from .distributed import FeatureGatherer
                 gatherer = FeatureGatherer(side_stream=False)
             x = gatherer.gather(x)
+        if self.device is not None:
+            return self._append_device(x)                 # no host copy, no synchronisation: the fault word is read at the read-outs
         rows = x.cpu().numpy()                            # a synchronisation point: the features are on the host
         if x.is_cuda:
             from . import _lib
@@ -194,34 +270,69 @@ class FeatureStats:
         self.append(rows)
 
     # -- results ------------------------------------------------------------------------------------------------------
+    def _read_back(self, *tensors):
+        """Device tensors -> numpy, then the fault word: the copy is the synchronisation point `append_torch` no longer is."""
+        out = [t.cpu().numpy() for t in tensors]
+        from . import _lib
+        _lib.raise_on_device_fault('the generator forwards behind these feature statistics')
+        return out
+
+    def get_all_torch(self):
+        """metric_utils.py:163-164: the kept rows as one tensor -- on `device` for device statistics, without a copy through the host."""
+        if not self.capture_all:
+            raise AssertionError('constructed without capture_all')
+        if self.device is None:
+            return torch.from_numpy(self.get_all())
+        return torch.cat(self._kept, dim=0)
+
     def get_all(self):
         if not self.capture_all:
             raise AssertionError('constructed without capture_all')
+        if self.device is not None:
+            return self._read_back(self.get_all_torch())[0]
         return np.concatenate(self._kept, axis=0)
+
+    def get_mean_cov_torch(self):
+        """(mean, covariance) as fp64 tensors: on `device` for device statistics, nothing read back."""
+        if not self.capture_mean_cov:
+            raise AssertionError('constructed without capture_mean_cov')
+        if self.device is None:
+            return tuple(torch.from_numpy(a) for a in self.get_mean_cov())
+        return self._moments.central(self.num_items)
 
     def get_mean_cov(self):
         if not self.capture_mean_cov:
             raise AssertionError('constructed without capture_mean_cov')
+        if self.device is not None:
+            return tuple(self._read_back(*self._moments.central(self.num_items)))
         return self._moments.central(self.num_items)
 
     # -- persistence: a neutral container (npz) instead of the reference's pickle of __dict__ ---------------------------
     def save(self, path):
         width = self.num_features or 0
+        s1, s2 = (self._moments.s1, self._moments.s2) if self._moments else (np.zeros(width), np.zeros((width, width)))
+        if isinstance(s1, torch.Tensor):
+            s1, s2 = self._read_back(s1, s2)
         np.savez(path, capture_all=self.capture_all, capture_mean_cov=self.capture_mean_cov, max_items=-1 if self.max_items is None else self.max_items,
-                 num_items=self.num_items, raw_mean=self._moments.s1 if self._moments else np.zeros(width), raw_cov=self._moments.s2 if self._moments else np.zeros((width, width)),
+                 num_items=self.num_items, raw_mean=s1, raw_cov=s2,
                  all_features=self.get_all() if self.capture_all and self._kept else np.zeros([0, width], np.float32))
 
     @staticmethod
-    def load(path):
+    def load(path, device=None):
+        """`device`: place the loaded totals (and rows) on that GPU; None = the host object."""
         d = np.load(path)
         cap = int(d['max_items'])
-        st = FeatureStats(capture_all=bool(d['capture_all']), capture_mean_cov=bool(d['capture_mean_cov']), max_items=None if cap < 0 else cap)
+        st = FeatureStats(capture_all=bool(d['capture_all']), capture_mean_cov=bool(d['capture_mean_cov']), max_items=None if cap < 0 else cap, device=device)
         st.set_num_features(d['raw_mean'].shape[0])
         st.num_items = int(d['num_items'])
-        st._moments.s1[...] = d['raw_mean']
-        st._moments.s2[...] = d['raw_cov']
+        if st.device is None:
+            st._moments.s1[...] = d['raw_mean']
+            st._moments.s2[...] = d['raw_cov']
+        elif st._moments is not None:
+            st._moments.s1.copy_(torch.from_numpy(d['raw_mean']))
+            st._moments.s2.copy_(torch.from_numpy(d['raw_cov']))
         if st.capture_all and d['all_features'].size:
-            st._kept = [d['all_features']]
+            st._kept = [d['all_features'] if st.device is None else torch.from_numpy(d['all_features']).to(st.device)]
         return st
 
 
@@ -231,6 +342,47 @@ def frechet_distance(mu_gen, sigma_gen, mu_real, sigma_real):
     m = np.square(mu_gen - mu_real).sum()
     s, _ = scipy.linalg.sqrtm(np.dot(sigma_gen, sigma_real), disp=False)
     return float(np.real(m + np.trace(sigma_gen + sigma_real - s * 2)))
+
+
+def frechet_distance_eigh(mu_gen, sigma_gen, mu_real, sigma_real):
+    """The Frechet distance from two symmetric eigenproblems instead of `scipy.linalg.sqrtm` of the non-symmetric product:
+    |mu_g - mu_r|^2 + tr S_g + tr S_r - 2 sum_i sqrt(max(lambda_i, 0)), lambda = eigenvalues of S_g^(1/2) S_r S_g^(1/2) (those of S_g S_r).
+    S_g^(1/2) comes from one `eigh` with negative eigenvalues clamped to zero; the product is symmetrised before `eigvalsh`.  fp64 tensors or
+    arrays; runs on the device of `sigma_gen`.  `frechet_distance` stays the reference's expression and the yardstick."""
+    def t(a, device=None):
+        a = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a, dtype=np.float64))
+        return a.to(device=a.device if device is None else device, dtype=torch.float64)
+    sg = t(sigma_gen)
+    mg, mr, sr = t(mu_gen, sg.device), t(mu_real, sg.device), t(sigma_real, sg.device)
+    lam, vec = torch.linalg.eigh(sg)
+    root = (vec * lam.clamp_min(0).sqrt()) @ vec.T
+    m = root @ sr @ root
+    lam2 = torch.linalg.eigvalsh((m + m.T) * 0.5)
+    value = (mg - mr).square().sum() + sg.trace() + sr.trace() - 2 * lam2.clamp_min(0).sqrt().sum()
+    return float(value)
+
+
+def _mean_cov_of(stats):
+    """(mu, sigma) of a compute_fid argument: a FeatureStats with capture_mean_cov, the path of a saved one, or the pair itself."""
+    if isinstance(stats, (str, bytes)) or hasattr(stats, '__fspath__'):
+        stats = FeatureStats.load(stats)
+    if isinstance(stats, FeatureStats):
+        return stats.get_mean_cov_torch() if stats.device is not None else stats.get_mean_cov()
+    mu, sigma = stats
+    return mu, sigma
+
+
+def compute_fid(real, gen):
+    """frechet_inception_distance.py:20-39 on gathered statistics: `real` / `gen` are FeatureStats with capture_mean_cov, saved paths or
+    (mu, sigma) pairs.  Statistics on the host take the reference's expression (`frechet_distance`); when either side is resident on a GPU both
+    go there and the distance is `frechet_distance_eigh` on that device, one float read back."""
+    (mu_r, sigma_r), (mu_g, sigma_g) = _mean_cov_of(real), _mean_cov_of(gen)
+    devices = [a.device for a in (sigma_g, sigma_r) if isinstance(a, torch.Tensor) and a.is_cuda]
+    if not devices:
+        as_np = lambda a: a.numpy() if isinstance(a, torch.Tensor) else np.asarray(a)         # noqa: E731
+        return frechet_distance(as_np(mu_g), as_np(sigma_g), as_np(mu_r), as_np(sigma_r))
+    on = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a, dtype=np.float64))).to(devices[0])      # noqa: E731
+    return frechet_distance_eigh(on(mu_g), on(sigma_g), on(mu_r), on(sigma_r))
 
 
 def iterate_random_conditioning(G, batch_size, device='cpu', camera_cfg=None, dataset=None, frontal_camera=False):
@@ -291,16 +443,18 @@ def resolve_batch_gen(batch_size, batch_gen=None):
 
 
 def compute_feature_stats_for_generator(G, detector, max_items, batch_size=64, batch_gen=None, camera_cfg=None, c_sampler=None, num_gpus=1, rank=0,
-                                        device='cuda', gatherer=None, G_kwargs=None, dataset=None, **stats_kwargs):
+                                        device='cuda', gatherer=None, G_kwargs=None, dataset=None, stats_device=None, **stats_kwargs):
     """metric_utils.py:288-320: generate `batch_size` images per iteration in chunks of `batch_gen`, run the detector, gather the
     feature block across ranks, accumulate.  Conditioning comes from `iterate_random_conditioning` (labels / custom angles from
     `dataset`) or, when given, from `c_sampler(batch) -> c [batch, c_dim]`; cameras come from the prior (`camera_cfg`, default
     camera/base.yaml) and pass through G's camera adaptor when it has one.
     `batch_gen` is the caller's option it is in the reference (MetricOptions.batch_gen, metric_utils.py:26,36): None = the reference's default
-    min(batch_size, 4) (:289); 16 generates the same images 8-9 % faster on one MI355X (bench.py --fid-loop prints both)."""
+    min(batch_size, 4) (:289); 16 generates the same images 8-9 % faster on one MI355X (bench.py --fid-loop prints both).
+    `device` is where the draws are made; `stats_device` is FeatureStats' own `device` (None: host statistics, one copy and one
+    synchronisation per block; a GPU: the blocks and the moments stay there and the loop never waits for the device)."""
     batch_gen = resolve_batch_gen(batch_size, batch_gen)
     G_kwargs = {} if G_kwargs is None else G_kwargs
-    stats = FeatureStats(max_items=max_items, **stats_kwargs)
+    stats = FeatureStats(max_items=max_items, device=stats_device, **stats_kwargs)
     batches = _generator_batches(G, batch_gen, camera_cfg, c_sampler, dataset, device)
     while not stats.is_full():
         images = []
@@ -512,10 +666,36 @@ def _real_rows(real):
     return real if isinstance(real, torch.Tensor) else torch.from_numpy(np.asarray(real, dtype=np.float32))
 
 
+def _on_generator_device(G, kw):
+    """The draws are made where the generator lives, and when that is a GPU the statistics stay there too."""
+    kw.setdefault('device', _device_of(G))
+    if torch.device(kw['device']).type == 'cuda':
+        kw.setdefault('stats_device', kw['device'])
+
+
+def _checked(G, value):
+    """`value` was read back from the device (a synchronisation point): the fault word covers every forward behind it."""
+    if _device_of(G).type == 'cuda':
+        from . import _lib
+        _lib.raise_on_device_fault('the generator forwards behind these feature rows')
+    return value
+
+
 def _generated_rows(G, detector, num_gen, kw):
-    kw.setdefault('device', _device_of(G))           # the draws are made where the generator lives
+    _on_generator_device(G, kw)
     stats = compute_feature_stats_for_generator(G, detector, max_items=num_gen, capture_all=True, **kw)
-    return torch.from_numpy(stats.get_all())
+    return stats.get_all_torch()
+
+
+def fid_for_generator(G, detector, real, num_gen=50000, **kw):
+    """'fid50k[_full]' (metric_main.py) for a generator: mean and covariance of the features of `num_gen` generated images
+    (`compute_feature_stats_for_generator`, whose keywords `kw` are) against the real-side statistics `real` (a FeatureStats with
+    capture_mean_cov, a saved one, or a (mu, sigma) pair) -> the Frechet distance; NaN on ranks other than 0 as in the reference."""
+    _on_generator_device(G, kw)
+    gen = compute_feature_stats_for_generator(G, detector, max_items=num_gen, capture_mean_cov=True, **kw)
+    if kw.get('rank', 0) != 0:
+        return float('nan')
+    return _checked(G, compute_fid(real, gen))
 
 
 def pr_for_generator(G, detector, real, num_gen=50000, nhood_size=3, **kw):
@@ -524,7 +704,7 @@ def pr_for_generator(G, detector, real, num_gen=50000, nhood_size=3, **kw):
     a saved FeatureStats."""
     gen = _generated_rows(G, detector, num_gen, kw)
     device = _device_of(G)
-    return compute_pr(_real_rows(real).to(device), gen.to(device), nhood_size=nhood_size, num_gpus=kw.get('num_gpus', 1), rank=kw.get('rank', 0))
+    return _checked(G, compute_pr(_real_rows(real).to(device), gen.to(device), nhood_size=nhood_size, num_gpus=kw.get('num_gpus', 1), rank=kw.get('rank', 0)))
 
 
 def kid_for_generator(G, detector, real, num_gen=50000, num_subsets=100, max_subset_size=1000, **kw):
@@ -533,7 +713,7 @@ def kid_for_generator(G, detector, real, num_gen=50000, num_subsets=100, max_sub
     if kw.get('rank', 0) != 0:
         return float('nan')
     device = _device_of(G)
-    return compute_kid(_real_rows(real).to(device), gen.to(device), num_subsets=num_subsets, max_subset_size=max_subset_size)
+    return _checked(G, compute_kid(_real_rows(real).to(device), gen.to(device), num_subsets=num_subsets, max_subset_size=max_subset_size))
 
 
 def is_for_generator(G, detector, num_gen=50000, num_splits=10, **kw):
@@ -541,7 +721,7 @@ def is_for_generator(G, detector, num_gen=50000, num_splits=10, **kw):
     probs = _generated_rows(G, detector, num_gen, kw)
     if kw.get('rank', 0) != 0:
         return float('nan'), float('nan')
-    return compute_is(probs.to(_device_of(G)), num_splits=num_splits)
+    return _checked(G, compute_is(probs.to(_device_of(G)), num_splits=num_splits))
 
 
 # ----------------------------------------------------------------------------------------------------------------------

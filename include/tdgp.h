@@ -473,6 +473,23 @@ int64_t tdgp_pr_member_workspace_bytes(int64_t np, int64_t nc);
 int     tdgp_pr_member(const uint16_t* probes, const float* probe_norms, int64_t np, const uint16_t* cols, const float* col_norms,
                        const uint16_t* kth, int64_t nc, int Fpad, uint8_t* member, void* workspace, int64_t workspace_bytes, tdgp_stream_t stream);
 
+/* FID feature moments (src/metrics/metric_utils.py:128-161: `x.sum(0)` and `x.T @ x` in fp64 per feature block, on host arrays): the running
+ * raw moments of fp32 rows on the device.  rows [n,F] fp32 contiguous; s1 [F] and s2 [F,F] fp64, caller-owned running totals.
+ * On return s1[f] += sum_i rows[i,f] and s2[f,g] += sum_i rows[i,f] * rows[i,g].
+ * Arithmetic: every row value is widened fp32 -> fp64 (exact), every product is formed in fp64 (exact: 24 + 24 significand bits fit in 53),
+ *   only the additions round; nothing is accumulated in fp32.  The Gram part runs on v_mfma_f64_16x16x4_f64.
+ * s2 is symmetric bit for bit on return: 64 x 64 tiles on and above the diagonal are computed, each is written to both sides, and of a
+ *   diagonal tile only the elements on or above the diagonal are used (whatever s2 held below the diagonal is overwritten by the mirror).
+ * Rows and columns past n or F enter as zeros.  A NaN / Inf row value propagates as in IEEE arithmetic (0 * Inf = NaN).
+ * Partition, a function of (n, F) alone: tiles x runs of rows, a run at least 512 rows long and tiles x runs <= 2048 blocks where that leaves
+ *   more than one run.  One run adds in place; several runs leave one partial per (run, tile) in the workspace, and a merge kernel adds them to
+ *   s2 in run order: no atomics, one writer per value, the same bytes on every run.
+ * 0 <= n < 2^31 (n = 0: nothing is done), 1 <= F <= 16384, no alignment requirement on F; s1 / s2 / workspace 8-byte aligned.
+ * workspace: tdgp_moments_workspace_bytes(n, F) bytes (-1 for a shape it refuses), caller-owned.  A refused shape or a workspace that is too
+ * small returns TDGP_EINVAL before anything is launched. */
+int64_t tdgp_moments_workspace_bytes(int64_t n, int F);
+int     tdgp_moments_add(const float* rows, int64_t n, int F, double* s1, double* s2, void* workspace, int64_t workspace_bytes, tdgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
