@@ -10,7 +10,7 @@ The directory name starts with a digit, so import it with ``importlib.import_mod
   generator            Generator / SynthesisNetwork / MappingNetwork with the reference's state-dict names
   adaptors             DepthAdaptor / CameraAdaptor / Conv2dLayer
   metrics              FeatureStats, Frechet distance, camera priors, generator feature loop (host side)
-  inference            generate / generate_trajectory / camera trajectories
+  inference            generate / generate_trajectory / camera trajectories; shared tri-planes, uint8 video grids on the device
   compat               `src.*` module aliases so reference-style call sites resolve to this package
   distributed          batch-sharded multi-GPU generation (one process per GPU, RCCL all-gather of features)
   graphs               the whole generator forward as one captured HIP graph per (batch, options)

@@ -643,6 +643,124 @@ class SynthesisNetwork(torch.nn.Module):
         planes = self.tri_plane_decoder(ws[:, :self.tri_plane_decoder.num_ws], hwc=True, **block_kwargs)
         return _renderer.simple_tri_plane_renderer(planes, coords, self.tri_plane_mlp, scale=self.cfg.cube_scale)['sigma']
 
+    # -- planes and views as separate steps: the planes depend on `ws` alone, so a trajectory renders V views of a sample from ONE backbone run
+    @torch.no_grad()
+    def tri_planes(self, ws, **block_kwargs):
+        """ws [B,num_ws,w_dim] -> renderer.HWCPlanes [B,3,R,R,feat]: the planes exactly as `forward` obtains them for this batch (the same
+        `forward_chunks(..., hwc=True, chunk=None)` route, hence the same bits as `forward` at the same batch size).  Eval mode only."""
+        if self.training:
+            raise RuntimeError('tri_planes / render_views are the inference route: call .eval() first (training mode renders patches with density noise)')
+        planes = None
+        for _, p in self.tri_plane_decoder.forward_chunks(ws[:, :self.tri_plane_decoder.num_ws], hwc=True, chunk=None, **block_kwargs):
+            planes = p
+        return planes
+
+    def _views_per_call(self, B, R, S, N, max_rays, device):
+        """How many views of B samples one renderer call takes: at most `max_rays` rays, and a tdgp_render_fused workspace (it grows with
+        rays x samples) of at most half the memory that is free on the device or cached by the allocator."""
+        views = max(1, max_rays // (B * R))
+        if device.type == 'cuda':
+            free = torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+            ws_bytes = _lib.load().tdgp_render_fused_workspace_bytes
+            while views > 1 and int(ws_bytes(B, views * R, S, N)) > free // 2:
+                views = (views + 1) // 2
+        return views
+
+    @torch.no_grad()
+    def render_views(self, planes, camera_params, ws=None, render_opts={}, u_coarse=None, u_fine=None, max_rays_per_call=None, patch_params=None,
+                     ray_major=False):
+        """V views of each of B samples from that sample's planes (`tri_planes`), without running the backbone again.
+
+        planes: HWCPlanes [B,...]; camera_params: B * V cameras, sample-major (item n * V + v = view v of sample n, the order
+        `inference.generate_camera_trajectory` produces).  The V * R rays of a sample are handed to the renderer as one image of V * h rows of
+        w rays over that sample's planes (`ray_grid_w = w`); views are taken in chunks so that one renderer call holds at most
+        `max_rays_per_call` rays (default: 16 images' worth, further limited by the workspace the fused renderer asks for).  Rays are
+        independent, so the chunking does not change a bit.  u_coarse [B*V,R,S] / u_fine [B*V*R,N]: explicit draws, as in `forward`.
+        -> img [B*V,C,h,w], or TensorGroup(img, depth, depth_adapted) with render_opts['return_depth' / 'return_depth_adapted'], as `forward`
+        returns them; the depth adaptor (same conditions as in `forward`) needs `ws` and takes `ws[:, 0].repeat_interleave(V)`.
+        ray_major=True: TensorGroup(rgb [B*V,R,C], depth [B*V,R,1]) as the renderer leaves them -- what `tdgp_frames_to_grid_u8` reads; no
+        CHW image is made and no adaptor is applied."""
+        render_opts = {**self._default_render_options, **render_opts}
+        if self.training:
+            raise RuntimeError('render_views is the inference route: call .eval() first (training mode renders patches with density noise)')
+        if patch_params is not None:
+            raise NotImplementedError('render_views renders whole frames: patch_params are not supported')
+        if float(render_opts['cut_quantile']) > 0.0:
+            raise NotImplementedError('render_views refuses cut_quantile > 0: the quantile is taken over one renderer call and would change with the '
+                                      'chunking of the views')
+        if (render_opts['return_depth_adapted'] or render_opts['concat_depth']) and self.depth_adaptor is None:
+            raise RuntimeError('return_depth_adapted / concat_depth need cfg.depth_adaptor')
+        if not isinstance(planes, _renderer.HWCPlanes):
+            raise TypeError('render_views takes the HWCPlanes that tri_planes returns')
+        cam = camera_params
+        get = (lambda k: cam[k]) if isinstance(cam, dict) else (lambda k: getattr(cam, k))
+        B, BV = int(planes.t.shape[0]), int(get('angles').shape[0])
+        if B < 1 or BV < B or BV % B != 0:
+            raise ValueError(f'{BV} cameras are not a multiple of the plane batch {B} (sample-major: camera n * V + v is view v of sample n)')
+        V = BV // B
+        adapt = (not ray_major and self.depth_adaptor is not None
+                 and bool(render_opts['concat_depth'] or render_opts['return_depth_adapted'] or self.strict_nan_propagation))
+        if adapt and (ws is None or ws.shape[0] != B):
+            raise ValueError(f'the depth adaptor is conditioned on ws[:, 0]: pass the ws [{B}, ...] the planes were made from')
+        if max_rays_per_call is not None and int(max_rays_per_call) < 1:
+            raise ValueError(f'max_rays_per_call must be positive, got {max_rays_per_call!r}')
+        h = w = self.test_resolution
+        R = h * w
+        dev = planes.t.device
+        _lib.require_cuda(planes.t, 'planes')
+        c2w = _renderer.compute_cam2world_matrix(cam)
+        ray_o, ray_d = _renderer.sample_rays(c2w, fov=get('fov'), resolution=(h, w), device=dev)
+        ray_o, ray_d = ray_o.reshape(B, V * R, 3), ray_d.reshape(B, V * R, 3)
+        opts = self.rendering_options(render_opts)
+        opts['ray_grid_w'] = w                      # V frames of h rows each: one image of V * h rows of w rays per sample
+        opts['n_coarse'] = opts['n_fine'] = None
+        S, N = int(opts['num_proposal_steps']), int(opts['num_fine_steps'])
+        uc = None if u_coarse is None else u_coarse.reshape(B, V, R, -1)
+        uf = None if u_fine is None else u_fine.reshape(B, V, R, -1)
+        max_rays = 16 * R if max_rays_per_call is None else int(max_rays_per_call)
+        bstep = B if B * R <= max_rays else max(1, max_rays // R)          # a plane batch too large for one view per call is split by samples
+        vstep = self._views_per_call(bstep, R, S, N, max_rays, dev)
+        C = self.img_channels
+        rgb = depth = None
+        for b0 in range(0, B, bstep):
+            bs = slice(b0, min(b0 + bstep, B))
+            nb = bs.stop - bs.start
+            for v0 in range(0, V, vstep):
+                vs = slice(v0, min(v0 + vstep, V))
+                nv = vs.stop - vs.start
+                whole = nb == B and nv == V
+                o = dict(opts, u_coarse=None if uc is None else uc[bs, vs].reshape(nb, nv * R, -1),
+                         u_fine=None if uf is None else uf[bs, vs].reshape(nb * nv * R, -1))
+                p_c = planes if nb == B else _renderer.HWCPlanes(planes.t[bs])
+                ro, rd = (ray_o, ray_d) if whole else (t.reshape(B, V, R, 3)[bs, vs].reshape(nb, nv * R, 3) for t in (ray_o, ray_d))
+                rgb_c, depth_c = self._render_within_field_bound(p_c, ro, rd, o, w)
+                if whole:
+                    rgb, depth = rgb_c.reshape(BV, R, C), depth_c.reshape(BV, R, 1)
+                    break
+                if rgb is None:
+                    rgb = torch.empty([B, V, R, C], dtype=torch.float32, device=dev)
+                    depth = torch.empty([B, V, R, 1], dtype=torch.float32, device=dev)
+                rgb[bs, vs], depth[bs, vs] = rgb_c.reshape(nb, nv, R, C), depth_c.reshape(nb, nv, R, 1)
+        rgb, depth = rgb.reshape(BV, R, C), depth.reshape(BV, R, 1)
+        if ray_major:
+            return TensorGroup(rgb=rgb, depth=depth)
+        img = torch.empty([BV, C, h, w], dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.call('tdgp_rays_to_image', rgb.data_ptr(), img.data_ptr(), BV, h * w, _lib.stream_of(rgb))
+        depth = depth.reshape(BV, 1, h, w)
+        depth_adapted = None
+        if adapt:                                                           # networks_epigraf.py:246-253, elided as in `forward` when not needed
+            depth_adapted = self.depth_adaptor(depth, ws[:, 0].repeat_interleave(V, dim=0))
+            img = torch.cat([img, depth_adapted], dim=1) if render_opts['concat_depth'] else img + 0.0 * depth_adapted.max()
+        if render_opts['return_depth'] or render_opts['return_depth_adapted']:
+            out = TensorGroup(img=img)
+            if render_opts['return_depth']:
+                out.depth = depth
+            if render_opts['return_depth_adapted']:
+                out.depth_adapted = depth_adapted
+            return out
+        return img
+
     def forward_autograd(self, ws, camera_params, patch_params=None, render_opts={}, u_coarse=None, u_fine=None, n_coarse=None, n_fine=None,
                          **block_kwargs):
         """The same forward as a differentiable graph: gradients reach every parameter of the tri-plane

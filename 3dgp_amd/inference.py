@@ -4,6 +4,10 @@ Reference: `src/training/inference_utils.py:88-215` -- `generate`, `generate_tra
 `approximate_mean_camera_params`, `sample_posterior_camera_params`; `scripts/inference.py:87-150` -- `sample_z_from_seeds`,
 `sample_c_from_seeds`, `c_idx_to_c`, `sample_ws_from_seeds`.  Host-side orchestration only: every frame is one
 `G.synthesis` call on the HIP path; trajectories are a few hundred floats of tensor arithmetic kept on the CPU like the reference.
+
+Trajectories of one sample share its tri-planes (`generate_trajectory(share_planes=True)`, `generate_videos`, `render_video_grid`,
+`render_image_strips`: `SynthesisNetwork.tri_planes` once per sample, `render_views` for its cameras), and frames become uint8 grids on the
+device (`frames_to_grid`, csrc/frames_grid.hip) -- DESIGN.md 5.11.
 """
 import numpy as np
 import torch
@@ -61,13 +65,51 @@ def generate(G, ws, camera_params, batch_size=8, **synthesis_kwargs):
     return TensorGroup.cat(frames, dim=0) if isinstance(frames[0], TensorGroup) else torch.cat(frames, dim=0)
 
 
-def generate_trajectory(G, ws, camera_params, **generate_kwargs):
-    """inference_utils.py:88-103: every `ws` under every camera of its trajectory -> [num_cameras, num_samples, c, h, w]."""
+def _plane_batches(G, ws, camera_params, plane_batch, u_coarse=None, u_fine=None, render_opts={}, max_rays_per_call=None, ray_major=False,
+                   batch_size=None, **block_kwargs):
+    """The shared-planes route: `tri_planes` on `plane_batch` samples at a time (block kwargs and noise_mode='const' go there), `render_views` on
+    their cameras.  Yields what render_views returns, per plane batch, sample-major.  `batch_size` (the per-frame route's chunk) has no role here."""
+    num_samples = len(ws)
+    if num_samples < 1 or len(camera_params) % num_samples != 0 or len(camera_params) < num_samples:
+        raise ValueError(f'{len(camera_params)} cameras are not a multiple of the {num_samples} samples')
+    if int(plane_batch) < 1:
+        raise ValueError(f'plane_batch must be positive, got {plane_batch!r}')
+    V = len(camera_params) // num_samples
+    camera_params = camera_params.to(dtype=torch.float32, device=ws.device)
+    syn = G.synthesis
+    R = syn.test_resolution ** 2
+    for n0 in range(0, num_samples, int(plane_batch)):
+        n1 = min(n0 + int(plane_batch), num_samples)
+        planes = syn.tri_planes(ws[n0:n1], noise_mode='const', **block_kwargs)
+        yield syn.render_views(planes, camera_params[n0 * V:n1 * V], ws=ws[n0:n1], render_opts=render_opts,
+                               u_coarse=None if u_coarse is None else u_coarse.reshape(num_samples * V, R, -1)[n0 * V:n1 * V],
+                               u_fine=None if u_fine is None else u_fine.reshape(num_samples * V * R, -1)[n0 * V * R:n1 * V * R],
+                               max_rays_per_call=max_rays_per_call, ray_major=ray_major)
+
+
+def generate_trajectory(G, ws, camera_params, share_planes=False, plane_batch=4, **generate_kwargs):
+    """inference_utils.py:88-103: every `ws` under every camera of its trajectory -> [num_cameras, num_samples, c, h, w].
+
+    share_planes=False is the reference's structure: `ws` repeated per camera, the whole `G.synthesis` (tri-plane backbone included) once per
+    frame.  share_planes=True runs the backbone once per SAMPLE (`SynthesisNetwork.tri_planes`, `plane_batch` samples at a time) and renders all
+    cameras of those samples from their planes (`render_views`); same layout, same [0, 1] mapping, one host copy per plane batch."""
     num_cameras = len(camera_params) // len(ws)
     num_samples = len(camera_params) // num_cameras
-    camera_params = camera_params.to(dtype=torch.float32, device=ws.device)
-    ws = ws.repeat_interleave(num_cameras, dim=0)
-    images = generate(G, ws=ws, camera_params=camera_params, **generate_kwargs)
+    if share_planes:
+        frames = []
+        for frame in _plane_batches(G, ws, camera_params, plane_batch, **generate_kwargs):
+            if isinstance(frame, TensorGroup) and 'depth' in frame:
+                depth_range = G.cfg.ray_end - G.cfg.ray_start
+                depth_mid = (G.cfg.ray_start + G.cfg.ray_end) * 0.5
+                frame.depth = (frame.depth - depth_mid) / depth_range * 2.0
+            frames.append(frame.clamp(-1, 1).cpu() * 0.5 + 0.5)         # a synchronisation point
+            if ws.is_cuda:
+                _lib.raise_on_device_fault('generate_trajectory()')
+        images = TensorGroup.cat(frames, dim=0) if isinstance(frames[0], TensorGroup) else torch.cat(frames, dim=0)
+    else:
+        camera_params = camera_params.to(dtype=torch.float32, device=ws.device)
+        ws = ws.repeat_interleave(num_cameras, dim=0)
+        images = generate(G, ws=ws, camera_params=camera_params, **generate_kwargs)
     if isinstance(images, TensorGroup):
         images = images.reshape_each(lambda x: [num_samples, num_cameras, *x.shape[1:]])
     else:
@@ -122,6 +164,185 @@ def approximate_mean_camera_params(G, num_samples=1024, device='cpu', camera_cfg
     z = torch.randn(num_samples, G.z_dim, device=device)
     c = c_sampler(num_samples).to(device) if c_sampler is not None else torch.zeros(num_samples, G.c_dim, device=device)
     return sample_posterior_camera_params(G, z, c, camera_cfg).mean(dim=0, keepdim=True)
+
+
+def get_mean_camera_params(G, device='cpu', camera_cfg=None):
+    """inference_utils.py:182-191.  The 'custom' branch (dataset-provided angles) is taken where the mapping network carries
+    `mean_camera_params` (yaw, pitch, roll, fov, radius); otherwise the Monte-Carlo mean of 1024 posterior samples.  [1, ...]."""
+    m = getattr(G.mapping, 'mean_camera_params', None)
+    if m is not None and m.numel() >= 5:
+        m = m.to(device)
+        return TensorGroup(angles=m[[0, 1, 2]].unsqueeze(0), fov=m[[3]], radius=m[[4]], look_at=torch.zeros(1, 3, device=device)).float()
+    return approximate_mean_camera_params(G, num_samples=1024, device=device, camera_cfg=camera_cfg)
+
+
+def generate_camera_params(G, z, c, trajectory, camera_cfg=None):
+    """inference_utils.py:127-133: the canonical camera of every sample (the mean camera repeated with `use_mean_camera`, a posterior sample
+    otherwise), then its trajectory -> [num_samples * num_frames, ...], sample-major."""
+    if _tg(trajectory, 'use_mean_camera', False):
+        canonical = get_mean_camera_params(G, device=z.device, camera_cfg=camera_cfg).repeat_interleave(len(z), dim=0)
+    else:
+        canonical = sample_posterior_camera_params(G, z, c, camera_cfg)
+    return generate_camera_trajectory(trajectory, canonical_camera_params=canonical)
+
+
+SNAPSHOT_TRAJECTORY = dict(name='front_circle', num_frames=32, fov_diff=1.0, yaw_diff=0.5, pitch_diff=0.3, use_mean_camera=True)
+
+
+def generate_videos(G, z, c, gen_depths=False, plane_batch=4):
+    """inference_utils.py:63-77, the training snapshots' videos: 9 (resolution >= 1024) or 16 samples under 32 `front_circle` frames around the
+    mean camera -> TensorGroup(img [num_videos, 32, c, h, w], ...) in [0, 1] on the host.  Built on the shared-planes route (the reference's
+    vis_cfg.batch_size = 4 is the plane batch here)."""
+    num_videos = 9 if G.img_resolution >= 1024 else 16
+    z, c = z[:num_videos], c[:num_videos]
+    camera_params = generate_camera_params(G, z, c, SNAPSHOT_TRAJECTORY)
+    ws = G.mapping(z, c)
+    render_opts = dict(return_depth=gen_depths, return_depth_adapted=gen_depths)
+    images = generate_trajectory(G, ws, camera_params, share_planes=True, plane_batch=plane_batch, render_opts=render_opts).permute(1, 0, 2, 3, 4)
+    return images if isinstance(images, TensorGroup) else TensorGroup(img=images)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# frames -> uint8 grids on the device (csrc/frames_grid.hip), video / image files
+# ----------------------------------------------------------------------------------------------------------------------
+def grid_shape(h, w, tiles, nrow, padding=2):
+    """(GH, GW) of torchvision's make_grid(nrow, padding) over `tiles` images of h x w: xmaps = min(nrow, tiles), ymaps = ceil(tiles / xmaps),
+    GH = (h + padding) * ymaps + padding, GW = (w + padding) * xmaps + padding; a single tile is returned as it is, unpadded."""
+    for name, v, lo in (('h', h, 1), ('w', w, 1), ('tiles', tiles, 1), ('nrow', nrow, 1), ('padding', padding, 0)):
+        if int(v) != v or v < lo:
+            raise ValueError(f'{name} must be an integer >= {lo}, got {v!r}')
+    if tiles == 1:
+        return int(h), int(w)
+    xmaps = min(int(nrow), int(tiles))
+    ymaps = -(-int(tiles) // xmaps)
+    return (int(h) + int(padding)) * ymaps + int(padding), (int(w) + int(padding)) * xmaps + int(padding)
+
+
+def frames_to_grid(frames, h, w, tiles, images, stride_image, stride_tile, nrow, padding=2, normalise=None):
+    """Ray-major fp32 frames [num_frames, h*w, C] (C in {1, 3}: the renderer's `rgb` / `depth` buffers, `render_views(ray_major=True)`) ->
+    uint8 [images, GH, GW, 3] on the device, the [T,H,W,C] block a video or image encoder takes (tdgp_frames_to_grid_u8: one streaming kernel,
+    no rays_to_image, no fp32 image, no host copy in between).  Tile k of image i shows frame i * stride_image + k * stride_tile: a video grid
+    over V-frame trajectories is (images = V, tiles = samples, stride_image = 1, stride_tile = V), a strip of one sample's views
+    (images = samples, tiles = V, stride_image = V, stride_tile = 1).  Layout: `grid_shape` (make_grid with pad_value 0; C = 1 is replicated).
+
+    Values follow `generate` + `(x * 255).to(uint8)` as torch's CPU kernels evaluate them, each operation rounded once in fp32: with
+    normalise = (mid, range) first y = ((x - mid) / range) * 2 (a true division), then clamp to [-1, 1], * 0.5 + 0.5, * 255, truncation; NaN
+    gives 0.  (`generate` run on a GPU tensor multiplies by the reciprocal of `range` instead -- torch's GPU kernel for a division by a
+    scalar -- which may move a depth value by an ulp; this function follows the CPU chain.)  GPU only; arguments are checked first."""
+    GH, GW = grid_shape(h, w, tiles, nrow, padding)
+    for name, v, lo in (('images', images, 1), ('stride_image', stride_image, 0), ('stride_tile', stride_tile, 0)):
+        if int(v) != v or v < lo:
+            raise ValueError(f'{name} must be an integer >= {lo}, got {v!r}')
+    if not isinstance(frames, torch.Tensor) or frames.ndim != 3 or frames.shape[1] != h * w or frames.shape[2] not in (1, 3) or frames.shape[0] < 1:
+        raise ValueError(f'frames must be a tensor [num_frames, h*w = {h * w}, 1 or 3], got {tuple(getattr(frames, "shape", ()))}')
+    last = (images - 1) * stride_image + (tiles - 1) * stride_tile
+    if last >= frames.shape[0]:
+        raise ValueError(f'source frame index {last} (image {images - 1}, tile {tiles - 1}) is out of range: there are {frames.shape[0]} frames')
+    if GH * GW * 3 >= 2 ** 31:
+        raise ValueError(f'one {GH} x {GW} grid exceeds 2^31 bytes')
+    if normalise is not None:
+        mid, rng = (float(v) for v in normalise)
+    else:
+        mid, rng = 0.0, 1.0
+    _lib.require_cuda(frames, 'frames')
+    frames = _lib.f32c(frames)
+    out = torch.empty([int(images), GH, GW, 3], dtype=torch.uint8, device=frames.device)
+    with torch.cuda.device(frames.device):
+        _lib.call('tdgp_frames_to_grid_u8', frames.data_ptr(), frames.shape[0], int(h), int(w), frames.shape[2], out.data_ptr(), int(images), int(tiles),
+                  int(stride_image), int(stride_tile), int(nrow), int(padding), int(normalise is not None), mid, rng, _lib.stream_of(frames))
+    return out
+
+
+def _ray_major_frames(G, ws, camera_params, depth, plane_batch, **kwargs):
+    """All frames of all samples, ray-major and sample-major on the device: rgb [num_samples * V, R, C] or depth [num_samples * V, R, 1]."""
+    parts = [(out.depth if depth else out.rgb) for out in _plane_batches(G, ws, camera_params, plane_batch, ray_major=True, **kwargs)]
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+
+
+def _depth_normalisation(G):
+    return ((G.cfg.ray_start + G.cfg.ray_end) * 0.5, G.cfg.ray_end - G.cfg.ray_start)
+
+
+def render_video_grid(G, ws, camera_params, nrow='auto', depth=False, plane_batch=4, num_videos=None, padding=2, as_numpy=False, **kwargs):
+    """scripts/inference.py:68-75 (`video_grid`) on the device: frame t of the video is the make_grid of every sample's view t ->
+    uint8 [T, GH, GW, 3] (a device tensor; as_numpy=True: one copy to the host).  Shared planes, ray-major buffers, `frames_to_grid`.
+    nrow='auto' = ceil(sqrt(min(num_videos, num_samples))) as the reference script sets it (num_videos: its num_videos_per_grid, default all
+    samples).  depth=True shows the depth maps, normalised by the ray range.  kwargs: render_opts, u_coarse, u_fine, max_rays_per_call, block kwargs."""
+    num_samples = len(ws)
+    V = len(camera_params) // max(num_samples, 1)
+    if nrow == 'auto':
+        nrow = int(np.ceil(min(num_samples if num_videos is None else num_videos, num_samples) ** 0.5))
+    res = G.synthesis.test_resolution
+    grid_shape(res, res, num_samples, nrow, padding)
+    frames = _ray_major_frames(G, ws, camera_params, depth, plane_batch, **kwargs)
+    out = frames_to_grid(frames, res, res, tiles=num_samples, images=V, stride_image=1, stride_tile=V, nrow=nrow, padding=padding,
+                         normalise=_depth_normalisation(G) if depth else None)
+    return _to_host(out) if as_numpy else out
+
+
+def render_image_strips(G, ws, camera_params, depth=False, plane_batch=4, as_numpy=False, **kwargs):
+    """scripts/inference.py:63-66 (`image_grid`): per sample, its views side by side (`torch.cat(list(images), dim=3)`) ->
+    uint8 [num_samples, h, V * w, 3] on the device."""
+    num_samples = len(ws)
+    V = len(camera_params) // max(num_samples, 1)
+    res = G.synthesis.test_resolution
+    frames = _ray_major_frames(G, ws, camera_params, depth, plane_batch, **kwargs)
+    out = frames_to_grid(frames, res, res, tiles=V, images=num_samples, stride_image=V, stride_tile=1, nrow=V, padding=0,
+                         normalise=_depth_normalisation(G) if depth else None)
+    return _to_host(out) if as_numpy else out
+
+
+def _to_host(out):
+    host = out.cpu().numpy()                                           # a synchronisation point
+    _lib.raise_on_device_fault('frames_to_grid()')
+    return host
+
+
+def save_video(frames_u8, path, fps=25):
+    """uint8 [T, H, W, 3] (device / host tensor or numpy) -> `path`, by extension: .gif through PIL exactly as scripts/inference.py:78-79 writes
+    it; .png one grid (T == 1, or a single [H, W, 3] image); .npy the raw block; .mp4 through torchvision.io or PyAV when one of them is
+    installed (h264, as scripts/inference.py:81) -- no encoder is vendored."""
+    from PIL import Image
+    x = _to_host(frames_u8) if isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda else np.asarray(frames_u8)
+    if x.ndim == 3:
+        x = x[None]
+    if x.dtype != np.uint8 or x.ndim != 4 or x.shape[-1] != 3 or x.shape[0] < 1:
+        raise ValueError(f'save_video takes uint8 [T, H, W, 3], got {x.dtype} {x.shape}')
+    ext = str(path).rsplit('.', 1)[-1].lower()
+    if ext == 'gif':
+        frames = [Image.fromarray(f, 'RGB') for f in x]
+        frames[0].save(path, quality=75, save_all=True, append_images=frames[1:], duration=1000 / fps, loop=0)
+    elif ext == 'png':
+        if x.shape[0] != 1:
+            raise ValueError(f'.png holds one grid, got {x.shape[0]} frames (use .gif / .npy / .mp4)')
+        Image.fromarray(x[0], 'RGB').save(path)
+    elif ext == 'npy':
+        np.save(path, x)
+    elif ext == 'mp4':
+        try:
+            from torchvision.io import write_video
+        except ImportError:
+            write_video = None
+        if write_video is not None:
+            write_video(path, torch.from_numpy(x), fps=fps, video_codec='h264', options={'crf': '10'})
+            return path
+        try:
+            import av
+        except ImportError:
+            raise RuntimeError('.mp4 needs an encoder: install PyAV (`av`) or torchvision (`torchvision.io`); neither imports here. '
+                               '.gif, .png and .npy need nothing else') from None
+        with av.open(path, mode='w') as container:
+            stream = container.add_stream('h264', rate=int(fps))
+            stream.height, stream.width, stream.pix_fmt = x.shape[1], x.shape[2], 'yuv420p'
+            stream.options = {'crf': '10'}
+            for f in x:
+                for packet in stream.encode(av.VideoFrame.from_ndarray(f, format='rgb24')):
+                    container.mux(packet)
+            for packet in stream.encode():
+                container.mux(packet)
+    else:
+        raise ValueError(f'unknown extension {ext!r}: .gif, .png, .npy or .mp4')
+    return path
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -399,6 +399,21 @@ int     tdgp_render_fused(const float* planes_hwc, const float* w0, const float*
 /* [B, h*w, 3] ray colours -> [B,3,h,w] image (networks_epigraf.py:242). */
 int tdgp_rays_to_image(const float* rgb, float* img, int B, int hw, tdgp_stream_t stream);
 
+/* Ray-major fp32 frames -> uint8 image grids, the [T,H,W,3] block a video / image encoder takes (inference_utils.py:113-117 `generate`'s value
+ * chain, scripts/inference.py:66,74-75 make_grid + `(x * 255).to(uint8)` + permute, which the reference runs on the host).
+ * frames [num_frames, h*w, C] fp32 (the renderer's rgb, C = 3, or depth, C = 1: replicated to three channels) -> out [images, GH, GW, 3] uint8.
+ * Tile k of output image i shows frame i * stride_image + k * stride_tile; an index >= num_frames is TDGP_EINVAL.
+ * Layout = torchvision make_grid(nrow, padding, pad_value = 0): xmaps = min(nrow, tiles), ymaps = ceil(tiles / xmaps),
+ *   GH = (h + padding) * ymaps + padding, GW = (w + padding) * xmaps + padding, tile k at row (k / xmaps) * (h + padding) + padding and column
+ *   (k % xmaps) * (w + padding) + padding; every byte outside a tile (the cells of a ragged last row too) is 0; tiles == 1: the tile itself,
+ *   unpadded (GH = h, GW = w).
+ * Values, each operation rounded once in fp32 as torch's CPU kernels evaluate them: y = x, or with `normalise` y = ((x - mid) / range) * 2 (IEEE
+ *   division); y = min(max(y, -1), 1); z = y * 0.5 + 0.5; byte = trunc(z * 255); NaN -> 0.
+ * One writer per output byte, no atomics, no workspace: the same bytes on every run.  frames and out 4-byte aligned; one output image < 2^31 bytes. */
+int tdgp_frames_to_grid_u8(const float* frames, int64_t num_frames, int h, int w, int C, uint8_t* out, int images, int tiles,
+                           int64_t stride_image, int64_t stride_tile, int nrow, int padding, int normalise, float mid, float range,
+                           tdgp_stream_t stream);
+
 /* create_voxel_coords (scripts/extract_geometry.py:55-76; torch CPU ops over the whole grid there): the coordinates of grid indices
  * [i0, i0 + n) of a res^3 grid -> coords [n,3], bit for bit the reference's fp32 chain: the index converted to fp32 (inexact above 2^24),
  * y = (idx / res) % res and x = ((idx / res) / res) % res as UNFLOORED fp32 divisions, z from the integer remainder, then

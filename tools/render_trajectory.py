@@ -1,0 +1,120 @@
+#!/usr/bin/env python3
+"""Render camera trajectories of generated samples into a video grid or image strips (the reference's scripts/inference.py): one JSON line.
+
+    python tools/render_trajectory.py --ckpt exported_dir/ --seeds 0-15 --trajectory front_circle --num-frames 32 --vis video_grid \\
+        --img-resolution 256 --ray-step-multiplier 2 --out grid.gif
+
+`--ckpt` is a directory written by tools/export_reference_checkpoint.py.  `--vis video_grid`: frame t of the output shows every sample's view t
+in a make_grid (`--nrow auto` = ceil(sqrt(samples))); write it as .gif, .npy or -- with PyAV or torchvision installed -- .mp4.  `--vis image_grid`:
+one strip per sample, its views side by side; .png (the strips stacked into one image) or .npy.  The tri-plane backbone runs once per sample
+(`--plane-batch` samples at a time), every frame is rendered from its sample's planes, and the frames become the uint8 grid on the device.
+"""
+import argparse
+import importlib
+import json
+import os
+import re
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def parse_range(s):
+    """'0-15', '1,4,7' or '0-3,8' -> list of ints (scripts/inference.py's seed syntax)."""
+    out = []
+    for part in str(s).split(','):
+        m = re.fullmatch(r'\s*(\d+)\s*-\s*(\d+)\s*', part)
+        if m:
+            out.extend(range(int(m.group(1)), int(m.group(2)) + 1))
+        elif part.strip():
+            out.append(int(part))
+    if not out:
+        raise argparse.ArgumentTypeError(f'empty range {s!r}')
+    return out
+
+
+def build_trajectory(args):
+    """The trajectory entries of configs/scripts/inference.yaml, from the command line."""
+    t = dict(name=args.trajectory, num_frames=args.num_frames, use_mean_camera=not args.posterior_camera, fov_offset=args.fov_offset)
+    if args.trajectory == 'front_circle':
+        t.update(yaw_diff=args.yaw_diff, pitch_diff=args.pitch_diff, fov_diff=args.fov_diff)
+    elif args.trajectory == 'points':
+        t.update(yaw_offsets=[float(v) for v in args.yaw_offsets.split(',')], pitch_offset=args.pitch_offset)
+    elif args.trajectory == 'point':
+        t.update(num_frames=1, yaw_offset=args.yaw_offset, pitch_offset=args.pitch_offset)
+    elif args.trajectory == 'line':
+        t.update(yaw_start=args.yaw_start, yaw_end=args.yaw_end, pitch_start=args.pitch_start, pitch_end=args.pitch_end, fov=None)
+    return t
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    p.add_argument('--ckpt', required=True, metavar='DIR', help='directory written by tools/export_reference_checkpoint.py')
+    p.add_argument('--seeds', type=parse_range, default=parse_range('0-15'), help="e.g. '0-15' or '1,4,7'")
+    p.add_argument('--classes', type=parse_range, default=None, help='class indices of a conditional generator (every seed under every class)')
+    p.add_argument('--truncation-psi', type=float, default=1.0)
+    p.add_argument('--trajectory', choices=['front_circle', 'points', 'point', 'line'], default='front_circle')
+    p.add_argument('--num-frames', type=int, default=32)
+    p.add_argument('--yaw-diff', type=float, default=0.5)
+    p.add_argument('--pitch-diff', type=float, default=0.3)
+    p.add_argument('--fov-diff', type=float, default=1.0)
+    p.add_argument('--fov-offset', type=float, default=0.0)
+    p.add_argument('--yaw-offsets', default='-0.5,0.0,0.5', help="the 'points' trajectory; write --yaw-offsets=-0.5,0,0.5 (a leading minus needs the '=')")
+    p.add_argument('--yaw-offset', type=float, default=0.0)
+    p.add_argument('--pitch-offset', type=float, default=0.0)
+    p.add_argument('--yaw-start', type=float, default=-0.6)
+    p.add_argument('--yaw-end', type=float, default=0.6)
+    p.add_argument('--pitch-start', type=float, default=np.pi / 2)
+    p.add_argument('--pitch-end', type=float, default=np.pi / 2)
+    p.add_argument('--posterior-camera', action='store_true', help='a posterior camera sample per seed instead of the mean camera')
+    p.add_argument('--vis', choices=['video_grid', 'image_grid'], default='video_grid')
+    p.add_argument('--nrow', default='auto', help="'auto' or an integer (video_grid)")
+    p.add_argument('--fps', type=float, default=25)
+    p.add_argument('--depth', action='store_true', help='show the depth maps (normalised by the ray range) instead of the colours')
+    p.add_argument('--img-resolution', type=int, default=None, help='default: the checkpoint\'s')
+    p.add_argument('--ray-step-multiplier', type=int, default=1)
+    p.add_argument('--force-whiteback', action='store_true')
+    p.add_argument('--far-plane-offset', type=float, default=0.0)
+    p.add_argument('--plane-batch', type=int, default=4, help='samples whose tri-planes are held at a time')
+    p.add_argument('--seed', type=int, default=0, help='fixes the non-z randomness (stratified / importance draws, posterior cameras)')
+    p.add_argument('--out', required=True, metavar='PATH', help='.gif / .npy / .mp4 (video_grid), .png / .npy (image_grid)')
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    nrow = args.nrow if args.nrow == 'auto' else int(args.nrow)
+    if REPO not in sys.path:
+        sys.path.insert(0, REPO)
+    import torch
+    tdgp = importlib.import_module('3dgp_amd')
+    I = tdgp.inference
+    cfg, sd = tdgp.weights.load_exported(args.ckpt)
+    G = tdgp.generator.Generator(cfg)
+    G.load_numpy_state_dict(sd)
+    G = G.to('cuda').eval()
+    I.configure_for_inference(G, args.img_resolution or G.img_resolution, args.ray_step_multiplier, force_whiteback=args.force_whiteback,
+                              far_plane_offset=args.far_plane_offset)
+    torch.manual_seed(args.seed)
+    np.random.seed(args.seed)
+    t0 = time.perf_counter()
+    with torch.no_grad():
+        ws, z, c = I.sample_ws_from_seeds(G, args.seeds, truncation_psi=args.truncation_psi, device='cuda', classes=args.classes)
+        cams = I.generate_camera_params(G, z, c, build_trajectory(args))
+        if args.vis == 'video_grid':
+            block = I.render_video_grid(G, ws, cams, nrow=nrow, depth=args.depth, plane_batch=args.plane_batch, as_numpy=True)
+        else:
+            block = I.render_image_strips(G, ws, cams, depth=args.depth, plane_batch=args.plane_batch, as_numpy=True)
+            if not args.out.lower().endswith('.npy'):
+                block = block.reshape(1, -1, *block.shape[2:])                  # the strips under each other: one image
+    seconds = time.perf_counter() - t0
+    I.save_video(block, args.out, fps=args.fps)
+    print(json.dumps(dict(out=args.out, vis=args.vis, shape=list(block.shape), samples=len(ws), frames=len(cams) // len(ws), trajectory=args.trajectory,
+                          img_resolution=G.synthesis.test_resolution, ray_steps=G.cfg.num_ray_steps, depth=args.depth, seconds=seconds, ckpt=args.ckpt)))
+
+
+if __name__ == '__main__':
+    main()
