@@ -59,8 +59,8 @@ def density_grid(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=
     slab = int(min(max(int(slab_points), 1), total, FIELD_POINTS_MAX))
     planes = _renderer.planes_to_hwc(syn.tri_plane_decoder(ws[:, :syn.tri_plane_decoder.num_ws], hwc=True, noise_mode=noise_mode))
     mlp, scale = syn.tri_plane_mlp, syn.cfg.cube_scale
-    fused = _renderer.fused_form(mlp)
-    params = _renderer._mlp_params(mlp) if fused else None
+    fused = _renderer.fused_form(mlp) or _renderer.deep_form(mlp)          # a field kernel evaluates it: two layers, or the deep form (3 / 4)
+    params = (_renderer._mlp_params_deep(mlp) if _renderer.deep_form(mlp) else _renderer._mlp_params(mlp)) if fused else None
     consts = _grid_constants(res, voxel_origin, cube_size)
     B = planes.t.shape[0]
     grid = torch.empty([B, total], dtype=torch.float32, device=ws.device)

@@ -17,6 +17,8 @@ Random numbers: the reference draws `torch.rand_like([B,R,S,1])` (:225) and `tor
 renderer.  Here they may be supplied explicitly as `rendering_options['u_coarse']` / `['u_fine']` (that is how parity
 is defined); when absent they are drawn on the device in the same order and shapes.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -246,8 +248,9 @@ class TriPlaneMLP(torch.nn.Module):
       n_layers == 0 : `nn.Identity` (feat_dim must be out_dim + 1: the planes carry rgb + sigma themselves);
       n_layers >= 2 : FC(feat -> hid, lrelu) x (n_layers - 1), FC(hid -> backbone_out_dim, linear), backbone_out_dim = 1 + (hid if has_view_cond else out_dim)
                       (with has_view_cond the reference's forward asserts backbone_out_dim == out_dim + 1, i.e. only hid_dim == out_dim runs: kept as is).
-    The 2-layer rgb + sigma form with widths from the kernel's table runs inside the fused field kernel (`fused_form`); every other form runs as the
-    reference does -- eager tensor ops on the looked-up features (tdgp_triplane_features) -- correct, not fast (VERDICT r05 missing #2)."""
+    The 2-layer rgb + sigma form with widths from the kernel's table runs inside the fused field kernel (`fused_form`), the 3- and 4-layer rgb + sigma
+    forms with hid_dim <= 64 inside the deep field kernel (`deep_form`, csrc/field_deep.hip), forward and gradient; every other form runs as the
+    reference does -- eager tensor ops on the looked-up features (tdgp_triplane_features) -- correct, not fast (VERDICT r05 missing #2), inference only."""
 
     class _FC(torch.nn.Module):
         def __init__(self, i, o, activation='linear'):
@@ -327,6 +330,34 @@ def _decoder_marcher(mlp):
     return marcher if marcher is not None else getattr(getattr(mlp, 'cfg', None), 'ray_marcher_type', 'classical')
 
 
+def deep_form(mlp):
+    """Does the deep field kernel (tdgp_triplane_field_deep) evaluate this decoder?  (3 or 4 layers, rgb + sigma, (feat_dim, hid_dim) from the
+    fused kernel's table with hid_dim <= 64, every hidden layer hid x hid.)  Works on a module shaped like the reference's too.
+    The gradient kernel takes feat_dim <= 32 of these (like the two-layer one): feat_dim 64 / hid_dim 64 is forward-only, and `render_autograd` says so up front."""
+    model = getattr(mlp, 'model', None)
+    if model is None or isinstance(model, torch.nn.Identity) or len(model) not in (3, 4):
+        return False
+    ws = [getattr(fc, 'weight', None) for fc in model]
+    if any(w is None or w.ndim != 2 for w in ws):
+        return False
+    hid, feat = ws[0].shape
+    return (ws[-1].shape[0] == 4 and hid <= 64 and (feat, hid) in _FUSED_PAIRS and all(tuple(w.shape) == (hid, hid) for w in ws[1:-1])
+            and ws[-1].shape[1] == hid)
+
+
+def _mlp_params_deep(mlp):
+    """([w0 .. w{n-1}], [b0 .. b{n-1}], marcher) of a 3- / 4-layer decoder -- the deep field kernel's operands."""
+    if not deep_form(mlp):
+        raise NotImplementedError('the deep field kernel takes the 3- or 4-layer rgb + sigma TriPlaneMLP with (feat_dim, hid_dim) from the fused table and '
+                                  'hid_dim <= 64; other decoders run through the eager path (renderer._field_eager)')
+    return ([_lib.f32c(fc.weight.detach()) for fc in mlp.model], [_lib.f32c(fc.bias.detach()) for fc in mlp.model], _decoder_marcher(mlp))
+
+
+def _ptr_array(tensors):
+    """Host array of device pointers (the `const float* const*` arguments of the deep entry points)."""
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
 class HWCPlanes:
     """Tri-planes already in the field kernel's layout [B,3,H,W,F] (what the fused backbone emits)."""
 
@@ -352,7 +383,14 @@ def planes_to_hwc(x):
 
 
 def _field(planes, mlp_params, scale, coords=None, ray_o=None, ray_d=None, t=None, tap_idx=None, ray_w=0, sigma_noise=None, density_noise=0.0):
-    w0, b0, w1, b1, marcher = mlp_params
+    """One field evaluation; the parameter pack picks the kernel: (w0, b0, w1, b1, marcher) from `_mlp_params` -> tdgp_triplane_field,
+    ([w..], [b..], marcher) from `_mlp_params_deep` -> tdgp_triplane_field_deep."""
+    deep = len(mlp_params) == 3
+    if deep:
+        ws, bs, marcher = mlp_params
+        w0 = ws[0]
+    else:
+        w0, b0, w1, b1, marcher = mlp_params
     p = planes.t
     B, _, H, W, F = p.shape
     if coords is not None:
@@ -368,6 +406,11 @@ def _field(planes, mlp_params, scale, coords=None, ray_o=None, ray_d=None, t=Non
         if sigma_noise.numel() != B * P:
             raise RuntimeError(f'sigma noise must have {B}x{P} elements')
     with torch.cuda.device(p.device):
+        if deep:
+            _lib.call('tdgp_triplane_field_deep', p.data_ptr(), _lib.ptr(coords), _lib.ptr(ray_o), _lib.ptr(ray_d), _lib.ptr(t), _ptr_array(ws), _ptr_array(bs),
+                      len(ws), _lib.ptr(sigma_noise) if density_noise > 0.0 else None, float(density_noise), rgbs.data_ptr(), _lib.ptr(tap_idx), B, P, S,
+                      int(ray_w), F, H, W, w0.shape[0], float(scale), MARCHER_IDS[marcher], _lib.stream_of(p))
+            return rgbs
         _lib.call('tdgp_triplane_field', p.data_ptr(), _lib.ptr(coords), _lib.ptr(ray_o), _lib.ptr(ray_d), _lib.ptr(t), w0.data_ptr(),
                   b0.data_ptr(), w1.data_ptr(), b1.data_ptr(), _lib.ptr(sigma_noise) if density_noise > 0.0 else None, float(density_noise),
                   rgbs.data_ptr(), _lib.ptr(tap_idx), B, P, S, int(ray_w), F, H, W, w0.shape[0], float(scale), MARCHER_IDS[marcher],
@@ -417,12 +460,14 @@ def simple_tri_plane_renderer(x, coords, mlp, scale=1.0, return_taps=False, sigm
     B = planes.t.shape[0]
     assert coords.ndim == 3 and coords.shape[0] == B and coords.shape[2] == 3, f'Wrong shape: coords {tuple(coords.shape)}'
     taps = torch.empty([B, coords.shape[1], 3, 2], dtype=torch.int32, device=coords.device) if return_taps else None
-    if not fused_form(mlp):
+    deep = deep_form(mlp)
+    if not deep and not fused_form(mlp):
         if return_taps:
-            raise NotImplementedError('tap indices are an output of the fused field kernel (2-layer decoder)')
+            raise NotImplementedError('tap indices are an output of the field kernels (2-, 3- and 4-layer decoders)')
         rgbs = _field_eager(planes, mlp, scale, coords=coords, sigma_noise=sigma_noise, density_noise=density_noise)
         return {'rgb': rgbs[..., :-1], 'sigma': rgbs[..., -1:]}
-    rgbs = _field(planes, _mlp_params(mlp), scale, coords=coords, tap_idx=taps, sigma_noise=sigma_noise, density_noise=density_noise)
+    rgbs = _field(planes, _mlp_params_deep(mlp) if deep else _mlp_params(mlp), scale, coords=coords, tap_idx=taps, sigma_noise=sigma_noise,
+                  density_noise=density_noise)
     out = {'rgb': rgbs[..., :3], 'sigma': rgbs[..., 3:4]}
     if return_taps:
         out['taps'] = taps
@@ -433,16 +478,29 @@ def simple_tri_plane_renderer_backward(x, coords, mlp, d_rgb, d_sigma, scale=1.0
     """Gradients of `simple_tri_plane_renderer` (tri_plane_renderer.py:560-588 + TriPlaneMLP) for incoming d_rgb [B,P,3], d_sigma
     [B,P,1]: returns (d_planes in the field layout [B,3,H,W,F] or None, d_w0, d_b0, d_w1, d_b1) and, with `coords_grad`, d_coords
     [B,P,3] (grid_sampler's grid gradient through the plane mean and `coords / scale`).  tdgp_triplane_field_grad: forward values are
-    recomputed; the plane gradient is a scatter with fp32 atomics (as torch's grid_sampler backward)."""
+    recomputed; the plane gradient is a scatter with fp32 atomics (as torch's grid_sampler backward).
+    For a 3- / 4-layer decoder (`deep_form`, tdgp_triplane_field_deep_grad) the return is (d_planes, [d_w0 ..], [d_b0 ..]) and, with `coords_grad`, d_coords."""
     planes = planes_to_hwc(x)
     _lib.require_cuda(coords, 'coords')
     coords = _lib.f32c(coords)
-    w0, b0, w1, b1, marcher = _mlp_params(mlp)
     p = planes.t
     B, _, H, W, F = p.shape
     P = coords.shape[1]
     d_out = torch.cat([_lib.f32c(d_rgb), _lib.f32c(d_sigma)], dim=-1).contiguous()
     d_planes = torch.zeros_like(p) if planes_grad else None
+    if deep_form(mlp):
+        ws, bs, marcher = _mlp_params_deep(mlp)
+        hid, n = ws[0].shape[0], len(ws)
+        d_ws, d_bs = [torch.empty_like(w) for w in ws], [torch.empty_like(b) for b in bs]
+        d_coords = torch.empty([B, P, 3], dtype=torch.float32, device=p.device) if coords_grad else None
+        nbytes = int(_lib.load().tdgp_triplane_field_deep_grad_workspace_bytes(B, P, F, hid, n))
+        ws_buf = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=p.device)
+        with torch.cuda.device(p.device):
+            _lib.call('tdgp_triplane_field_deep_grad', p.data_ptr(), coords.data_ptr(), _ptr_array(ws), _ptr_array(bs), n, d_out.data_ptr(),
+                      _lib.ptr(d_planes), _ptr_array(d_ws), _ptr_array(d_bs), _lib.ptr(d_coords), ws_buf.data_ptr(), nbytes, B, P, F, H, W, hid,
+                      float(scale), MARCHER_IDS[marcher], _lib.stream_of(p))
+        return (d_planes, d_ws, d_bs, d_coords) if coords_grad else (d_planes, d_ws, d_bs)
+    w0, b0, w1, b1, marcher = _mlp_params(mlp)
     hid = w0.shape[0]
     d_w0, d_b0, d_w1, d_b1 = torch.empty_like(w0), torch.empty_like(b0), torch.empty_like(w1), torch.empty_like(b1)
     d_coords = torch.empty([B, P, 3], dtype=torch.float32, device=p.device) if coords_grad else None
@@ -580,7 +638,8 @@ class ImportanceRenderer(torch.nn.Module):
     # -- gradient of the whole chain -----------------------------------------------------------------------------------
     def backward(self, planes, decoder, ray_origins, ray_directions, rendering_options, d_rgb, d_depth=None, rays_grad=False):
         """Gradients of `forward` (tri_plane_renderer.py:126-170 under autograd) w.r.t. the planes and the decoder's tensors for
-        incoming d_rgb [B,R,3] / d_depth [B,R,1]: returns dict(planes=[B,3F,H,W], w0, b0, w1, b1) and, with `rays_grad`, ray_o / ray_d
+        incoming d_rgb [B,R,3] / d_depth [B,R,1]: returns dict(planes=[B,3F,H,W], w0, b0, w1, b1) -- w0 .. w{n-1}, b0 .. b{n-1} for an n-layer
+        decoder of the deep form -- and, with `rays_grad`, ray_o / ray_d
         [B,R,3] -- the gradient that reaches the cameras (points = origin + t * direction, :141; the field kernel's coordinate gradient
         summed over a ray's samples).
 
@@ -622,16 +681,24 @@ class ImportanceRenderer(torch.nn.Module):
             passes = [(pts_c, g_c, g_s)]
         total = None
         d_ro = d_rd = None
+        deep = deep_form(decoder)
         for (pts, gc, gs), tt in zip(passes, (td, tf) if N > 0 else (td,)):
             res = simple_tri_plane_renderer_backward(hw, pts, decoder, gc.reshape(B, -1, 3), gs.reshape(B, -1, 1), scale=scale, coords_grad=rays_grad)
             if rays_grad:
                 # points = origin + t * direction (tri_plane_renderer.py:141): the depths are data (stratified draws / detached importance samples)
-                dpts = res[5].reshape(B, R, -1, 3)
+                dpts = res[-1].reshape(B, R, -1, 3)
                 d_ro = dpts.sum(2) if d_ro is None else d_ro + dpts.sum(2)
                 d_rd = (dpts * tt).sum(2) if d_rd is None else d_rd + (dpts * tt).sum(2)
-                res = res[:5]
+                res = res[:-1]
+            if deep:                     # (d_planes, [d_w..], [d_b..]) -> one flat list, layer by layer
+                res = [res[0]] + [g for pair in zip(res[1], res[2]) for g in pair]
             total = list(res) if total is None else [a + b for a, b in zip(total, res)]
-        out = dict(planes=planes_from_hwc(total[0]), w0=total[1], b0=total[2], w1=total[3], b1=total[4])
+        if deep:
+            out = dict(planes=planes_from_hwc(total[0]))
+            for i in range((len(total) - 1) // 2):
+                out[f'w{i}'], out[f'b{i}'] = total[1 + 2 * i], total[2 + 2 * i]
+        else:
+            out = dict(planes=planes_from_hwc(total[0]), w0=total[1], b0=total[2], w1=total[3], b1=total[4])
         if rays_grad:
             out.update(ray_o=d_ro, ray_d=d_rd)
         return out
@@ -649,12 +716,13 @@ class ImportanceRenderer(torch.nn.Module):
         n_coarse, n_fine = opts.get('n_coarse'), opts.get('n_fine')
         planes = planes_to_hwc(planes)
         fused_mlp = fused_form(decoder)
-        mlp = _mlp_params(decoder) if fused_mlp else None
+        deep_mlp = deep_form(decoder)
+        mlp = _mlp_params(decoder) if fused_mlp else (_mlp_params_deep(decoder) if deep_mlp else None)
         if _decoder_marcher(decoder) != marcher:
             raise RuntimeError(f'decoder was built for ray_marcher_type={_decoder_marcher(decoder)}, renderer for {marcher}')
-        if fused_mlp:
+        if fused_mlp or deep_mlp:         # (deep: the staged chain below with tdgp_triplane_field_deep; tdgp_render_fused stays two-layer only)
             field = lambda tt, nz: _field(planes, mlp, scale, ray_o=ray_o, ray_d=ray_d, t=tt, ray_w=ray_w, sigma_noise=nz, density_noise=dnoise)      # noqa: E731
-        else:         # tri_plane.mlp.n_layers != 2 / has_view_cond / widths outside the kernel's table: the reference's own op sequence (eager), same chain around it
+        else:         # tri_plane.mlp.n_layers 0 or > 4 / has_view_cond / widths outside the kernels' table: the reference's own op sequence (eager), same chain around it
             if getattr(decoder, 'out_dim', 3) != 3:
                 raise NotImplementedError('the march kernels composite rgb + sigma (out_dim == 3)')
             field = lambda tt, nz: _field_eager(planes, decoder, scale, ray_o=ray_o, ray_d=ray_d, t=tt, sigma_noise=nz, density_noise=dnoise)              # noqa: E731
@@ -785,10 +853,38 @@ class _RenderFunction(torch.autograd.Function):
         return res['planes'], res['w0'], res['b0'], res['w1'], res['b1'], None, None, res.get('ray_o'), res.get('ray_d'), None
 
 
+class _RenderFunctionDeep(torch.autograd.Function):
+    """`_RenderFunction` for the 3- and 4-layer decoders (`deep_form`): the same node with every layer's weight and bias as inputs
+    (w0, b0, .., w{n-1}, b{n-1} behind the fixed arguments) and as many gradients returned."""
+
+    @staticmethod
+    def forward(ctx, planes, renderer, decoder, ray_o, ray_d, opts, *params):
+        return _RenderFunction.forward(ctx, planes, None, None, None, None, renderer, decoder, ray_o, ray_d, opts)
+
+    @staticmethod
+    def backward(ctx, d_rgb, d_depth):
+        planes, = ctx.saved_tensors
+        renderer, decoder, ray_o, ray_d, opts = ctx.state
+        if d_rgb is None:
+            d_rgb = torch.zeros([ray_o.shape[0], ray_o.shape[1], 3], device=ray_o.device)
+        rays_grad = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
+        res = renderer.backward(planes.detach(), decoder, ray_o, ray_d, opts, d_rgb.contiguous(), None if d_depth is None else d_depth.contiguous(),
+                                rays_grad=rays_grad)
+        n = len(decoder.model)
+        grads = [g for i in range(n) for g in (res[f'w{i}'], res[f'b{i}'])]
+        return (res['planes'], None, None, res.get('ray_o'), res.get('ray_d'), None, *grads)
+
+
 def render_autograd(renderer, planes, decoder, ray_origins, ray_directions, rendering_options):
-    """(rgb [B,R,3], depth [B,R,1]) with gradients flowing to `planes` ([B,3F,H,W]), the decoder's four tensors and -- when they carry
-    a graph (camera_rays_autograd) -- the ray origins / directions."""
+    """(rgb [B,R,3], depth [B,R,1]) with gradients flowing to `planes` ([B,3F,H,W]), the decoder's tensors (four for the two-layer form,
+    every layer's for the 3- / 4-layer deep form) and -- when they carry a graph (camera_rays_autograd) -- the ray origins / directions."""
     check_grad_sample_counts(int(rendering_options['num_proposal_steps']), int(rendering_options['num_fine_steps']))
     m = decoder.model
+    if deep_form(decoder):
+        if m[0].weight.shape[1] > 32:       # tdgp_triplane_field_deep_grad takes feat_dim <= 32 (as the two-layer gradient kernel): say so here, not inside backward()
+            raise NotImplementedError(f'gradients through a 3- / 4-layer decoder take feat_dim in {{8, 16, 32}} (got {m[0].weight.shape[1]}): the '
+                                      f'feat_dim 64 / hid_dim 64 form is forward-only')
+        params = [t for fc in m for t in (fc.weight, fc.bias)]
+        return _RenderFunctionDeep.apply(planes, renderer, decoder, ray_origins, ray_directions, rendering_options, *params)
     return _RenderFunction.apply(planes, m[0].weight, m[0].bias, m[1].weight, m[1].bias, renderer, decoder, ray_origins, ray_directions,
                                  rendering_options)

@@ -323,6 +323,29 @@ int     tdgp_triplane_field_grad(const float* planes_hwc, const float* coords, c
                                  float* d_b0, float* d_w1, float* d_b1, float* d_coords, void* workspace, int64_t workspace_bytes,
                                  int B, int64_t P, int F, int H, int W, int hid, float scale, int marcher, tdgp_stream_t stream);
 
+/* tdgp_triplane_field for the 3- and 4-layer decoders (tri_plane.mlp.n_layers = 3, 4; networks_epigraf.py:35-43: FC(F -> hid, lrelu),
+ * n_layers - 2 x FC(hid -> hid, lrelu), FC(hid -> 4)).  Same contract in every other respect: coords or ray mode, `ray_w` image walk (results
+ * are identical), tap_idx rows (equal to tdgp_triplane_field's on the same points), sigma_noise / density_noise, marcher, rgbs [B,P,4].
+ * w, b: HOST arrays of n_layers DEVICE pointers to the RAW module parameters: w[0] [hid,F], w[1 .. n_layers-2] [hid,hid], w[n_layers-1] [4,hid],
+ * b[i] the matching biases (gains 1/sqrt(fan_in), lrelu 0.2 * sqrt(2) applied inside).
+ * Takes n_layers 3 and 4 with F in {8,16,32} x hid in {16,32,64}, or F = hid = 64; everything else -- n_layers 2 (tdgp_triplane_field is the
+ * only route of two-layer decoders), hid 128 (two hidden layers' operands do not fit the LDS) -- returns TDGP_EUNSUPPORTED before any launch. */
+int tdgp_triplane_field_deep(const float* planes_hwc, const float* coords, const float* ray_o, const float* ray_d,
+                             const float* t, const float* const* w, const float* const* b, int n_layers,
+                             const float* sigma_noise, float density_noise, float* rgbs, int32_t* tap_idx, int B, int64_t P,
+                             int S, int ray_w, int F, int H, int W, int hid, float scale, int marcher, tdgp_stream_t stream);
+
+/* Gradient of tdgp_triplane_field_deep in coords mode, with tdgp_triplane_field_grad's semantics: forward values are recomputed; d_planes_hwc
+ * is ACCUMULATED into with fp32 atomics (zero it first; NULL skips it); d_coords [B,P,3] is optional (NULL skips it); d_w[i] / d_b[i] (HOST
+ * arrays of n_layers DEVICE pointers, shapes of w[i] / b[i]) are written, reduced wave -> block -> grid in a fixed order: identical bytes run
+ * to run.  Requires n_layers 3 or 4, F in {8,16,24,32}, hid <= 64 (else TDGP_EUNSUPPORTED).
+ * workspace: tdgp_triplane_field_deep_grad_workspace_bytes(B, P, F, hid, n_layers) bytes (-1 for an n_layers it does not take). */
+int64_t tdgp_triplane_field_deep_grad_workspace_bytes(int B, int64_t P, int F, int hid, int n_layers);
+int     tdgp_triplane_field_deep_grad(const float* planes_hwc, const float* coords, const float* const* w, const float* const* b,
+                                      int n_layers, const float* d_out, float* d_planes_hwc, float* const* d_w, float* const* d_b,
+                                      float* d_coords, void* workspace, int64_t workspace_bytes, int B, int64_t P, int F, int H, int W,
+                                      int hid, float scale, int marcher, tdgp_stream_t stream);
+
 /* Generic marcher on [rays,S,C] colours, [rays,S] densities/depths (2 <= S <= 1024: a merged list of up to 512 + 512 samples; C <= 8).
  * Lists longer than 256 round alpha's exp from fp64; S > 1024 -> TDGP_EUNSUPPORTED.
  * weights: [rays,S] (classical, or mip with inf depth) / [rays,S-1] (mip without); may be NULL.

@@ -470,6 +470,81 @@ def gen_field_grad():
     save('field_grad', **arrays)
 
 
+def gen_field_deep():
+    """The 3- and 4-layer decoders the deep field kernels evaluate (tdgp_triplane_field_deep / _grad): simple_tri_plane_renderer + TriPlaneMLP under
+    autograd, `small_n3` (F 8, hid 16, 3 layers) and `hot_n4` (F 32, hid 64, 4 layers, a third of the points outside the cube), both marchers, every
+    output and gradient in fp32 AND from a float64 run of the same modules (the yardstick of the reference's own rounding noise), the latter stored
+    as `<name>_f64m32` = float64 result - fp32 result (a float32 array holds that difference to 2^-24 of itself, so float64 = fp32 + difference; stored
+    outright the float64 arrays would push the file past the size limit of a committed file); the decoder's tensors are shared by both marchers; plus one whole
+    ImportanceRenderer.forward under autograd with the 3-layer decoder (R = 64, S = N = 8, draws stored), as render_grad.npz has for two layers."""
+    arrays = {}
+    for tag, (B, F, R, hid, n, P) in dict(small_n3=(1, 8, 16, 16, 3, 200), hot_n4=(1, 32, 16, 64, 4, 32 * 5 + 7)).items():
+        g = np.random.RandomState(70 + F)
+        planes = g.randn(B, 3 * F, R, R).astype(np.float32)
+        coords = (g.rand(B, P, 3).astype(np.float32) * 2 - 1) * 0.48
+        if tag == 'hot_n4':
+            coords[:, ::3] *= 1.0 + 0.4 * g.rand(B, len(range(0, P, 3)), 3).astype(np.float32) + 0.05      # every third point leaves the cube (|c| up to 0.7)
+            coords[:, ::3] += np.sign(coords[:, ::3]) * 0.5 * (np.abs(coords[:, ::3]).max(-1, keepdims=True) < 0.5)
+        coords[0, :4] = [[0.5, 0.5, 0.5], [-0.5, -0.5, -0.5], [0.0, 0.0, 0.0], [0.5, -0.5, 0.25]]
+        d_rgb, d_sigma = g.randn(B, P, 3).astype(np.float32), g.randn(B, P, 1).astype(np.float32)
+        arrays.update({f'{tag}_planes': planes, f'{tag}_coords': coords, f'{tag}_d_rgb': d_rgb, f'{tag}_d_sigma': d_sigma})
+        biases = [g.randn(4 if i == n - 1 else hid).astype(np.float32) * 0.3 for i in range(n)]
+        for marcher in ('classical', 'mip'):
+            cfg = EasyDict(tri_plane=EasyDict(feat_dim=F, mlp=EasyDict(n_layers=n, hid_dim=hid)), has_view_cond=False, ray_marcher_type=marcher)
+            torch.manual_seed(8)
+            mlp = TriPlaneMLP(cfg, out_dim=3)
+            with torch.no_grad():
+                for fc, bias in zip(mlp.model, biases):
+                    fc.bias.copy_(T(bias))
+            for i, fc in enumerate(mlp.model):
+                arrays[f'{tag}_w{i}'], arrays[f'{tag}_b{i}'] = npy(fc.weight), npy(fc.bias)
+            res = {}
+            for suffix, dt in (('', torch.float32), ('_f64', torch.float64)):
+                m = mlp.to(dt)
+                x = T(planes).to(dt).requires_grad_(True)
+                cc = T(coords).to(dt).requires_grad_(True)
+                out = ref_tpr.simple_tri_plane_renderer(x, cc, m, scale=0.5)
+                params = [t for fc in m.model for t in (fc.weight, fc.bias)]
+                grads = torch.autograd.grad([out['rgb'], out['sigma']], [x] + params + [cc], [T(d_rgb).to(dt), T(d_sigma).to(dt)])
+                names = ['d_planes'] + [f'd_{k}{i}' for i in range(n) for k in ('w', 'b')] + ['d_coords']
+                res[suffix] = dict(zip(['rgb', 'sigma'] + names, [npy(t) for t in (out['rgb'], out['sigma'], *grads)]))
+            for name, a in res[''].items():
+                assert a.dtype == np.float32 and res['_f64'][name].dtype == np.float64
+                arrays[f'{tag}_{marcher}_{name}'] = a
+                arrays[f'{tag}_{marcher}_{name}_f64m32'] = (res['_f64'][name] - a.astype(np.float64)).astype(np.float32)
+    # the renderer chain with the 3-layer decoder
+    g = np.random.RandomState(73)
+    B, F, H, hid, hw, S = 2, 8, 16, 16, 8, 8
+    R = hw * hw
+    planes = g.randn(B, 3 * F, H, H).astype(np.float32)
+    cam = TensorGroup(angles=T(np.array([[0.3, 1.2, 0.0], [-0.6, 1.8, 0.0]], np.float32)), radius=T(np.ones(2, np.float32)),
+                      look_at=T(np.zeros((2, 3), np.float32)))
+    ro, rd = ref_tpr.sample_rays(ref_ru.compute_cam2world_matrix(cam), T(np.array([25.0, 40.0], np.float32)), (hw, hw))
+    u1, u2 = g.rand(B, R, S, 1).astype(np.float32), g.rand(B * R, S).astype(np.float32)
+    d_rgb, d_depth = g.randn(B, R, 3).astype(np.float32), g.randn(B, R, 1).astype(np.float32)
+    arrays.update(r_planes=planes, r_ray_o=npy(ro), r_ray_d=npy(rd), r_u_coarse=u1, r_u_fine=u2, r_d_rgb=d_rgb, r_d_depth=d_depth)
+    cfg = EasyDict(tri_plane=EasyDict(feat_dim=F, mlp=EasyDict(n_layers=3, hid_dim=hid)), has_view_cond=False, ray_marcher_type='classical')
+    torch.manual_seed(9)
+    mlp = TriPlaneMLP(cfg, out_dim=3)
+    with torch.no_grad():
+        for fc in mlp.model:
+            fc.bias.copy_(T(g.randn(*fc.bias.shape).astype(np.float32) * 0.3))
+    opts = EasyDict(box_size=1.0, num_proposal_steps=S, num_fine_steps=S, clamp_mode='softplus', use_inf_depth=True, ray_start=0.75, ray_end=1.25,
+                    white_back=False, last_back=False, density_bias=0.0, cut_quantile=0.0, max_batch_res=64, density_noise=0.0)
+    x = T(planes).requires_grad_(True)
+    rend = ref_tpr.ImportanceRenderer(ray_marcher_type='classical')
+    with PatchedRNG(rand_like=[T(u1)], rand=[T(u2)]):
+        rgb, depth, wsum, fT = rend(x.view(B, 3, F, H, H), mlp, ro, rd, opts)
+    params = [t for fc in mlp.model for t in (fc.weight, fc.bias)]
+    grads = torch.autograd.grad([rgb, depth], [x] + params, [T(d_rgb), T(d_depth)])
+    for i, fc in enumerate(mlp.model):
+        arrays[f'r_w{i}'], arrays[f'r_b{i}'] = npy(fc.weight), npy(fc.bias)
+    for name, t in zip(['d_planes'] + [f'd_{k}{i}' for i in range(3) for k in ('w', 'b')], grads):
+        arrays[f'r_{name}'] = npy(t)
+    arrays['r_rgb'], arrays['r_depth'] = npy(rgb), npy(depth)
+    save('field_deep', **arrays)
+
+
 def gen_render_grad():
     """Autograd through ImportanceRenderer.forward (tri_plane_renderer.py:126-170): gradient of sum(rgb * d_rgb) + sum(depth * d_depth)
     w.r.t. the planes and the decoder tensors, both marchers, with the stratification / inverse-CDF draws fixed."""
@@ -1661,6 +1736,7 @@ def main():
     gen_conv2d_grad()
     gen_march_grad()
     gen_field_grad()
+    gen_field_deep()
     gen_render_grad()
     gen_modconv_grad()
     gen_modconv()
