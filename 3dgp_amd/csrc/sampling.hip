@@ -836,7 +836,415 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(const float* __res
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// 64 + 64 pair forms: a wave owns rays 2w and 2w + 1, 8 rays per 256-thread block.  The kernels above sit at the
+// hardware's 8 waves per SIMD with half the register file empty, and what bounds them is the length of one ray's chain of dependent
+// LDS / cross-lane steps; here every phase is a function of ONE ray's state, fence-free inside, called for ray A and then for ray B
+// with the wave fence after both, so the scheduler has two independent chains to interleave and the global loads of both rays are
+// out before anything waits.  Per ray the operations and their order are those of the one-ray kernels (the loops below are the
+// same loops with their trip counts at 64 / 128 written out and their branches as selects): the same bits.  The slow paths (the
+// bitonic network after a key collision, the brute-force rank of a list that is not ascending) are wave-uniform branches per ray.
+// An odd last ray: its wave computes it twice (B = A) and B stores nothing.
+// ------------------------------------------------------------------------------------------------
+constexpr int PAIR_RAYS_PER_BLOCK = 8;
+
+// alpha_i and the transmittance factor of sample i of an LDS-resident list of S samples: march_classical_lds' / march_mip_lds' own expressions.
+__device__ __forceinline__ void classical_alpha(const float* z, const float* sig, int i, int S, int flags, float cut_thr, float& alpha, float& fac) {
+    const float delta = (i < S - 1) ? (z[i + 1] - z[i]) : ((flags & 1) ? 1e10f : 1e-3f);
+    float sp = (flags & 8) ? (sig[i] > 0.f ? sig[i] : 0.f) : softplus20f(sig[i]);
+    if (sp < cut_thr) sp = 0.f;
+    alpha = 1.0f - expf(-(delta * sp));
+    fac = (1.0f - alpha) + 1e-10f;
+}
+__device__ __forceinline__ void mip_alpha(const float* z, const float* sig, int i, int S, int M, float density_bias, float cut_thr, float& alpha, float& fac) {
+    alpha = 0.f; fac = 1.0f;
+    if (i < M) {
+        float delta, smid;
+        if (i < S - 1) { delta = z[i + 1] - z[i]; smid = (sig[i] + sig[i + 1]) / 2.f; }
+        else { delta = 1e10f; smid = sig[S - 1]; }
+        float sp = softplus20f(smid + density_bias);
+        if (sp < cut_thr) sp = 0.f;
+        const float dd = sp * delta;
+        alpha = 1.0f - expf(-dd);
+        fac = (1.0f - alpha) + 1e-10f;
+    }
+}
+
+// Importance form.  Scratch: z, sig, w, cdf, bins and the key column at 64 entries = 1552 B per ray, 12.4 KB per block; 8 blocks per CU
+// (99 KB of LDS) = 8 waves = 16 rays per SIMD, twice the one-ray form's.
+struct alignas(16) ImpPairScratch { float z[64]; float sig[64]; float w[64 + 4]; float cdf[64]; float bins[64]; float key[64]; };
+
+struct ImpRay {
+    ImpPairScratch* sc;
+    int64_t r;          // the ray (B of an odd last pair: A's ray again)
+    bool live;          // this ray stores its results
+    float zl, sg, u;    // lane l's coarse depth, density and draw
+    float nv;           // mip: the smoothed weight between its read and its write
+    float key;          // lane l's fine sample in t-space (draw order), then the sample sorted to position l
+    int cnt, idx;       // the number of smaller keys; the draw index sorted to position l
+};
+
+__device__ __forceinline__ void imp_load(ImpRay& R, const float* __restrict__ rgbs, const float* __restrict__ sdist, const float* __restrict__ u_fine) {
+    const int l = lane_id();
+    R.zl = sdist[R.r * 64 + l]; R.sg = rgbs[(R.r * 64 + l) * 4 + 3]; R.u = u_fine[R.r * 64 + l];
+}
+__device__ __forceinline__ void imp_park(ImpRay& R) { const int l = lane_id(); R.sc->z[l] = R.zl; R.sc->sig[l] = R.sg; }
+// coarse march of 64 samples: the single pass of march_classical_lds' / march_mip_lds' loop (carry = 1); returns sum w
+__device__ __forceinline__ float imp_march(ImpRay& R, int marcher, int flags, float density_bias, float cut_thr) {
+    const int l = lane_id();
+    const int M = (marcher == 0 || (flags & 1)) ? 64 : 63;
+    float alpha, fac;
+    if (marcher == 0) classical_alpha(R.sc->z, R.sc->sig, l, 64, flags, cut_thr, alpha, fac);
+    else mip_alpha(R.sc->z, R.sc->sig, l, 64, M, density_bias, cut_thr, alpha, fac);
+    const double carry = 1.0;
+    const double incl64 = wave_scan_f64<true>((double)fac) * carry;
+    const float incl = (float)incl64;
+    const float excl = wave_shr1_f32(incl, (float)carry);
+    const float wi = alpha * excl;
+    float wsum = 0.0f;
+    if (l < M) { R.sc->w[l] = wi; wsum += wi; }
+    return wave_sum_f32(wsum);
+}
+__device__ __forceinline__ void imp_last_back(ImpRay& R, float wagg) { if (lane_id() == 0) R.sc->w[63] += (1.0f - wagg); }
+// importance_lds' smoothing (mip: in two steps around a fence) or offset of the weights
+__device__ __forceinline__ void imp_smooth_read(ImpRay& R, int Wn) {
+    const int i = lane_id();
+    const float* w = R.sc->w;
+    if (i < Wn) {
+        const float a = (i - 1 >= 0) ? w[i - 1] : -INFINITY, b = w[i], d = (i + 1 < Wn) ? w[i + 1] : -INFINITY;
+        const float t0 = a > b ? a : b, t1 = b > d ? b : d;
+        R.nv = (t0 + t1) / 2.f + 0.01f;
+    }
+}
+__device__ __forceinline__ void imp_smooth_write(ImpRay& R, int Wn) { const int i = lane_id(); if (i < Wn) R.sc->w[i] = R.nv; }
+__device__ __forceinline__ void imp_offset(ImpRay& R, int Wn) { const int i = lane_id(); if (i < Wn) R.sc->w[i] = R.sc->w[i] + 1e-5f; }
+// torch_order_sum_lds for 56 <= n <= 62 (a pdf row of 61 or 62 entries): nv = 7 vectors, one interleaved group, vectors 4..6 into accumulator 0, n - 56 tail elements
+__device__ __forceinline__ float torch_order_sum_62(const float* w1, int n, float eps) {
+    const int l = lane_id();
+    const int col = l & 7, a = (l >> 3) & 3;
+    float acc = 0.f;
+    acc = __fadd_rn(acc, __fadd_rn(w1[a * 8 + col], eps));
+#pragma unroll
+    for (int j = 4; j < 7; j++) {
+        const float v = __fadd_rn(w1[j * 8 + col], eps);
+        if (a == 0) acc = __fadd_rn(acc, v);
+    }
+    float p = __shfl(acc, col, 64);
+    p = __fadd_rn(p, __shfl(acc, col + 8, 64));
+    p = __fadd_rn(p, __shfl(acc, col + 16, 64));
+    p = __fadd_rn(p, __shfl(acc, col + 24, 64));
+    float fin = 0.f;
+#pragma unroll
+    for (int k = 56; k < 62; k++) {
+        const float t = __fadd_rn(fin, __fadd_rn(w1[k], eps));
+        fin = k < n ? t : fin;
+    }
+#pragma unroll
+    for (int c = 0; c < 8; c++) fin = __fadd_rn(fin, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), c)));
+    return fin;
+}
+// bins, pdf normaliser (torch's order), cdf = [0, cumsum(pdf)] as the fp64 scan rounded per prefix
+__device__ __forceinline__ void imp_cdf(ImpRay& R, int Wn) {
+    const int l = lane_id();
+    const float eps = 1e-5f;
+    ImpPairScratch& sc = *R.sc;
+    const int ns = Wn - 2;
+    if (l < 63) sc.bins[l] = 0.5f * (sc.z[l] + sc.z[l + 1]);
+    const float totf = torch_order_sum_62(sc.w + 1, ns, eps);
+    const double carry = 0.0;
+    if (l == 0) sc.cdf[0] = 0.f;
+    const float pdf = (l < ns) ? (sc.w[1 + l] + eps) / totf : 0.f;
+    const double incl = wave_scan_f64<false>((double)pdf) + carry;
+    if (l < ns) sc.cdf[l + 1] = (float)incl;
+}
+// searchsorted(right=True) of lane l's draw in the nc <= 63 knots (6 halvings empty any such interval: the loop of importance_lds with a
+// fixed trip count), the sample, its t-space key into the key column
+__device__ __forceinline__ void imp_search(ImpRay& R, int Wn, float t_near, float t_far, float* __restrict__ sfine, int32_t* __restrict__ inds) {
+    const int l = lane_id();
+    const float eps = 1e-5f;
+    ImpPairScratch& sc = *R.sc;
+    const int nb = 63, ns = Wn - 2, nc = ns + 1;
+    const float uu = R.u;
+    int lo = 0, hi = nc;
+#pragma unroll
+    for (int it = 0; it < 6; it++) {
+        const bool open = lo < hi;
+        const int mid = (lo + hi) >> 1;
+        const bool right = sc.cdf[open ? mid : 0] <= uu;
+        lo = (open && right) ? mid + 1 : lo;
+        hi = (open && !right) ? mid : hi;
+    }
+    const int ind = lo;
+    const int below = ind - 1 < 0 ? 0 : ind - 1;
+    const int above = ind > ns ? ns : ind;
+    const float cb = sc.cdf[below], ca = sc.cdf[above];
+    const float bb = sc.bins[below < nb ? below : nb - 1], ba = sc.bins[above < nb ? above : nb - 1];
+    float denom = ca - cb;
+    if (denom < eps) denom = 1.f;
+    const float smp = bb + (uu - cb) / denom * (ba - bb);
+    R.key = s2t(smp, t_near, t_far);
+    sc.key[l] = R.key;
+    if (R.live) {
+        if (sfine) sfine[R.r * 64 + l] = smp;
+        if (inds) inds[R.r * 64 + l] = ind;
+    }
+}
+// the sorted slot of a key is the number of smaller keys; equal keys collide on a slot
+__device__ __forceinline__ void imp_count(ImpRay& R) {
+    const int l = lane_id();
+    int cnt = 0;
+#pragma unroll
+    for (int jj = 0; jj < 16; jj++) {
+        const float4 k4 = *(const float4*)&R.sc->key[4 * jj];
+        cnt += (k4.x < R.key ? 1 : 0) + (k4.y < R.key ? 1 : 0) + (k4.z < R.key ? 1 : 0) + (k4.w < R.key ? 1 : 0);
+    }
+    R.cnt = cnt;
+    ((int*)R.sc->bins)[cnt] = l;            // bins is free since imp_search
+}
+// read back: without a collision position l takes the key whose slot it is; with one the ray keeps (key, l) for the network.  Returns "no collision".
+__device__ __forceinline__ bool imp_gather(ImpRay& R) {
+    const int l = lane_id();
+    const int* slot = (const int*)R.sc->bins;
+    const bool ok = __all(slot[R.cnt] == l);
+    const int src = ok ? slot[l] : l;
+    R.key = R.sc->key[src];
+    R.idx = src;
+    return ok;
+}
+__device__ __forceinline__ void imp_store(const ImpRay& R, float* __restrict__ tfine, int32_t* __restrict__ fine_perm) {
+    const int l = lane_id();
+    if (R.live) {
+        tfine[R.r * 64 + l] = R.key;
+        if (fine_perm) fine_perm[R.r * 64 + l] = R.idx;
+    }
+}
+
+// importance_from_coarse_kernel<128> at S = N = 64, two rays per wave.  gfx950: see DESIGN.md 5.5 for the register count (at most 64, no scratch).
+__global__ __launch_bounds__(256, 8) void importance_from_coarse_pair_kernel(const float* __restrict__ rgbs, const float* __restrict__ sdist,
+                                                                            const float* __restrict__ u_fine, float* __restrict__ tfine,
+                                                                            float* __restrict__ sfine, int32_t* __restrict__ inds,
+                                                                            int32_t* __restrict__ fine_perm, int64_t rays, int marcher, int flags,
+                                                                            float density_bias, float cut_thr, float t_near, float t_far) {
+    __shared__ ImpPairScratch scratch[PAIR_RAYS_PER_BLOCK];
+    const int wv = threadIdx.x >> 6;
+    const int64_t r0 = ((int64_t)blockIdx.x * (PAIR_RAYS_PER_BLOCK / 2) + wv) * 2;
+    if (r0 >= rays) return;
+    ImpRay A, B;
+    A.sc = &scratch[2 * wv]; A.r = r0; A.live = true;
+    B.sc = &scratch[2 * wv + 1]; B.live = r0 + 1 < rays; B.r = B.live ? r0 + 1 : r0;
+    imp_load(A, rgbs, sdist, u_fine); imp_load(B, rgbs, sdist, u_fine);
+    imp_park(A); imp_park(B);
+    wave_sync();
+    const float waA = imp_march(A, marcher, flags, density_bias, cut_thr), waB = imp_march(B, marcher, flags, density_bias, cut_thr);
+    wave_sync();
+    int Wn = 64;
+    if (marcher == 0) {
+        if (flags & 2) { imp_last_back(A, waA); imp_last_back(B, waB); }
+        wave_sync();
+        imp_offset(A, Wn); imp_offset(B, Wn);
+    } else {
+        Wn = (flags & 1) ? 64 : 63;
+        imp_smooth_read(A, Wn); imp_smooth_read(B, Wn);
+        wave_sync();
+        imp_smooth_write(A, Wn); imp_smooth_write(B, Wn);
+    }
+    wave_sync();
+    imp_cdf(A, Wn); imp_cdf(B, Wn);
+    wave_sync();
+    imp_search(A, Wn, t_near, t_far, sfine, inds); imp_search(B, Wn, t_near, t_far, sfine, inds);
+    wave_sync();
+    imp_count(A); imp_count(B);
+    wave_sync();
+    const bool okA = imp_gather(A), okB = imp_gather(B);
+    if (!okA) wave_bitonic_sort(A.key, A.idx);      // per ray: the other one is done
+    if (!okB) wave_bitonic_sort(B.key, B.idx);
+    imp_store(A, tfine, fine_perm); imp_store(B, tfine, fine_perm);
+}
+
+// Merge form.  Scratch: six arrays of 128 entries = 3072 B per ray (the one-ray form's eight: the unsorted keys are dead once the scatter has run
+// and the weights take their place; last[] is dead before the scatter writes z and lives there), 24.6 KB per block; 6 blocks per CU
+// (147 KB of LDS) = 6 waves = 12 rays per SIMD against the one-ray form's 8.
+struct alignas(16) MergePairScratch {
+    float key[128];     // unsorted depths (coarse 0..63, fine 64..127); from the march on: the weights
+    float z[128];       // last[0..64] of the rank computation, then the sorted depths
+    float sig[128];
+    float col[3][128];
+};
+
+struct MergeRay {
+    MergePairScratch* sc;
+    int64_t r;
+    bool live;
+    float k[2];         // lane l's coarse and fine depth
+    float4 c[2];        // and their colours + density
+    int p2;             // draw index of fine element l
+    int lo;             // fine element l: #coarse <= its depth
+    int rank[2];
+    bool bad;
+};
+
+__device__ __forceinline__ void mrg_load(MergeRay& R, const float* __restrict__ rgbs1, const float* __restrict__ t1, const float* __restrict__ rgbs2,
+                                         const float* __restrict__ t2, const int32_t* __restrict__ perm2, bool want_perm) {
+    const int l = lane_id();
+    R.k[0] = t1[R.r * 64 + l]; R.k[1] = t2[R.r * 64 + l];
+    R.c[0] = ((const float4*)rgbs1)[R.r * 64 + l]; R.c[1] = ((const float4*)rgbs2)[R.r * 64 + l];
+    R.p2 = (want_perm && perm2) ? perm2[R.r * 64 + l] : l;
+}
+__device__ __forceinline__ void mrg_park(MergeRay& R) { const int l = lane_id(); R.sc->key[l] = R.k[0]; R.sc->key[64 + l] = R.k[1]; }
+// ascending check, last[] zeroed, the fine elements' binary search in the coarse list (7 lock-step halvings of [0, 64))
+__device__ __forceinline__ void mrg_search(MergeRay& R) {
+    const int l = lane_id();
+    const float* key = R.sc->key;
+    R.bad = l < 63 && (key[l + 1] < key[l] || key[64 + l + 1] < key[64 + l]);
+    int* const last = (int*)R.sc->z;
+    last[l] = 0;
+    if (l == 0) last[64] = 0;
+    const float v = R.k[1];
+    int lo = 0, hi = 64;
+#pragma unroll
+    for (int it = 0; it < 7; it++) {
+        const bool open = lo < hi;
+        const int mid = (lo + hi) >> 1;
+        const bool right = key[open ? mid : 0] <= v;
+        lo = (open && right) ? mid + 1 : lo;
+        hi = (open && !right) ? mid : hi;
+    }
+    R.lo = lo;
+}
+__device__ __forceinline__ void mrg_scatter_last(MergeRay& R) { atomicMax(&((int*)R.sc->z)[R.lo], lane_id() + 1); }
+// coarse ranks = own index + prefix maximum of last[]; fine ranks = own index + lo.  Returns "not ascending" (the ray needs the brute-force rank).
+__device__ __forceinline__ bool mrg_ranks(MergeRay& R) {
+    const int l = lane_id();
+    const int incl = max(wave_scan_max_i32(((const int*)R.sc->z)[l]), 0);
+    R.rank[0] = l + incl;
+    R.rank[1] = l + R.lo;
+    return __any(R.bad);
+}
+__device__ __forceinline__ void mrg_scatter(MergeRay& R, int32_t* __restrict__ perm) {
+    const int l = lane_id();
+    MergePairScratch& sc = *R.sc;
+#pragma unroll
+    for (int cc = 0; cc < 2; cc++) {
+        const int pos = R.rank[cc];
+        const float4 v = R.c[cc];
+        sc.z[pos] = R.k[cc];
+        sc.col[0][pos] = v.x; sc.col[1][pos] = v.y; sc.col[2][pos] = v.z; sc.sig[pos] = v.w;
+        if (perm && R.live) perm[R.r * 128 + pos] = cc == 0 ? l : 64 + R.p2;
+    }
+}
+// march of the merged 128 samples: march_classical_lds' two side-by-side chunks / the two passes of march_mip_lds' loop
+__device__ __forceinline__ void mrg_march(MergeRay& R, int marcher, int flags, float density_bias, float cut_thr, float& final_T, float& wagg) {
+    const int l = lane_id();
+    MergePairScratch& sc = *R.sc;
+    float* w = sc.key;
+    double carry = 1.0;
+    float wsum = 0.0f;
+    if (marcher == 0) {
+        float alpha[2], fac[2];
+#pragma unroll
+        for (int c = 0; c < 2; c++) classical_alpha(sc.z, sc.sig, 64 * c + l, 128, flags, cut_thr, alpha[c], fac[c]);
+        const double s0 = wave_scan_f64<true>((double)fac[0]), s1 = wave_scan_f64<true>((double)fac[1]);
+        const double c1 = wave_last_f64(s0);
+        const double i1 = s1 * c1;
+        const float incl0 = (float)s0, incl1 = (float)i1;
+        const float wi0 = alpha[0] * wave_shr1_f32(incl0, 1.0f), wi1 = alpha[1] * wave_shr1_f32(incl1, (float)c1);
+        w[l] = wi0; wsum += wi0;
+        w[64 + l] = wi1; wsum += wi1;
+        carry = wave_last_f64(i1);
+    } else {
+        const int M = (flags & 1) ? 128 : 127;
+#pragma unroll
+        for (int base = 0; base < 128; base += 64) {
+            const int i = base + l;
+            float alpha, fac;
+            mip_alpha(sc.z, sc.sig, i, 128, M, density_bias, cut_thr, alpha, fac);
+            const double incl64 = wave_scan_f64<true>((double)fac) * carry;
+            const float incl = (float)incl64;
+            const float excl = wave_shr1_f32(incl, (float)carry);
+            const float wi = alpha * excl;
+            if (i < M) { w[i] = wi; wsum += wi; }
+            carry = wave_last_f64(incl64);
+        }
+    }
+    wagg = wave_sum_f32(wsum);
+    final_T = (float)carry;
+}
+__device__ __forceinline__ void mrg_last_back(MergeRay& R, float wagg) { if (lane_id() == 0) R.sc->key[127] += (1.0f - wagg); }
+__device__ __forceinline__ void mrg_composite(MergeRay& R, int marcher, int flags, float wagg, float fT, float* __restrict__ rgb, float* __restrict__ depth_o,
+                                              float* __restrict__ wsum_o, float* __restrict__ final_T) {
+    const int l = lane_id();
+    const MergePairScratch& sc = *R.sc;
+    const float* w = sc.key;
+    const int Mm = (marcher == 0 || (flags & 1)) ? 128 : 127;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f}, wacc = 0.f;
+#pragma unroll
+    for (int i = l; i < 128; i += 64) {
+        if (i < Mm) {
+            const float wi = w[i];
+            wacc += wi;
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                float v = c < 3 ? sc.col[c][i] : sc.z[i];
+                if (marcher == 1 && i < 127) v = (v + (c < 3 ? sc.col[c][i + 1] : sc.z[i + 1])) / 2.f;
+                acc[c] += wi * v;
+            }
+        }
+    }
+    float out[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) out[c] = wave_sum_f32(acc[c]);
+    const float wtot = wave_sum_f32(wacc);
+    if (marcher == 1) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            if (flags & 4) out[c] = out[c] + 1.0f - wagg;
+            out[c] = out[c] * 2.0f - 1.0f;
+        }
+    }
+    if (l == 0 && R.live) {
+        rgb[R.r * 3 + 0] = out[0]; rgb[R.r * 3 + 1] = out[1]; rgb[R.r * 3 + 2] = out[2];
+        depth_o[R.r] = out[3];
+        if (wsum_o) wsum_o[R.r] = wtot;
+        if (final_T) final_T[R.r] = fT;
+    }
+}
+
+// merge_composite_kernel<128> at S1 = S2 = 64, two rays per wave.  gfx950: see DESIGN.md 5.5 for the register count (at most 64, no scratch).
+__global__ __launch_bounds__(256, 8) void merge_composite_pair_kernel(const float* __restrict__ rgbs1, const float* __restrict__ t1,
+                                                                     const float* __restrict__ rgbs2, const float* __restrict__ t2,
+                                                                     float* __restrict__ rgb, float* __restrict__ depth_o, float* __restrict__ wsum_o,
+                                                                     float* __restrict__ final_T, int32_t* __restrict__ perm, const int32_t* __restrict__ perm2,
+                                                                     int64_t rays, int marcher, int flags, float density_bias, float cut_thr) {
+    __shared__ MergePairScratch scratch[PAIR_RAYS_PER_BLOCK];
+    const int wv = threadIdx.x >> 6;
+    const int64_t r0 = ((int64_t)blockIdx.x * (PAIR_RAYS_PER_BLOCK / 2) + wv) * 2;
+    if (r0 >= rays) return;
+    MergeRay A, B;
+    A.sc = &scratch[2 * wv]; A.r = r0; A.live = true;
+    B.sc = &scratch[2 * wv + 1]; B.live = r0 + 1 < rays; B.r = B.live ? r0 + 1 : r0;
+    mrg_load(A, rgbs1, t1, rgbs2, t2, perm2, perm != nullptr); mrg_load(B, rgbs1, t1, rgbs2, t2, perm2, perm != nullptr);
+    mrg_park(A); mrg_park(B);
+    wave_sync();
+    mrg_search(A); mrg_search(B);
+    wave_sync();                                    // last[] is zeroed before the max-scatter
+    mrg_scatter_last(A); mrg_scatter_last(B);
+    wave_sync();
+    const bool slowA = mrg_ranks(A), slowB = mrg_ranks(B);
+    if (slowA) stable_ranks_n<2>(A.sc->key, 128, A.rank);      // per ray: the other one keeps its merge ranks
+    if (slowB) stable_ranks_n<2>(B.sc->key, 128, B.rank);
+    wave_sync();                                    // last[] is read before z is written over it
+    mrg_scatter(A, perm); mrg_scatter(B, perm);
+    wave_sync();                                    // the keys are read before the weights are written over them
+    float fTA, waA, fTB, waB;
+    mrg_march(A, marcher, flags, density_bias, cut_thr, fTA, waA); mrg_march(B, marcher, flags, density_bias, cut_thr, fTB, waB);
+    wave_sync();
+    if (marcher == 0 && (flags & 2)) { mrg_last_back(A, waA); mrg_last_back(B, waB); }
+    wave_sync();
+    mrg_composite(A, marcher, flags, waA, fTA, rgb, depth_o, wsum_o, final_T); mrg_composite(B, marcher, flags, waB, fTB, rgb, depth_o, wsum_o, final_T);
+}
+
 inline int ray_blocks(int64_t rays) { return (int)cdiv64(rays, RAYS_PER_BLOCK); }
+inline int pair_blocks(int64_t rays) { return (int)cdiv64(rays, PAIR_RAYS_PER_BLOCK); }
 
 }  // namespace
 
@@ -927,7 +1335,10 @@ TDGP_API int tdgp_importance_from_coarse(const float* rgbs_coarse, const float* 
     TDGP_CHECK(marcher == 0 || marcher == 1, TDGP_EINVAL, "importance_from_coarse: unknown ray marcher %d", marcher);
     TDGP_FAULT_CHECK("importance_from_coarse");
     if (rays == 0) return TDGP_OK;
-    if (S <= 128 && N <= 128)
+    if (S == 64 && N == 64)         // the generator's 64 + 64: two rays per wave
+        TDGP_LAUNCH("importance_from_coarse_kernel", importance_from_coarse_pair_kernel, dim3(pair_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, sdist,
+                    u_fine, tdist_fine, sdist_fine, inds, fine_perm, rays, marcher, flags, density_bias, cut_threshold, t_near, t_far);
+    else if (S <= 128 && N <= 128)
         TDGP_LAUNCH("importance_from_coarse_kernel", importance_from_coarse_kernel<128>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, sdist,
                            u_fine, tdist_fine, sdist_fine, inds, fine_perm, rays, S, N, marcher, flags, density_bias, cut_threshold, t_near, t_far);
     else if (S <= MAXS && N <= MAXS)
@@ -948,7 +1359,10 @@ TDGP_API int tdgp_merge_composite(const float* rgbs_coarse, const float* t_coars
     TDGP_CHECK(marcher == 0 || marcher == 1, TDGP_EINVAL, "merge_composite: unknown ray marcher %d", marcher);
     TDGP_FAULT_CHECK("merge_composite");
     if (rays == 0) return TDGP_OK;
-    if (S1 + S2 <= 128)
+    if (S1 == 64 && S2 == 64)       // the generator's 64 + 64: two rays per wave
+        TDGP_LAUNCH("merge_composite_kernel", merge_composite_pair_kernel, dim3(pair_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, t_coarse, rgbs_fine,
+                    t_fine, rgb, depth, wsum, final_T, perm, fine_perm, rays, marcher, flags, density_bias, cut_threshold);
+    else if (S1 + S2 <= 128)
         TDGP_LAUNCH("merge_composite_kernel", merge_composite_kernel<128>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, t_coarse, S1,
                            rgbs_fine, t_fine, S2, rgb, depth, wsum, final_T, perm, fine_perm, rays, marcher, flags, density_bias, cut_threshold);
     else if (S1 + S2 <= 192)        // BASELINE configs[4]: 96 + 96 samples -- three lane slots and 6.2 KB of scratch per wave instead of four and 8.2 KB

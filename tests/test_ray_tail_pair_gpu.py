@@ -1,0 +1,221 @@
+"""The 64 + 64 pair forms of the per-ray tail (csrc/sampling.hip: importance_from_coarse_pair_kernel, merge_composite_pair_kernel -- a wave
+owns rays 2w and 2w + 1) against the staged op chain, which they do not touch:
+
+    tdgp_ray_march -> tdgp_sample_importance -> s-to-t conversion and stable sort -> tdgp_unify_samples -> tdgp_ray_march
+
+Every output bit for bit (torch.equal on the raw tensors): tfine, sfine, inds, fine_perm, rgb, depth, wsum, final_T, perm.  The chain has no
+`wsum` of its own: it is the chain's merged weights summed in the order the kernels document (lane l adds its samples l and 64 + l, then the
+pairwise tree of the DPP wave sum) -- fp32 additions of the chain's values, so still an equality of bits.
+
+Shapes: ray counts around a pair and a block of 8 rays (1, 2, 3, 8, 9) and many blocks with an odd tail (1027); both marchers; every flag;
+planted rays that take a slow path or a degenerate pdf, each at an even and at an odd position of a pair next to an ordinary partner; and the
+neighbouring sizes (64, 32), (32, 64), (96, 96), which keep the one-ray kernels."""
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+DEV = 'cuda:0'
+T_NEAR, T_FAR = 0.75, 1.25
+RAY_COUNTS = (1, 2, 3, 8, 9, 1027)
+# (marcher, flags): bit0 use_inf_depth, bit1 last_back (classical), bit2 white_back (mip), bit3 relu clamp (classical)
+FLAG_CASES = [('classical', 0), ('classical', 1), ('classical', 2), ('classical', 1 | 8), ('classical', 1 | 2 | 8), ('mip', 0), ('mip', 1), ('mip', 1 | 4)]
+
+
+@pytest.fixture(scope='module')
+def native():
+    tdgp = importlib.import_module('3dgp_amd')
+    assert torch.cuda.is_available(), 'GPU tests need a GPU'
+    tdgp._lib.load()
+    return tdgp
+
+
+def T(a, dtype=torch.float32):
+    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(DEV)
+
+
+def s2t(s):
+    return s * T_FAR + (1 - s) * T_NEAR
+
+
+def make_inputs(tdgp, rs, rays, S, N, marcher):
+    """Stratified coarse depths, coarse and fine colours with sigma in [-4, 6], fine draws (the fine colours in DRAW order)."""
+    rend = tdgp.renderer.ImportanceRenderer(marcher)
+    sd = rend.sample_stratified(torch.zeros(1, rays, 3, device=DEV), 0.0, 1.0, S, noise=T(rs.rand(1, rays, S, 1))).reshape(rays, S)
+    rgbs_c, rgbs_f = rs.randn(rays, S, 4).astype(np.float32), rs.randn(rays, N, 4).astype(np.float32)
+    rgbs_c[..., 3] = rs.uniform(-4, 6, (rays, S))
+    rgbs_f[..., 3] = rs.uniform(-4, 6, (rays, N))
+    return dict(sd=sd, rgbs_c=rgbs_c, rgbs_f=rgbs_f, u2=rs.rand(rays, N).astype(np.float32))
+
+
+def wave_order_sum(w):
+    """sum over a ray's <= 128 weights as merge_composite does it: lane l adds samples l and 64 + l, then the DPP scan's pairwise tree."""
+    rays, M = w.shape
+    x = torch.zeros(rays, 128, device=w.device)
+    x[:, :M] = w
+    x = (torch.zeros(rays, 64, device=w.device) + x[:, :64]) + x[:, 64:]
+    while x.shape[1] > 1:
+        x = x[:, 0::2] + x[:, 1::2]
+    return x.reshape(rays)
+
+
+def chain(tdgp, inp, marcher, flags, cut=0.0, bias=0.0, t_fine=None):
+    """The staged op chain.  `t_fine` (draw-order fine depths handed in) skips the importance stage: the merge-only form."""
+    L = tdgp._lib
+    mid = 0 if marcher == 'classical' else 1
+    sd, rgbs_c, rgbs_f = inp['sd'], T(inp['rgbs_c']), T(inp['rgbs_f'])
+    rays, S = sd.shape
+    N = rgbs_f.shape[1]
+    st = L.stream_of(sd)
+    cc, dc = rgbs_c[..., :3].contiguous(), rgbs_c[..., 3].contiguous()
+    cf, df = rgbs_f[..., :3].contiguous(), rgbs_f[..., 3].contiguous()
+    f32 = lambda *s: torch.empty(*s, device=DEV)                                   # noqa: E731
+    i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=DEV)                # noqa: E731
+    out = {}
+    if t_fine is None:
+        Wn = S if (mid == 0 or (flags & 1)) else S - 1
+        w, junk = f32(rays, Wn), [f32(rays, 3), f32(rays), f32(rays)]
+        L.call('tdgp_ray_march', cc.data_ptr(), dc.data_ptr(), sd.data_ptr(), junk[0].data_ptr(), junk[1].data_ptr(), w.data_ptr(), junk[2].data_ptr(), rays, S, 3,
+               mid, flags, bias, cut, st)
+        sfine, inds, below, above = f32(rays, N), i32(rays, N), i32(rays, N), i32(rays, N)
+        L.call('tdgp_sample_importance', sd.data_ptr(), w.data_ptr(), T(inp['u2']).data_ptr(), sfine.data_ptr(), inds.data_ptr(), below.data_ptr(), above.data_ptr(),
+               None, rays, S, Wn, N, mid, st)
+        t_fine = s2t(sfine)
+        srt = torch.sort(t_fine, dim=1, stable=True)                               # stable: by (depth, draw index)
+        out.update(sfine=sfine, inds=inds, tfine=srt.values.contiguous(), fine_perm=srt.indices.to(torch.int32))
+    td = s2t(sd)
+    M = S + N
+    d, c, s, perm = f32(rays, M), f32(rays, M, 3), f32(rays, M), i32(rays, M)
+    L.call('tdgp_unify_samples', td.data_ptr(), cc.data_ptr(), dc.data_ptr(), S, t_fine.data_ptr(), cf.data_ptr(), df.data_ptr(), N, d.data_ptr(), c.data_ptr(),
+           s.data_ptr(), perm.data_ptr(), rays, 3, st)
+    Mw = M if (mid == 0 or (flags & 1)) else M - 1
+    rgb, dep, w2, fT = f32(rays, 3), f32(rays), f32(rays, Mw), f32(rays)
+    L.call('tdgp_ray_march', c.data_ptr(), s.data_ptr(), d.data_ptr(), rgb.data_ptr(), dep.data_ptr(), w2.data_ptr(), fT.data_ptr(), rays, M, 3, mid, flags, bias,
+           cut, st)
+    out.update(perm=perm, rgb=rgb, depth=dep, final_T=fT)
+    if M <= 128:
+        out['wsum'] = wave_order_sum(w2)
+    return out
+
+
+def fused(tdgp, inp, marcher, flags, cut=0.0, bias=0.0, t_fine=None):
+    """tdgp_importance_from_coarse + tdgp_merge_composite, every optional output asked for.  With `t_fine` only the merge, on those lists as they are."""
+    L = tdgp._lib
+    mid = 0 if marcher == 'classical' else 1
+    sd, rgbs_c, rgbs_f = inp['sd'], T(inp['rgbs_c']), T(inp['rgbs_f'])
+    rays, S = sd.shape
+    N = rgbs_f.shape[1]
+    st = L.stream_of(sd)
+    out = {}
+    fine_perm = None
+    if t_fine is None:
+        tfine, sfine = torch.empty(rays, N, device=DEV), torch.empty(rays, N, device=DEV)
+        inds, fine_perm = torch.empty(rays, N, dtype=torch.int32, device=DEV), torch.empty(rays, N, dtype=torch.int32, device=DEV)
+        L.call('tdgp_importance_from_coarse', rgbs_c.data_ptr(), sd.data_ptr(), T(inp['u2']).data_ptr(), tfine.data_ptr(), sfine.data_ptr(), inds.data_ptr(),
+               fine_perm.data_ptr(), rays, S, N, mid, flags, bias, cut, T_NEAR, T_FAR, st)
+        out.update(tfine=tfine, sfine=sfine, inds=inds, fine_perm=fine_perm)
+        rgbs_f = torch.gather(rgbs_f, 1, fine_perm.long()[..., None].expand(rays, N, 4)).contiguous()      # the field pass runs on the sorted samples
+        t_fine = tfine
+    td = s2t(sd)
+    rgb, dep, wsum, fT = (torch.empty(rays, n, device=DEV) for n in (3, 1, 1, 1))
+    perm = torch.empty(rays, S + N, dtype=torch.int32, device=DEV)
+    L.call('tdgp_merge_composite', rgbs_c.data_ptr(), td.data_ptr(), S, rgbs_f.data_ptr(), t_fine.data_ptr(), N, rgb.data_ptr(), dep.data_ptr(), wsum.data_ptr(),
+           fT.data_ptr(), perm.data_ptr(), L.ptr(fine_perm), rays, mid, flags, bias, cut, st)
+    out.update(rgb=rgb, depth=dep.reshape(rays), wsum=wsum.reshape(rays), final_T=fT.reshape(rays), perm=perm)
+    return out
+
+
+def assert_same_bits(got, want, tag):
+    for k, ref in want.items():
+        assert got[k].dtype == ref.dtype and got[k].shape == ref.shape, (tag, k, got[k].dtype, ref.dtype, got[k].shape, ref.shape)
+        if not torch.equal(got[k], ref):
+            bad = (got[k] != ref).reshape(ref.shape[0], -1).any(1).nonzero().reshape(-1)[:8].tolist()
+            raise AssertionError(f'{tag}: `{k}` differs from the op chain on rays {bad}')
+
+
+@pytest.mark.parametrize('marcher,flags', FLAG_CASES)
+def test_pair_forms_equal_op_chain(native, marcher, flags):
+    """S = N = 64 at every ray count and flag: all nine outputs equal the chain's bits; with and without a cut threshold and a density bias."""
+    rs = np.random.RandomState(640 + 10 * flags + (marcher == 'mip'))
+    for rays in RAY_COUNTS:
+        inp = make_inputs(native, rs, rays, 64, 64, marcher)
+        for cut, bias in ((0.0, 0.0), (0.3, 0.5 if marcher == 'mip' else 0.0)):
+            want, got = chain(native, inp, marcher, flags, cut, bias), fused(native, inp, marcher, flags, cut, bias)
+            assert set(want) == {'tfine', 'sfine', 'inds', 'fine_perm', 'rgb', 'depth', 'wsum', 'final_T', 'perm'}
+            assert_same_bits(got, want, f'{marcher} flags={flags} rays={rays} cut={cut}')
+
+
+@pytest.mark.parametrize('marcher', ['classical', 'mip'])
+def test_planted_rays_in_a_pair(native, marcher):
+    """(a) two equal fine keys from duplicate draws (the bitonic network), (c) an all-zero-density ray (uniform pdf), (d) all density in one
+    sample (the fine samples crowd one bin): each at an even and at an odd position of its pair, its partner an ordinary ray."""
+    rs = np.random.RandomState(7 + (marcher == 'mip'))
+    rays = 16
+    inp = make_inputs(native, rs, rays, 64, 64, marcher)
+    for r in (2, 5):
+        inp['u2'][r, 5] = inp['u2'][r, 2]
+        inp['u2'][r, 63] = inp['u2'][r, 0]
+    for r in (6, 9):
+        inp['rgbs_c'][r, :, 3] = -100.0
+    for r in (10, 13):
+        inp['rgbs_c'][r, :, 3] = -100.0
+        inp['rgbs_c'][r, 20 + r, 3] = 2000.0
+    want, got = chain(native, inp, marcher, 1), fused(native, inp, marcher, 1)
+    ties = (want['tfine'][:, 1:] == want['tfine'][:, :-1]).any(1).cpu().numpy()
+    assert ties[2] and ties[5] and not ties[[3, 4]].any(), ties                      # exactly one ray of each of those pairs collides
+    crowd = (want['inds'][:, :, None] == want['inds'][:, None, :]).sum(2).max(1).values.cpu().numpy()      # most draws sharing one bin, per ray
+    assert crowd[10] >= 16 and crowd[13] >= 16 and (crowd[[11, 12]] < 16).all(), crowd
+    assert_same_bits(got, want, f'planted rays, {marcher}')
+
+
+@pytest.mark.parametrize('marcher', ['classical', 'mip'])
+def test_unsorted_list_in_a_pair(native, marcher):
+    """(b) tdgp_merge_composite handed lists that are not ascending (the brute-force stable rank): a fine list at an even and at an odd position,
+    a coarse list, and a pair whose two rays both are; every partner ascending.  Ties across and inside the lists."""
+    rs = np.random.RandomState(11 + (marcher == 'mip'))
+    rays = 13
+    inp = make_inputs(native, rs, rays, 64, 64, marcher)
+    t2 = np.sort(rs.uniform(T_NEAR, T_FAR, (rays, 64)).astype(np.float32), axis=1)
+    t2[:, 9] = s2t(inp['sd']).cpu().numpy()[:, 4]
+    t2.sort(axis=1)
+    for r in (2, 5, 8, 9):
+        t2[r] = rs.permutation(t2[r])
+    t2[5, 3] = t2[5, 7]
+    sd = inp['sd'].cpu().numpy()
+    sd[11] = sd[11, ::-1].copy()
+    inp['sd'] = T(sd)
+    t2 = T(t2)
+    want, got = chain(native, inp, marcher, 1, t_fine=t2), fused(native, inp, marcher, 1, t_fine=t2)
+    assert set(want) == {'rgb', 'depth', 'wsum', 'final_T', 'perm'}
+    assert_same_bits(got, want, f'unsorted lists, {marcher}')
+
+
+@pytest.mark.parametrize('S,N', [(64, 32), (32, 64), (96, 96)])
+def test_neighbouring_sizes_keep_their_kernels(native, S, N):
+    """The sizes next to 64 + 64 stay on the one-ray kernels and equal the chain as before."""
+    rs = np.random.RandomState(S * 100 + N)
+    for marcher, flags in (('classical', 1), ('classical', 2), ('mip', 1 | 4)):
+        for rays in (3, 9):
+            inp = make_inputs(native, rs, rays, S, N, marcher)
+            want, got = chain(native, inp, marcher, flags), fused(native, inp, marcher, flags)
+            assert_same_bits(got, want, f'{S}+{N} {marcher} flags={flags} rays={rays}')
+
+
+@pytest.mark.parametrize('S,N', [(64, 64), (64, 32), (96, 96)])
+def test_one_launch_per_call(native, S, N):
+    """Each entry point is one launch under its profiling label, at 64 + 64 (odd ray count: no second launch for the tail) as at the other sizes."""
+    L = native._lib
+    inp = make_inputs(native, np.random.RandomState(3), 1027, S, N, 'classical')
+    L.profile_enable(True)
+    try:
+        fused(native, inp, 'classical', 1)
+        torch.cuda.synchronize()
+        rep = L.profile_report()
+    finally:
+        L.profile_enable(False)
+    launches = {k: v['launches'] for k, v in rep.items()}
+    assert launches.get('importance_from_coarse_kernel') == 1 and launches.get('merge_composite_kernel') == 1, launches
+    assert set(launches) == {'importance_from_coarse_kernel', 'merge_composite_kernel'}, launches
