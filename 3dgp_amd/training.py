@@ -205,7 +205,7 @@ def maybe_blur(img, blur_sigma):
 class StyleGAN2Loss:
     def __init__(self, G, D, device, r1_gamma=10.0, patch_cfg=None, use_depth=False, adv_loss_type='non_saturating', blur_init_sigma=0, blur_fade_kimg=0,
                  blur_real_depth_sigma=0.0, logits_clamp_val=1e7, learn_camera_dist=False, camera_reg=None, kd_weight=0.0, kd_anneal_kimg=100000,
-                 kd_loss_type='l2', synthesis_kwargs=None):
+                 kd_loss_type='l2', synthesis_kwargs=None, augment_pipe=None):
         if learn_camera_dist and getattr(G.synthesis, 'camera_adaptor', None) is None:
             raise RuntimeError('learn_camera_dist=True needs a generator built with cfg.camera_adaptor')
         self.G, self.D, self.device = G, D, device
@@ -224,6 +224,7 @@ class StyleGAN2Loss:
         self.camera_reg = camera_reg if learn_camera_dist else None
         if self.camera_reg is not None and self.camera_reg.any_enabled and self.camera_reg.prior is None:
             raise RuntimeError('camera_reg needs the camera prior (CameraRegConfig.prior)')
+        self.augment_pipe = augment_pipe               # loss.py:97-98: an augment.AugmentPipe applied to everything the discriminator sees, or None
         self.stats = {}
         self.progressive_update(0)
 
@@ -289,13 +290,15 @@ class StyleGAN2Loss:
         return out, patch_params, camera_params
 
     def run_D(self, img, c, blur_sigma=0, update_emas=False, **kwargs):
-        """loss.py:88-104 (no ADA pipe)."""
+        """loss.py:88-104; the ADA pipe (loss.py:97-98) runs after the depth blur when the loss was given one."""
         img = maybe_blur(img, blur_sigma)
         assert img.shape[1] == 4 or not self.use_depth, f'Wrong shape: {img.shape}'
         if self.use_depth:
             blur_size = np.floor(blur_sigma * 3)
             f = torch.arange(-blur_size, blur_size + 1, device=img.device).div(30.0).square().neg().exp2()
             img = torch.cat([img[:, :3], _upfirdn2d.filter2d(img[:, [3]], f / f.sum()), img[:, 4:]], dim=1)
+        if self.augment_pipe is not None:
+            img = self.augment_pipe(img, num_color_channels=self.G.img_channels)
         kwargs.pop('camera_angles', None)                               # camera_cond is off in every 3dgp config
         return self.D(img, c, update_emas=update_emas, **kwargs)
 
@@ -357,6 +360,8 @@ class StyleGAN2Loss:
             do_Dkd = self.D_kd_weight > 0 and phase in ['Dmain', 'Dall']
             real_logits, real_feats = self.run_D(real_img_tmp, real_data.c, blur_sigma=blur_sigma, patch_params=patch_params, predict_feat=do_Dkd)
             self.stats['Loss/scores/real'] = real_logits.detach()
+            if self.augment_pipe is not None:                              # the controller's statistic: no host read here
+                self.augment_pipe.accumulate_signs(real_logits)
             loss_Dreal = 0.0
             if phase in ['Dmain', 'Dall']:
                 if self.adv_loss_type == 'non_saturating':
@@ -390,6 +395,34 @@ class StyleGAN2Loss:
                 loss_Dr1 = r1_penalty * (self.r1_gamma / 2)
                 self.stats['Loss/D/r1_penalty'] = r1_penalty.detach()
             (loss_Dreal + loss_Dr1 + loss_Dkd).mean().mul(gain).backward()
+
+
+class AdaController:
+    """training_loop.py:373-376: every `interval` batches the mean sign of the real logits is held against `target` and the pipe's strength
+    moves by a fixed step, p <- max(p + sign(mean - target) * batch_size * interval / (kimg * 1000), 0).  The loss adds `real_logits.sign()`
+    to the pipe's device-side (sum, count) pair in every phase that runs the real branch (training_loop.py:355's collector); `step` reads the
+    pair -- the only device-to-host copy of the augmentation path, and nothing is read outside `interval` -- all-reduces it across the ranks
+    when there is a world, and clears it."""
+
+    def __init__(self, augment_pipe, target, interval=4, kimg=500):
+        self.augment_pipe, self.target, self.interval, self.kimg = augment_pipe, float(target), int(interval), float(kimg)
+
+    def step(self, batch_idx, batch_size, world=None):
+        """-> the new p, or None when nothing was due (or no real branch has run since the last step)."""
+        pipe = self.augment_pipe
+        if batch_idx % self.interval != 0 or pipe.ada_stats is None:
+            return None
+        acc, pipe.ada_stats = pipe.ada_stats, None
+        if world is not None and world > 1:
+            import torch.distributed as dist
+            if dist.is_initialized():
+                dist.all_reduce(acc)
+        total, count = (float(v) for v in acc.tolist())
+        mean = total / count if count > 0 else 0.0
+        adjust = float(np.sign(mean - self.target)) * (batch_size * self.interval) / (self.kimg * 1000)
+        with torch.no_grad():
+            pipe.p.copy_((pipe.p + adjust).max(torch.zeros_like(pipe.p)))
+        return float(pipe.p)
 
 
 def optimizer_step(module, opt, world=None, grad_clip=None):
@@ -461,7 +494,7 @@ def _split(group, n):
     return [TensorGroup(**{k: parts[k][i] for k in keys}) for i in range(count)]
 
 
-def train_iteration(loss, phases, real_data, all_gen_data, batch_idx, cur_nimg, batch_size, batch_gpu, world=None, grad_clip=None):
+def train_iteration(loss, phases, real_data, all_gen_data, batch_idx, cur_nimg, batch_size, batch_gpu, world=None, grad_clip=None, ada=None):
     """training_loop.py:319-347: every phase whose interval divides `batch_idx` zeroes its gradients, accumulates them over the
     rank's sub-batches of `batch_gpu`, exchanges them (flat all-reduce) and steps.  `all_gen_data` holds `len(phases) * batch_size`
     latent / camera samples, one `batch_size` slice per phase.  Returns the names of the phases that ran."""
@@ -477,4 +510,6 @@ def train_iteration(loss, phases, real_data, all_gen_data, batch_idx, cur_nimg, 
         clip = grad_clip if phase['name'] in ('Gmain', 'Gall', 'Greg_pl') else None
         optimizer_step(phase['module'], phase['opt'], world=world, grad_clip=clip)
         ran.append(phase['name'])
+    if ada is not None:                                                    # training_loop.py:373-376
+        ada.step(batch_idx, batch_size, world=world)
     return ran

@@ -219,3 +219,20 @@ def load_exported(path):
     if missing:
         raise KeyError(f'exported checkpoint lacks {len(missing)} tensors the generator forward reads, e.g. {missing[:3]}')
     return cfg, OrderedDict((k, sd[k]) for k in spec)
+
+
+def load_exported_augment_pipe(path):
+    """(constructor arguments, state dict) of the snapshot's `augment_pipe` entry as tools/export_reference_checkpoint.py wrote it, or None
+    when the snapshot had none.  `augment.AugmentPipe(**kw)` followed by `load_numpy_state_dict`-style `load_state_dict` resumes it."""
+    import json
+    import os
+    jp, zp = os.path.join(path, 'augment_pipe.json'), os.path.join(path, 'augment_pipe.npz')
+    if not (os.path.exists(jp) and os.path.exists(zp)):
+        return None
+    kw = json.load(open(jp))
+    with np.load(zp) as z:
+        sd = OrderedDict((k, z[k]) for k in z.files)
+    missing = [k for k in ('p', 'Hz_geom', 'Hz_fbank') if k not in sd]
+    if missing:
+        raise KeyError(f'exported augment_pipe lacks {missing}')
+    return kw, sd

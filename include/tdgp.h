@@ -528,6 +528,37 @@ int     tdgp_pr_member(const uint16_t* probes, const float* probe_norms, int64_t
 int64_t tdgp_moments_workspace_bytes(int64_t n, int F);
 int     tdgp_moments_add(const float* rows, int64_t n, int F, double* s1, double* s2, void* workspace, int64_t workspace_bytes, tdgp_stream_t stream);
 
+/* ADA augmentation pipe (src/training/augment.py of the reference), csrc/augment.hip.  All tensors fp32, contiguous, NCHW.
+ * tdgp_augment_params: every per-sample parameter in one launch.  cfg: TDGP_AUGMENT_CFG_FLOATS floats on the HOST, the constructor's
+ *   arguments in its order (xflip, rotate90, xint, xint_max, scale, rotate, aniso, xfrac, scale_std, rotate_max, aniso_std, xfrac_std,
+ *   brightness, contrast, lumaflip, hue, saturation, brightness_std, contrast_std, hue_max, saturation_std, imgfilter, imgfilter_bands[4],
+ *   imgfilter_std, noise, cutout, noise_std, cutout_size).  p: the strength, one float on the device.  Either `uniforms`
+ *   [B, TDGP_AUGMENT_UNIFORMS] in [0, 1) and `normals` [B, TDGP_AUGMENT_NORMALS] (device), or use_percentile != 0 and `percentile`: the
+ *   reference's debug_percentile (every draw replaced by that quantile of its distribution; the post-rotation is zero).
+ *   Outputs (device; a null pointer skips that group): G_inv [B,3,3] pixel_out -> pixel_in, C [B,4,4], gains [B,4] of the band filter,
+ *   noise_sigma [B], cutout [B,4] = (size_x, size_y, centre_x, centre_y).  Plain fp32 in the reference's order of operations.
+ *   num_channels: hue and saturation are left out for a one-channel image.
+ * tdgp_augment_geom: y = the geometric stage (margins over the whole batch, reflect pad, x2 upsampling with f, bilinear sampling through
+ *   G_inv with zeros outside the padded image, x2 downsampling with f, crop) in one kernel; f: the 12 normalised low-pass taps (device).
+ *   G_inv rows 0-1 are used (affine).  2 <= H, W <= 8192, B <= 65535.  Nothing is read back, no intermediate image is stored.
+ * tdgp_augment_geom_adj: dx = the adjoint of the same operator applied to dy.  No atomics: the same bytes on every run.
+ *   workspace: tdgp_augment_geom_adj_workspace_bytes bytes (-1 for a refused shape), 4-byte aligned, caller-owned.
+ * tdgp_augment_color: y[:, :ncc] = C[:, :3, :3] x[:, :ncc] + C[:, :3, 3] (ncc = 3), or the scalar form of one colour channel (ncc = 1);
+ *   the other channels pass through; then + noise * noise_sigma[b] (noise [B,C,H,W] or null), then the cutout mask (cutout [B,4] or null).
+ *   Cmat null: no matrix.  transposed != 0 uses the transposed 3x3; with use_bias = 0 and no noise that is the adjoint.  x == y is allowed. */
+#define TDGP_AUGMENT_CFG_FLOATS 31
+#define TDGP_AUGMENT_UNIFORMS 29
+#define TDGP_AUGMENT_NORMALS 12
+int     tdgp_augment_params(const float* cfg, const float* p, int B, int H, int W, int num_channels, const float* uniforms, const float* normals,
+                            int use_percentile, float percentile, float* G_inv, float* Cmat, float* gains, float* noise_sigma, float* cutout,
+                            tdgp_stream_t stream);
+int     tdgp_augment_geom(const float* x, const float* G_inv, const float* f, float* y, int B, int C, int H, int W, tdgp_stream_t stream);
+int64_t tdgp_augment_geom_adj_workspace_bytes(int B, int C, int H, int W);
+int     tdgp_augment_geom_adj(const float* dy, const float* G_inv, const float* f, float* dx, int B, int C, int H, int W, void* workspace,
+                              int64_t workspace_bytes, tdgp_stream_t stream);
+int     tdgp_augment_color(const float* x, float* y, const float* Cmat, int transposed, int use_bias, const float* noise, const float* noise_sigma,
+                           const float* cutout, int B, int C, int H, int W, int num_color_channels, tdgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

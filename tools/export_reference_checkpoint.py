@@ -102,6 +102,22 @@ def export(G, out_dir):
     return cfg, sd
 
 
+AUGMENT_ARGS = ('xflip', 'rotate90', 'xint', 'xint_max', 'scale', 'rotate', 'aniso', 'xfrac', 'scale_std', 'rotate_max', 'aniso_std', 'xfrac_std',
+                'brightness', 'contrast', 'lumaflip', 'hue', 'saturation', 'brightness_std', 'contrast_std', 'hue_max', 'saturation_std',
+                'imgfilter', 'imgfilter_bands', 'imgfilter_std', 'noise', 'cutout', 'noise_std', 'cutout_size')
+
+
+def export_augment_pipe(pipe, out_dir):
+    """The snapshot's `augment_pipe` entry: out_dir/augment_pipe.json (the constructor's arguments, read off the module's attributes) and
+    out_dir/augment_pipe.npz (its state dict: p, Hz_geom, Hz_fbank) -- what `3dgp_amd.weights.load_exported_augment_pipe` reads."""
+    os.makedirs(out_dir, exist_ok=True)
+    kw = {k: (list(getattr(pipe, k)) if k == 'imgfilter_bands' else float(getattr(pipe, k))) for k in AUGMENT_ARGS}
+    sd = {k: v.detach().cpu().numpy() for k, v in pipe.state_dict().items()}
+    np.savez(os.path.join(out_dir, 'augment_pipe.npz'), **sd)
+    json.dump(kw, open(os.path.join(out_dir, 'augment_pipe.json'), 'w'), indent=1)
+    return kw, sd
+
+
 def main():
     sys.path.insert(0, REF)
     pkl, out_dir = sys.argv[1], sys.argv[2]
@@ -110,6 +126,9 @@ def main():
     G = data['G_ema'] if isinstance(data, dict) else data
     cfg, sd = export(G.eval(), out_dir)
     print(f'{len(sd)} tensors, {sum(v.size for v in sd.values()) / 1e6:.1f} M parameters -> {out_dir}')
+    if isinstance(data, dict) and data.get('augment_pipe') is not None:
+        kw, _ = export_augment_pipe(data['augment_pipe'], out_dir)
+        print(f'augment_pipe: p = {float(data["augment_pipe"].p):.4f}, ' + ', '.join(k for k, v in kw.items() if k in AUGMENT_ARGS[:3] + AUGMENT_ARGS[4:8] + AUGMENT_ARGS[12:17] and v > 0))
 
 
 if __name__ == '__main__':
