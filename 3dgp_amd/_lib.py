@@ -7,7 +7,7 @@ product path raises; there is no CPU or PyTorch fallback behind these entry poin
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
 
 import torch
 
@@ -86,6 +86,10 @@ _PROTOTYPES = {
     'tdgp_augment_geom_adj_workspace_bytes': (c_int64, [c_int, c_int, c_int, c_int]),
     'tdgp_augment_geom_adj': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, c_int64, P]),
     'tdgp_augment_color': (c_int, [P, P, P, c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    'tdgp_grads_pack': (c_int, [P, P, c_int, c_int64, c_int, P, c_int64, P]),
+    'tdgp_grads_sanitise_norm': (c_int, [P, c_int64, c_int, c_int, P, c_int64, P, P]),
+    'tdgp_adam_step': (c_int, [P, P, c_int, c_int64, c_int, P, c_int64, P, c_double, c_double, c_double, c_double, P]),
+    'tdgp_ema_update': (c_int, [P, c_int, c_int64, c_int, c_double, P]),
 }
 EXPORTS = tuple(_PROTOTYPES)
 

@@ -494,10 +494,12 @@ def _split(group, n):
     return [TensorGroup(**{k: parts[k][i] for k in keys}) for i in range(count)]
 
 
-def train_iteration(loss, phases, real_data, all_gen_data, batch_idx, cur_nimg, batch_size, batch_gpu, world=None, grad_clip=None, ada=None):
+def train_iteration(loss, phases, real_data, all_gen_data, batch_idx, cur_nimg, batch_size, batch_gpu, world=None, grad_clip=None, ada=None, step_tail=None):
     """training_loop.py:319-347: every phase whose interval divides `batch_idx` zeroes its gradients, accumulates them over the
     rank's sub-batches of `batch_gpu`, exchanges them (flat all-reduce) and steps.  `all_gen_data` holds `len(phases) * batch_size`
-    latent / camera samples, one `batch_size` slice per phase.  Returns the names of the phases that ran."""
+    latent / camera samples, one `batch_size` slice per phase.  Returns the names of the phases that ran.
+    `step_tail=True` runs exchange, sanitising, clipping and Adam through `step_tail.FusedStepTail` (one per phase, kept in the phase's
+    dict) instead of `optimizer_step`; the default is the eager tail."""
     ran = []
     for phase, gen_data in zip(phases, _split(all_gen_data, batch_size)):
         if batch_idx % phase['interval'] != 0:
@@ -508,7 +510,13 @@ def train_iteration(loss, phases, real_data, all_gen_data, batch_idx, cur_nimg, 
             loss.accumulate_gradients(phase=phase['name'], real_data=r, gen_data=g, gain=phase['interval'], cur_nimg=cur_nimg)
         phase['module'].requires_grad_(False)
         clip = grad_clip if phase['name'] in ('Gmain', 'Gall', 'Greg_pl') else None
-        optimizer_step(phase['module'], phase['opt'], world=world, grad_clip=clip)
+        if step_tail:
+            if 'step_tail' not in phase:
+                from .step_tail import FusedStepTail
+                phase['step_tail'] = FusedStepTail(phase['module'], phase['opt'])
+            phase['step_tail'].step(world=world, grad_clip=clip)
+        else:
+            optimizer_step(phase['module'], phase['opt'], world=world, grad_clip=clip)
         ran.append(phase['name'])
     if ada is not None:                                                    # training_loop.py:373-376
         ada.step(batch_idx, batch_size, world=world)

@@ -559,6 +559,39 @@ int     tdgp_augment_geom_adj(const float* dy, const float* G_inv, const float* 
 int     tdgp_augment_color(const float* x, float* y, const float* Cmat, int transposed, int use_bias, const float* noise, const float* noise_sigma,
                            const float* cutout, int B, int C, int H, int W, int num_color_channels, tdgp_stream_t stream);
 
+/* Step tail of a training phase (training_loop.py:334-347: gradient exchange, sanitising, clipping, Adam) and the per-batch EMA update
+ * (:357-367), csrc/step_tail.hip.  Multi-tensor kernels: ONE launch covers every tensor, a block works on one chunk of
+ * TDGP_STEP_TAIL_CHUNK elements of one tensor, found through a chunk -> tensor map the caller builds.  All tensors fp32, contiguous,
+ * 4-byte aligned (16-byte accesses where pointer and remaining length allow, scalar ones at ragged heads and tails).  No atomics, no
+ * kernel waits on another: the same bytes on every run.  `chunk` must be TDGP_STEP_TAIL_CHUNK (a caller built against another constant
+ * is refused).
+ * A table is a DEVICE array of int64 words: `rows` rows of num_tensors words each, then num_blocks words "tensor of block b", then
+ * num_blocks words "first element of block b inside its tensor".  Every block's range must lie inside its tensor; the caller guarantees it.
+ *   step table (5 rows): parameter pointer, exp_avg pointer, exp_avg_sq pointer, element count, offset in the flat buffer (elements)
+ *   ema table  (4 rows): source pointer, destination pointer, element count, kind (0: dst <- lerp(src, dst, beta); 1: dst <- src)
+ * The table that changes from step to step (3 rows of num_tensors words, device): gradient pointer; -(lr / (1 - beta1^t)) and
+ *   sqrt(1 - beta2^t) of the tensor's own step count t, each a double's bits.  They come from the host, in Python floats as torch does.
+ * tdgp_grads_pack: flat[off_t + i] = grad_t[i] for every tensor t of the step table; grad_table: row 0 of the per-step table.  Replaces
+ *   torch.cat.
+ * tdgp_grads_sanitise_norm: in place on flat[0 .. total): x / world, then NaN -> 0, +inf -> 1e5, -inf -> -1e5 (the order of
+ *   distributed.allreduce_gradients); block b writes partials[b] = the sum of the fp64 squares of its sanitised fp32 values, summed in fp64
+ *   in a fixed order; a second one-block launch sums the partials in a fixed order and writes norm[0] = sqrt(sum) (fp64).
+ *   num_partials must be ceil(total / chunk).
+ * tdgp_adam_step: torch.optim.Adam's update (no amsgrad, no weight decay, no maximize) of every tensor of the step table with
+ *   g = flat[off_t + i] * c, c = min(1, max_norm / (norm[0] + 1e-6)) (max_norm < 0: c = 1, norm may be null):
+ *   m += (1 - beta1) (g - m); v = beta2 v + (1 - beta2) g g; p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps), the two
+ *   t-dependent factors read per tensor from step_table (all three rows are passed).  flat is not rescaled.  m, v and p are each evaluated in fp64 from the fp32
+ *   operands and rounded once (as is the lerp of tdgp_ema_update).
+ * tdgp_ema_update: every pair of the ema table; beta == 0 turns every kind-0 pair into a bitwise copy. */
+#define TDGP_STEP_TAIL_CHUNK 4096
+int     tdgp_grads_pack(const int64_t* grad_table, const int64_t* table, int num_tensors, int64_t num_blocks, int chunk, float* flat, int64_t total,
+                        tdgp_stream_t stream);
+int     tdgp_grads_sanitise_norm(float* flat, int64_t total, int world, int chunk, double* partials, int64_t num_partials, double* norm,
+                                 tdgp_stream_t stream);
+int     tdgp_adam_step(const int64_t* table, const int64_t* step_table, int num_tensors, int64_t num_blocks, int chunk, const float* flat,
+                       int64_t total, const double* norm, double max_norm, double beta1, double beta2, double eps, tdgp_stream_t stream);
+int     tdgp_ema_update(const int64_t* table, int num_tensors, int64_t num_blocks, int chunk, double beta, tdgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

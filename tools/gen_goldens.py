@@ -1724,6 +1724,7 @@ def main():
     gen_feature_metrics()
     gen_trajectories()
     gen_harness()
+    gen_infinite_sampler()
     gen_synthesis_grad()
     gen_discriminator()
     gen_loss()
@@ -1967,6 +1968,23 @@ def gen_feature_metrics():
     for k in ('seed', 'rows', 'nhood_size', 'kid_set', 'kid_seed', 'kid_num_subsets', 'kid_max_subset_size', 'is_seed', 'is_rows', 'is_classes', 'is_splits'):
         arrays[k] = np.array(gg[k], dtype=np.int64)
     save('feature_metrics', **arrays)
+
+
+INFINITE_SAMPLER_CASES = [(10, seed, rank, 2, window) for seed in (0, 3) for rank in (0, 1) for window in (0.5, 0.0)]
+
+
+def gen_infinite_sampler():
+    """The reference's InfiniteSampler (misc.py:112-143): the first 64 indices of every case (length, seed, rank, replicas, window).  Indices
+    only; tests/test_dataset.py holds 3dgp_amd.dataset.InfiniteSampler against them."""
+    import itertools
+    from src.torch_utils import misc as ref_misc
+    arrays = dict(cases=np.array(INFINITE_SAMPLER_CASES, dtype=np.float64))
+    for k, (n, seed, rank, world, window) in enumerate(INFINITE_SAMPLER_CASES):
+        # (its constructor passes the dataset on to torch.utils.data.Sampler.__init__, which current torch no longer takes: the attributes
+        # it would set are given directly and the reference's own __iter__ runs on them)
+        sampler = types.SimpleNamespace(dataset=list(range(n)), rank=rank, num_replicas=world, shuffle=True, seed=seed, window_size=window)
+        arrays[f'indices_{k}'] = np.array(list(itertools.islice(ref_misc.InfiniteSampler.__iter__(sampler), 64)), dtype=np.int64)
+    save('infinite_sampler', **arrays)
 
 
 def gen_e2e_all():
