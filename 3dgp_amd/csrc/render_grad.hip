@@ -222,8 +222,9 @@ TDGP_API int tdgp_ray_march_grad(const float* colors, const float* densities, co
 // =================================================================================================================================
 namespace {
 
-typedef float fg_f32x16 __attribute__((ext_vector_type(16)));
-constexpr int FG_PITCH = 33;
+// fg_f32x16, FG_PITCH, fg_row_of, fg_wave_sync; and, included again inside the tile loop, stage 1 (geometry + gather) and stage 6 (d_coords and
+// the scatter) -- shared with field_deep.hip's gradient kernel.  This file keeps the two-layer MLP middle (stages 2-5) and its reduction.
+#include "field_grad.inc"
 
 struct FieldGradParams {
     const float* planes;       // [B,3,H,W,F]
@@ -280,68 +281,16 @@ __global__ __launch_bounds__(64 * NW) void triplane_field_grad_kernel(FieldGradP
         const bool valid = gp < p.total;
         const int64_t gpc = valid ? gp : 0;
         const int b = (int)(gpc / p.P);
-        // ---- 1. geometry + gather ------------------------------------------------------------------------------------------
-        const float* cp = p.coords + gpc * 3;
-        const float q[3] = {cp[0] / p.scale, cp[1] / p.scale, cp[2] / p.scale};
-        float tw_[3][4];
-        int to_[3][4];
-        float fr_[3][2];                                      // (tw, tn): fractional position inside the texel cell, per plane
-        int in_[3];                                           // in-range mask of the four taps (bit t), per plane
-        float gsum[16];
-#pragma unroll
-        for (int c = 0; c < 16; c++) gsum[c] = 0.f;
-        float acc3[3][16];
-#pragma unroll
-        for (int pl = 0; pl < 3; pl++) {
-            const float ix = (q[pl == 2 ? 1 : 0] + 1.0f) * sx, iy = (q[pl == 0 ? 1 : 2] + 1.0f) * sy;
-            const float fx = floorf(ix), fy = floorf(iy);
-            const float twx = ix - fx, te = 1.0f - twx, tn = iy - fy, ts = 1.0f - tn;
-            const float cfx = fminf(fmaxf(fx, -2.f), (float)p.W), cfy = fminf(fmaxf(fy, -2.f), (float)p.H);
-            const int x0 = (int)cfx, y0 = (int)cfy;
-            const float wgt[4] = {ts * te, ts * twx, tn * te, tn * twx};
-            const float* plane = p.planes + ((int64_t)b * 3 + pl) * p.H * p.W * p.F;
-            fr_[pl][0] = twx; fr_[pl][1] = tn; in_[pl] = 0;
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                const int x = x0 + (t & 1), y = y0 + (t >> 1);
-                const bool in = valid && x >= 0 && x < p.W && y >= 0 && y < p.H;
-                tw_[pl][t] = in ? wgt[t] : 0.f;
-                to_[pl][t] = in ? (y * p.W + x) * p.F : 0;
-                in_[pl] |= in ? (1 << t) : 0;
-            }
-#pragma unroll
-            for (int c = 0; c < 16; c++) acc3[pl][c] = 0.f;
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                const float* texel = plane + to_[pl][t] + half * fh;
-#pragma unroll
-                for (int c4 = 0; c4 < 4; c4++) {
-                    if (4 * c4 < fh) {
-                        const float4 v = *(const float4*)(texel + 4 * c4);
-                        acc3[pl][4 * c4 + 0] += v.x * tw_[pl][t]; acc3[pl][4 * c4 + 1] += v.y * tw_[pl][t];
-                        acc3[pl][4 * c4 + 2] += v.z * tw_[pl][t]; acc3[pl][4 * c4 + 3] += v.w * tw_[pl][t];
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 16; c++) gsum[c] = ((acc3[0][c] + acc3[1][c]) + acc3[2][c]) / 3.0f;
-        // features of the point: [pt][f], zero beyond F
-#pragma unroll
-        for (int c = 0; c < 16; c++) {
-            if (c < fh) gl[l32 * FG_PITCH + half * fh + c] = gsum[c];
-        }
-        for (int f = p.F + half; f < 32; f += 2) gl[l32 * FG_PITCH + f] = 0.f;
-        const float4 dout4 = valid ? *(const float4*)(p.d_out + gpc * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+#define FIELD_GRAD_ZERO_GSUM                                  // (see there: this kernel's listing needs the dead zero fill)
+#define FIELD_GRAD_STAGE 1
+#include "field_grad.inc"
 
         // ---- 2. h_pre = W0s g + b0 (MFMA), h = lrelu * sqrt2 -> LDS ----------------------------------------------------------
         fg_f32x16 hacc[MT];
 #pragma unroll
         for (int mt = 0; mt < MT; mt++)
 #pragma unroll
-            for (int r = 0; r < 16; r++) hacc[mt][r] = B0[mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
+            for (int r = 0; r < 16; r++) hacc[mt][r] = B0[fg_row_of(mt, r, half)];
 #pragma unroll
         for (int ks = 0; ks < 16; ks++) {
             const float bf = gl[l32 * FG_PITCH + 2 * ks + half];
@@ -353,7 +302,7 @@ __global__ __launch_bounds__(64 * NW) void triplane_field_grad_kernel(FieldGradP
         for (int mt = 0; mt < MT; mt++)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int m = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int m = fg_row_of(mt, r, half);
                 const float hp = hacc[mt][r];
                 const float h = (hp > 0.f ? hp : hp * 0.2f) * sqrt2;
                 hacc[mt][r] = h;
@@ -378,7 +327,7 @@ __global__ __launch_bounds__(64 * NW) void triplane_field_grad_kernel(FieldGradP
         for (int mt = 0; mt < MT; mt++)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int m = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int m = fg_row_of(mt, r, half);
                 float dh = 0.f;
 #pragma unroll
                 for (int j = 0; j < 4; j++) dh = fmaf_(W1s[j * HP + m], dj[j], dh);
@@ -386,8 +335,7 @@ __global__ __launch_bounds__(64 * NW) void triplane_field_grad_kernel(FieldGradP
                 db0a[mt][r] += dhp;
                 dl[m * FG_PITCH + l32] = dhp;
             }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        fg_wave_sync();
 
         // ---- 5. weight-gradient GEMMs over the 32 points; dg = W0s^T dh_pre ----------------------------------------------------
 #pragma unroll
@@ -409,83 +357,14 @@ __global__ __launch_bounds__(64 * NW) void triplane_field_grad_kernel(FieldGradP
             const int k = 2 * ks + half;                                          // hidden unit of this K step
             dg = __builtin_amdgcn_mfma_f32_32x32x2f32(W0s[k * FG_PITCH + l32], dl[k * FG_PITCH + l32], dg, 0, 0, 0);   // A[m = f][k], B[k][n = pt]
         }
-        // ---- 6. scatter: d_plane[tap] += w_tap * dg / 3 ------------------------------------------------------------------------
-        // Transposed through LDS so that ONE atomic instruction adds the 32 channels of one tap (a 128-B line) per half-wave:
-        // issued from the accumulator layout (lane = point) every instruction touched 64 different lines and the kernel ran at
-        // the L2's atomic line rate (82 ms for 8.4 M points).  What bounds it now (round 4, tools/dev/ubench_atomics.hip): the chip
-        // retires 10.3 G such lines per second = 0.6 lane-atomics per clock and CU -- the same for a 24-MiB and a 1.6-GiB target, with
-        // or without sc1 / nt, and with every XCD kept inside its own eighth of the target -- so 12 lines per point are 1.17 ms per
-        // million points whatever the access pattern; only fewer lines (an LDS window that merges the taps of neighbouring rays before
-        // they leave the CU) can lower it.
+        // ---- 6. dg transposed through LDS (lane = point -> lane = channel), then d_coords and the scatter
         if (p.d_planes || p.d_coords) {
 #pragma unroll
-            for (int r = 0; r < 16; r++) gl[l32 * FG_PITCH + (r & 3) + 8 * (r >> 2) + 4 * half] = dg[r];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            for (int r = 0; r < 16; r++) gl[l32 * FG_PITCH + fg_row_of(0, r, half)] = dg[r];
+            fg_wave_sync();
         }
-        // ---- 6a. gradient w.r.t. the sample position (grid_sampler's grid gradient; what a camera is trained through, loss.py:69-83):
-        //     d ix = sum_c dg_c/3 [(ne - nw) ts + (se - sw) tn],   d iy = sum_c dg_c/3 [(sw - nw) te + (se - ne) tw]
-        // taps outside the plane read as zero (torch grid_sampler_2d_backward), then x (size - 1) / 2 (align_corners) and / scale.
-        // lane = (point, channel half): the taps are fetched again (cache hits: this wave gathered them a moment ago).
-        if (p.d_coords) {
-            float dq[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-            for (int pl = 0; pl < 3; pl++) {
-                const float* plane = p.planes + ((int64_t)b * 3 + pl) * p.H * p.W * p.F;
-                const float twx = fr_[pl][0], tn = fr_[pl][1], te = 1.0f - twx, ts = 1.0f - tn;
-                float gix = 0.f, giy = 0.f;
-#pragma unroll
-                for (int c4 = 0; c4 < 4; c4++) {
-                    if (4 * c4 < fh) {
-                        float4 tv[4];
-#pragma unroll
-                        for (int t = 0; t < 4; t++) {
-                            tv[t] = *(const float4*)(plane + to_[pl][t] + half * fh + 4 * c4);
-                            if (!((in_[pl] >> t) & 1)) tv[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-                        }
-                        const float* gq = gl + l32 * FG_PITCH + half * fh + 4 * c4;
-                        const float gv[4] = {gq[0], gq[1], gq[2], gq[3]};
-                        const float nw[4] = {tv[0].x, tv[0].y, tv[0].z, tv[0].w}, ne[4] = {tv[1].x, tv[1].y, tv[1].z, tv[1].w};
-                        const float sw[4] = {tv[2].x, tv[2].y, tv[2].z, tv[2].w}, se[4] = {tv[3].x, tv[3].y, tv[3].z, tv[3].w};
-#pragma unroll
-                        for (int i = 0; i < 4; i++) {
-                            gix = fmaf_(gv[i], (ne[i] - nw[i]) * ts + (se[i] - sw[i]) * tn, gix);
-                            giy = fmaf_(gv[i], (sw[i] - nw[i]) * te + (se[i] - ne[i]) * twx, giy);
-                        }
-                    }
-                }
-                gix += __shfl_xor(gix, 32, 64);
-                giy += __shfl_xor(giy, 32, 64);
-                dq[pl == 2 ? 1 : 0] += gix * sx;                 // planes (x,y), (x,z), (y,z): width <- first coordinate
-                dq[pl == 0 ? 1 : 2] += giy * sy;
-            }
-            if (half == 0 && valid) {
-                const float k = 1.0f / (3.0f * p.scale);
-                float* dc = p.d_coords + gpc * 3;
-                dc[0] = dq[0] * k; dc[1] = dq[1] * k; dc[2] = dq[2] * k;
-            }
-        }
-        if (p.d_planes) {
-            int* tab_off = (int*)hl;                             // [32 pts][12 taps] float offset into d_planes (h / dh_pre are dead now)
-            float* tab_w = hl + 32 * 12;
-#pragma unroll
-            for (int pl = 0; pl < 3; pl++)
-#pragma unroll
-                for (int t = 0; t < 4; t++)
-                    if (((pl * 4 + t) & 1) == half) {
-                        tab_off[l32 * 12 + pl * 4 + t] = (int)((((int64_t)b * 3 + pl) * p.H * p.W) * p.F) + to_[pl][t];
-                        tab_w[l32 * 12 + pl * 4 + t] = tw_[pl][t] / 3.0f;
-                    }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            for (int e2 = 0; e2 < 32 * 12 / 2; e2++) {
-                const int e = 2 * e2 + half;                    // (point, tap) handled by this half-wave; lane = channel
-                const float wt = tab_w[e];
-                if (wt != 0.f && l32 < p.F) unsafeAtomicAdd(p.d_planes + tab_off[e] + l32, wt * gl[(e / 12) * FG_PITCH + l32]);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+#define FIELD_GRAD_STAGE 6
+#include "field_grad.inc"
     }
 
     // ---- reduction of the weight gradients: lanes -> wave slot in LDS -> block (fixed order) -> partial[blockIdx] ------------
@@ -493,14 +372,13 @@ __global__ __launch_bounds__(64 * NW) void triplane_field_grad_kernel(FieldGradP
     __syncthreads();
     float* slot = wave_mem + wv * WAVE_FLOATS;                 // >= npart floats (host check)
     for (int i = l; i < p.npart; i += 64) slot[i] = 0.f;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    fg_wave_sync();
     const int o_db0 = p.hid * p.F, o_dw1 = o_db0 + p.hid, o_db1 = o_dw1 + 4 * p.hid;
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int m = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int m = fg_row_of(mt, r, half);
             if (m < p.hid && l32 < p.F) slot[m * p.F + l32] = dW0a[mt][r];                 // C[m][n = f]
             if (m < p.hid && l32 < 4) slot[o_dw1 + l32 * p.hid + m] = dW1a[mt][r];          // C[m][n = j]
             float s = db0a[mt][r];

@@ -178,6 +178,81 @@ def test_walks_give_identical_bytes(tdgp, B, h, w, S, n, marcher):
     assert torch.equal(noisy[..., 3], plain[..., 3] + noise * 0.8)
 
 
+# ------------------------------------------------------------------------------------------------ 3b. every branch of the shared addressing
+def _addressing_coords(scale):
+    """[37, 3] positions that take every branch of the bilinear geometry the kernels share (csrc/field_body.inc, csrc/field_grad.inc), as
+    normalised values q = c / scale per axis: the corners -1 and +1, 2^-20 inside and outside of each, beyond -2 texels and beyond W / H (the
+    clamps).  Every such value stands on one axis at a time next to two interior ones -- so a cell's +1 neighbour is out of range on x only, on
+    y only, on z only -- and then on all three axes at once.  All of them, and scale = 2^-1, are exact in fp32, so fp32 and float64 agree on the cell."""
+    e = 2.0 ** -20
+    special = [-1.0, 1.0, -1.0 + e, -1.0 - e, 1.0 - e, 1.0 + e, -2.5, 2.5]
+    inner = [0.13, -0.41, 0.62]
+    pts = []
+    for axis in range(3):
+        for v in special:
+            p = [inner[(axis + 1) % 3], inner[(axis + 2) % 3], inner[axis]]
+            p[axis] = v
+            pts.append(p)
+    pts += [[v, v, v] for v in special] + [[-1.0, 1.0, -2.5], [1.0 + e, -1.0 - e, 2.5], [2.5, -2.5, 1.0], inner, [-0.77, 0.05, 0.99]]
+    q = np.asarray(pts, np.float32)
+    assert q.shape == (37, 3)
+    return q * np.float32(scale)
+
+
+def _expected_cells(coords, scale, H, W):
+    """[.., 3, 2] the (x0, y0) tap rows of the three planes in the kernels' own fp32 steps (divide, add, multiply, floor, clamp to [-2, size])."""
+    q = coords.astype(np.float32) / np.float32(scale)
+    out = np.empty(coords.shape[:-1] + (3, 2), np.int32)
+    for pl, (u, v) in enumerate(((0, 1), (0, 2), (1, 2))):                         # planes (x,y), (x,z), (y,z): width <- first coordinate
+        for k, (a, n) in enumerate(((u, W), (v, H))):
+            i = (q[..., a] + np.float32(1.0)) * np.float32((n - 1) / 2.0)
+            out[..., pl, k] = np.clip(np.floor(i), -2, n).astype(np.int32)
+    return out
+
+
+@pytest.mark.parametrize('F,hid', [(8, 16), (32, 64)])
+def test_shared_addressing_at_every_branch(tdgp, F, hid):
+    rs = np.random.RandomState(500 + F)
+    R = tdgp.renderer
+    B, H, W, scale = 2, 5, 7, 0.5
+    one = _addressing_coords(scale)
+    coords = np.stack([one, one[::-1]])                                            # 2 x 37 points: no multiple of 16 or of 32
+    P = coords.shape[1]
+    assert (B * P) % 16 and (B * P) % 32 and P % 16
+    # the list lands where it is meant to: every cell from the lower clamp to the upper one on both axes, out-of-range +1 neighbours on one axis alone
+    cells = _expected_cells(coords, scale, H, W)
+    assert set(cells[..., 0].ravel()) >= {-2, -1, 0, W - 2, W - 1, W} and set(cells[..., 1].ravel()) >= {-2, -1, 0, H - 2, H - 1, H}
+    xy = cells[0, :, 0]
+    assert ((xy[:, 0] == W - 1) & (xy[:, 1] >= 0) & (xy[:, 1] < H - 1)).any() and ((xy[:, 1] == H - 1) & (xy[:, 0] >= 0) & (xy[:, 0] < W - 1)).any()
+    with torch.no_grad():                                                          # and float64 sees the same cells (the file's _reference: grid_sample's own floor)
+        c64 = torch.as_tensor(coords, dtype=torch.float64) / scale
+        for pl, (u, v) in enumerate(((0, 1), (0, 2), (1, 2))):
+            ref_cell = torch.stack([torch.floor((c64[..., u] + 1) * (W - 1) / 2).clamp(-2, W), torch.floor((c64[..., v] + 1) * (H - 1) / 2).clamp(-2, H)], dim=-1)
+            assert np.array_equal(ref_cell.numpy().astype(np.int32), cells[..., pl, :])
+    planes = rs.randn(B, 3 * F, H, W).astype(np.float32)
+    d_out = rs.randn(B, P, 4).astype(np.float32)
+    hw = R.planes_to_hwc(T(planes))
+    taps = {}
+    for n in (2, 3, 4):
+        mlp, ws, bs = _random_mlp(tdgp, rs, F, hid, n, 'classical')
+        pack = R._mlp_params(mlp) if n == 2 else R._mlp_params_deep(mlp)
+        taps[n] = torch.full([B, P, 3, 2], -99, dtype=torch.int32, device=DEV)
+        got = R._field(hw, pack, scale, coords=T(coords), tap_idx=taps[n])
+        refs = {}
+        for dtype in (torch.float64, torch.float32):
+            x, c = _cpu([planes, coords], dtype, grad=True)
+            out = _reference(x, c, _cpu(ws, dtype), _cpu(bs, dtype), 'classical', scale, dtype)
+            g = torch.autograd.grad(out, [x, c], torch.as_tensor(d_out).to(dtype))
+            refs[dtype] = dict(out=out.detach().numpy(), d_planes=g[0].numpy(), d_coords=g[1].numpy())
+        _within_reference_noise(N(got), refs[torch.float64]['out'], refs[torch.float32]['out'], f'addressing branches F {F} hid {hid} n_layers {n} forward')
+        # each gradient kernel against float64 autograd (not against the other kernel); the MLP gradients are not part of this comparison
+        res = R.simple_tri_plane_renderer_backward(T(planes), T(coords), mlp, T(d_out[..., :3]), T(d_out[..., 3:]), scale=scale, coords_grad=True)
+        for name, t in (('d_planes', R.planes_from_hwc(res[0])), ('d_coords', res[-1])):
+            _within_reference_noise(N(t), refs[torch.float64][name], refs[torch.float32][name], f'addressing branches F {F} hid {hid} n_layers {n} {name}')
+    assert torch.equal(taps[2], taps[3]) and torch.equal(taps[2], taps[4])          # byte for byte
+    assert np.array_equal(N(taps[2]), cells)
+
+
 # ------------------------------------------------------------------------------------------------ 4. edges
 def test_edges_and_refusals(tdgp):
     rs = np.random.RandomState(4)

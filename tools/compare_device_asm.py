@@ -6,7 +6,8 @@
 The listings are what the build makes for its ISA check (`hipcc` + build.FLAGS + `-S --cuda-device-only`; `--compile` produces them).  Compared
 per kernel symbol -- the order of the template instantiations in the file may move --: the set of `.amdhsa_kernel` symbols, the kernel
 descriptor of each and the instruction text of each.  Basic-block labels (and the comments that cite them) carry the function's ordinal in the
-file (`.LBB12_3`); the ordinal is dropped before comparing.  Exit status 0 = identical."""
+file (`.LBB12_3`); the ordinal is dropped before comparing.  Exit status 0 = identical.  `--allow-added` accepts kernels that exist only in NEW
+(a refactor that instantiates a shared body once more); a kernel that disappears or changes still fails."""
 import os
 import re
 import subprocess
@@ -31,7 +32,7 @@ def kernels(text):
     return out
 
 
-def compare(old_text, new_text):
+def compare(old_text, new_text, allow_added=False):
     old, new = kernels(old_text), kernels(new_text)
     gone, added = sorted(set(old) - set(new)), sorted(set(new) - set(old))
     differ = sorted(n for n in set(old) & set(new) if old[n] != new[n])
@@ -41,7 +42,7 @@ def compare(old_text, new_text):
     same = len(set(old) & set(new)) - len(differ)
     print(f'{len(old)} kernels in OLD, {len(new)} in NEW: {same} identical, {len(differ)} differ, {len(gone)} only in OLD, {len(added)} only in NEW; '
           f'{sum(len(b) for b in new.values())} lines of kernel text compared')
-    return not (gone or added or differ)
+    return not (gone or differ or (added and not allow_added))
 
 
 def listing(tree, source, out):
@@ -52,11 +53,12 @@ def listing(tree, source, out):
 
 
 if __name__ == '__main__':
-    args = sys.argv[1:]
+    args = [a for a in sys.argv[1:] if a != '--allow-added']
+    allow_added = '--allow-added' in sys.argv[1:]
     if args and args[0] == '--compile':
         source = args[3] if len(args) > 3 else os.path.join('3dgp_amd', 'csrc', 'modconv.hip')
         with tempfile.TemporaryDirectory() as d:
             texts = [listing(args[i], source, os.path.join(d, f'{i}.s')) for i in (1, 2)]
     else:
         texts = [open(a).read() for a in args[:2]]
-    sys.exit(0 if compare(*texts) else 1)
+    sys.exit(0 if compare(*texts, allow_added=allow_added) else 1)
