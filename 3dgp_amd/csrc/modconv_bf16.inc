@@ -18,7 +18,8 @@
 // Kernels (all block = 256 threads = 4 waves, K chunk = 32 channels = two 16-channel MFMA steps, one LDS stage per chunk, two
 // blocks per CU so that one block's staging runs under the other's MFMAs):
 //   conv3_bf16_kernel   3x3 stride 1, W % 32 == 0: the virtual-row scheme of conv3_mfma_kernel (zero row after every sample),
-//                       block tile 64 channels x (8 rows x 32 columns);
+//                       block tile 64 channels x (8 rows x 32 columns).  A block stages the styles of TWO samples (b_lo, b_lo + 1): its
+//                       8 + 2 virtual rows reach real rows of a third sample when H + 1 <= 7, so the host takes it for H >= 8 only;
 //   upconv_bf16_kernel  the x2 layers: upconv_mfma_kernel's linearised-grid transposed convolution, same parity-planar fp32 Z,
 //                       followed by fir_act_kernel<.., YBF> (FIR + demod + noise + bias + lrelu + clamp -> bf16);
 //   ToRGB               torgb_mfma_kernel<.., XBF> (fp32 MFMA: the layer is HBM-bound; bf16 input halves its read traffic).

@@ -753,8 +753,9 @@ TDGP_API int tdgp_modconv2d(const float* x, const void* wpack, const float* styl
 }
 
 // Reduced-precision blocks (BASELINE configs[4], modconv_bf16.inc): x is bf16 NCHW; y is bf16 NCHW (3x3 layers) or, for the ToRGB
-// form (k = 1, channel-last planes + fused skip), fp32.  Forms the bf16 MFMA kernels take: 3x3 with Cin % 32 == 0 and, for up = 1,
-// W % 32 == 0; the channel-last ToRGB.  Anything else returns TDGP_EUNSUPPORTED (the caller widens to fp32 and uses tdgp_modconv2d).
+// form (k = 1, channel-last planes + fused skip), fp32.  Forms the bf16 MFMA kernels take: 3x3 with Cin % 32 == 0, Cin <= 2048 and, for
+// up = 1, W % 32 == 0 and H >= 8 (conv3_bf16_kernel stages the styles of TWO samples per block: with H + 1 <= 7 its 10-row window reaches
+// real rows of a third); the channel-last ToRGB.  Anything else returns TDGP_EUNSUPPORTED (the caller widens to fp32 and uses tdgp_modconv2d).
 TDGP_API int tdgp_modconv2d_bf16(const void* x, const void* wpack, const float* styles, const float* dcoef_in, const float* noise, int64_t noise_bstride,
                                  const float* bias, const float* fir4x4, const float* skip, void* y, int B, int Cin, int Cout, int H, int W, int k, int up,
                                  int demodulate, int act, float alpha, float gain, float clamp, int out_layout, int out_feat, void* workspace,
@@ -767,8 +768,8 @@ TDGP_API int tdgp_modconv2d_bf16(const void* x, const void* wpack, const float* 
                "modconv2d_bf16: tensor too large (activations are addressed through 4 GiB buffer descriptors)");
     const bool rgb = k == 1 && up == 1 && out_layout == 1 && Cout <= 96 && !demodulate && !noise && act == 1 && ((H * W) & 3) == 0 && out_feat >= 4 &&
                      (out_feat % 4) == 0 && (Cout % out_feat) == 0 && (!skip || (fir4x4 && (H % 2) == 0 && (W % 2) == 0));
-    const bool c3 = k == 3 && up == 1 && out_layout == 0 && !skip && (W & 31) == 0 && (Cin & 31) == 0 && Cin <= 2048;
-    bool u3 = k == 3 && up == 2 && out_layout == 0 && !skip && fir4x4 && (Cin & 31) == 0 && (W & 1) == 0;
+    const bool c3 = k == 3 && up == 1 && out_layout == 0 && !skip && (W & 31) == 0 && (Cin & 31) == 0 && Cin <= 2048 && H >= 8;
+    bool u3 = k == 3 && up == 2 && out_layout == 0 && !skip && fir4x4 && (Cin & 31) == 0 && Cin <= 2048 && (W & 1) == 0;
     size_t u3_lds = 0;
     if (u3) {                                     // every acceptance test before the first launch: the x2 kernel keeps the styles of all samples a block's
         const UpPlan pl0 = up_plan(B, Cin, Cout, H, W);                                   // grid points can touch in LDS
@@ -776,7 +777,7 @@ TDGP_API int tdgp_modconv2d_bf16(const void* x, const void* wpack, const float* 
         u3_lds = (size_t)(9 * 2 * 64 * 32 + 2 * 2 * 130 * 32) + (size_t)nsb0 * Cin * 4;
         TDGP_CHECK(u3_lds <= 80 * 1024, TDGP_EUNSUPPORTED, "modconv2d_bf16: x2 layer with Cin=%d, B=%d, H=%d needs %zu bytes of LDS (> 80 KiB)", Cin, B, H, u3_lds);
     }
-    TDGP_CHECK(rgb || c3 || u3, TDGP_EUNSUPPORTED, "modconv2d_bf16: no bf16 kernel for k=%d up=%d Cin=%d W=%d layout=%d", k, up, Cin, W, out_layout);
+    TDGP_CHECK(rgb || c3 || u3, TDGP_EUNSUPPORTED, "modconv2d_bf16: no bf16 kernel for k=%d up=%d Cin=%d H=%d W=%d layout=%d", k, up, Cin, H, W, out_layout);
     const bool nz16 = noise_aligned(noise, noise_bstride, 16);
     TDGP_CHECK(nz16, TDGP_EINVAL, "modconv2d_bf16: noise must be 16-byte aligned with a batch stride that is a multiple of 4 floats");
     const WsLayout wl = ws_layout(B, Cin, Cout, H, W, k, up);

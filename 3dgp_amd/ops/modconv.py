@@ -124,6 +124,21 @@ def _packed(weight):
     return _cached(_PACK_CACHE, weight, PackedConv)
 
 
+def bf16_kernel_takes(k, up, cin, cout, H, W, out_layout=0, out_feat=0, demodulate=True, has_noise=False, act='linear', has_fir=True, has_skip=False):
+    """Mirror of the shape acceptance tests of tdgp_modconv2d_bf16 (csrc/modconv_host.inc): True where a bf16 MFMA kernel takes the call; anything
+    else is widened and runs on the fp32 kernels.  The one test it does not repeat is the x2 kernel's LDS budget (styles of every sample a
+    block touches, e.g. Cin = 2048, B >= 4 at 4 x 4): there the C side alone answers TDGP_EUNSUPPORTED and `modconv_forward` widens then."""
+    if out_layout == 1:           # the ToRGB form: 1x1, no demodulation, no noise, linear; fp32 channel-last planes, optional x2 skip
+        return (k == 1 and up == 1 and cout <= 96 and not demodulate and not has_noise and act == 'linear' and out_feat >= 4 and out_feat % 4 == 0 and
+                cout % out_feat == 0 and (H * W) % 4 == 0 and (not has_skip or (has_fir and H % 2 == 0 and W % 2 == 0)))
+    if out_layout != 0 or k != 3 or has_skip or cin % 32 != 0 or cin > 2048:
+        return False
+    if up == 2:
+        return has_fir and W % 2 == 0
+    # stride 1: conv3_bf16_kernel stages the styles of two samples per block, which covers its 10-row window for H >= 8 only
+    return up == 1 and W % 32 == 0 and H >= 8
+
+
 def modconv_forward(x, packed, styles, noise=None, bias=None, up=1, demodulate=True, act='linear', alpha=None, gain=None, clamp=None,
                     fir=None, skip=None, out_layout=0, out_feat=0, dcoef=None):
     """One call of tdgp_modconv2d (x fp32) / tdgp_modconv2d_bf16 (x bf16: the reduced-precision blocks).  x [B,Cin,H,W] NCHW; returns [B,Cout,H*up,W*up] (out_layout 0) or the
@@ -188,12 +203,8 @@ def modconv_forward(x, packed, styles, noise=None, bias=None, up=1, demodulate=T
         # the ToRGB form (1x1, no demodulation; `skip` = the running fp32 image it joins): its result is fp32 in EITHER layout --
         # `y.to(float32); img.add_(y)`, networks_stylegan2.py:268-269 -- so the NCHW fallback must not round the accumulated image to bf16
         rgb_form = rgb or (packed.k == 1 and not demodulate) or skip is not None
-        # mirror of the acceptance tests of tdgp_modconv2d_bf16 (modconv.hip): anything else is widened and runs on the fp32 kernels
-        if rgb:
-            takes = (packed.k == 1 and up == 1 and cout <= 96 and out_feat > 0 and out_feat % 4 == 0 and cout % out_feat == 0 and (H * W) % 4 == 0 and
-                     (skip is None or (H % 2 == 0 and W % 2 == 0)))
-        else:
-            takes = (packed.k == 3 and not rgb_form and cin % 32 == 0 and cin <= 2048 and ((up == 2 and W % 2 == 0) or (up == 1 and W % 32 == 0)))
+        takes = bf16_kernel_takes(packed.k, up, cin, cout, H, W, out_layout=out_layout, out_feat=out_feat, demodulate=demodulate, has_noise=noise is not None,
+                                  act=act, has_fir=fir is not None, has_skip=skip is not None)
         def widened():
             y = modconv_forward(x.float(), packed, styles, noise=noise, bias=bias, up=up, demodulate=demodulate, act=act, alpha=alpha, gain=gain,
                                 clamp=None if clamp < 0 else clamp, fir=fir, skip=skip, out_layout=out_layout, out_feat=out_feat, dcoef=dcoef)

@@ -167,7 +167,9 @@ int     tdgp_modconv2d(const float* x, const void* wpack, const float* styles, c
  * bf16 weights x bf16 (style-scaled) activations on v_mfma_f32_32x32x16_bf16, fp32 accumulation; demodulation, noise, bias,
  * activation, gain, clamp in fp32; the reference's rounding points behind the accumulator (conv output, + noise, bias_act output; the
  * bias itself is rounded as in `self.bias.to(x.dtype)`), and the skip is added AFTER the clamp.
- * Forms taken: 3x3 with Cin % 32 == 0 (and W % 32 == 0 for up = 1); the channel-last ToRGB with Cout <= 96.  Anything else returns
+ * Forms taken: 3x3 with Cin % 32 == 0 and Cin <= 2048 (and W % 32 == 0, H >= 8 for up = 1; W even for up = 2); the channel-last ToRGB
+ * with Cout <= 96.  The stride-1 kernel keeps the styles of two samples per block, which covers its 10-row window only for H >= 8:
+ * smaller images are refused like every other form without a bf16 kernel.  Anything else returns
  * TDGP_EUNSUPPORTED -- decided before anything is launched: widen x to fp32 and call tdgp_modconv2d.  `noise` must be 16-byte aligned with
  * a batch stride that is a multiple of 4 floats (TDGP_EINVAL otherwise; tdgp_modconv2d takes any float* and falls back to scalar
  * loads).  Workspace: tdgp_modconv2d_workspace_bytes of the same shape.

@@ -1756,8 +1756,9 @@ def test_bf16_planes_nchw_equal_channel_last(tdgp):
     hwc = dec(ws, noise_mode='const', hwc=True).t
     assert nchw.dtype == torch.float32 and hwc.dtype == torch.float32
     a, b = N(nchw), N(hwc.permute(0, 1, 4, 2, 3).reshape(nchw.shape))
-    # the channel-last kernel keeps the reference's bf16 rounding points inside ToRGB (weights, style-scaled activations, the pre-skip
-    # term), the widened NCHW fallback multiplies the same bf16 activations in fp32: they agree to bf16 rounding of ONE ToRGB term per
+    # the channel-last kernel multiplies the bf16 activations in fp32 (fp32 weights, fp32 style-scaled activations: tests/bf16_model.py matches it
+    # with unrounded operands) and keeps the reference's bf16 rounding points behind the sum (conv output, bias, the pre-skip term); the widened
+    # NCHW fallback multiplies the same activations in fp32 and rounds nothing: they agree to bf16 rounding of ONE ToRGB term per
     # block, and both sit inside the bf16 tolerance against the reference's own reduced-precision run
     _assert_bf16_close(a, b, 'tri-planes NCHW vs channel-last', max_tol=6e-3, mean_tol=5e-4)
     _assert_bf16_close(a, load_golden('bf16')['planes'], 'NCHW tri-planes vs the reference')
