@@ -14,6 +14,23 @@
 // is not the reference's either (torch's expf is Sleef's 1-ulp routine, its sums fp32 cascades).  What has to be EXACT is kept
 // exact: sample_pdf's normaliser follows torch's summation order, the cdf is torch's sequential-double cumsum rounded per prefix,
 // so for given weights the searchsorted indices and the fine samples equal the reference's bit for bit (the stage-level tests).
+//
+// Written once, fence-free functions (or statements) of one ray's LDS pointers and per-lane state, for the one-ray kernels (stage, wave_sync(),
+// next stage) and the 64 + 64 pair kernels (stage for ray A, for ray B, wave_sync()) alike:
+//   TDGP_CLASSICAL_ALPHA / TDGP_MIP_ALPHA   alpha and transmittance factor of a sample (both marchers, every branch; both pair marches)
+//   TDGP_MARCH_PASS / TDGP_MARCH_PASS2      the fp64-scan pass of a march and its two-chunk side-by-side form
+//   smooth_read / smooth_write / offset_weights / pdf_cdf / cdf_search / cdf_sample   the importance stages (importance_lds = all of them)
+//   wave_bitonic_sort_n<NS>                 the (key, index) network, NS = 1, 2, 4, 8 slots per lane
+//   stable_ranks<NR> over stable_ranks_n    the brute-force stable rank and its one dispatcher (short and long lists)
+//   TDGP_LAUNCH_RAYS                        the launch of every per-ray kernel family; an entry point selects an instantiation once
+// The first two are statement macros: as functions they change the instruction text of all ten one-ray kernels that hold a marcher, as text none.
+// Specialised copies in the pair section, each restating the one-ray text it names at 64 / 128 (profiles/ray_tail_refactor_ab.json):
+//   torch_order_sum_62      torch_order_sum_lds, branch n >= 8 at nv = 7, for the pair kernel's pdf row (pdf_cdf<true>)
+//   imp_count / imp_gather  the counting rank of importance_from_coarse_kernel's N <= 64 / N <= 128 blocks: behind one count_rank<NS> for all
+//                           three, importance_from_coarse_kernel<128> / <256> go from 57 / 97 to 65 / 104 VGPRs (7 instead of 8 waves per SIMD at <128>)
+//   mrg_search / _scatter_last / _ranks / mrg_scatter / mrg_composite   merge_composite_kernel's merge ranks, scatter and composite: as shared
+//                           stage functions merge_composite_pair_kernel goes from 572 to 606 us (parent spread 6) and merge_composite_kernel<512>
+//                           at 256 + 256 from 550 to 566 us (spread 2)
 #include "common.h"
 
 namespace {
@@ -66,56 +83,84 @@ __device__ __forceinline__ float s2t(float s, float t_near, float t_far) { retur
 template <bool LONGX>
 __device__ __forceinline__ float exp_neg(float x) { return LONGX ? (float)exp(-(double)x) : expf(-x); }
 
+// alpha_i and the transmittance factor (1 - alpha_i) + 1e-10 of sample i < S (classical; tri_plane_renderer.py:362-372) or of mid-point sample
+// i < M (mip; :313-330) of an LDS-resident list of S samples, (0, 1) past the end: the only place these expressions are written.  Statements, not functions:
+// behind a call (inlined or not) the compiler folds the marchers' `M = (flags & 1) ? S : S - 1` differently and every kernel with a marcher
+// changes; as text the one-ray kernels keep their code to the instruction.
+#define TDGP_CLASSICAL_ALPHA(LONGX, z, sig, i, S, flags, cut_thr, alpha, fac)                                        \
+    do {                                                                                                            \
+        alpha = 0.f; fac = 1.0f;                                                                                    \
+        if ((i) < (S)) {                                                                                            \
+            const float delta = ((i) < (S) - 1) ? (z[(i) + 1] - z[i]) : (((flags) & 1) ? 1e10f : 1e-3f);            \
+            float sp = ((flags) & 8) ? (sig[i] > 0.f ? sig[i] : 0.f) : softplus20f(sig[i]);                         \
+            if (sp < cut_thr) sp = 0.f; /* cut_quantile (:366-368); cut_thr = 0 never cuts (sp >= 0) */             \
+            alpha = 1.0f - exp_neg<LONGX>(delta * sp);                                                              \
+            fac = (1.0f - alpha) + 1e-10f;                                                                          \
+        }                                                                                                           \
+    } while (0)
+
+#define TDGP_MIP_ALPHA(LONGX, z, sig, i, S, M, density_bias, cut_thr, alpha, fac)                                    \
+    do {                                                                                                            \
+        alpha = 0.f; fac = 1.0f;                                                                                    \
+        if ((i) < (M)) {                                                                                            \
+            float delta, smid;                                                                                      \
+            if ((i) < (S) - 1) { delta = z[(i) + 1] - z[i]; smid = (sig[i] + sig[(i) + 1]) / 2.f; }                 \
+            else { delta = 1e10f; smid = sig[(S) - 1]; }                                                            \
+            float sp = softplus20f(smid + density_bias);                                                            \
+            if (sp < cut_thr) sp = 0.f; /* cut_quantile (:324-326) */                                               \
+            float dd = sp * delta;                                                                                  \
+            alpha = 1.0f - exp_neg<LONGX>(dd);                                                                      \
+            fac = (1.0f - alpha) + 1e-10f;                                                                          \
+        }                                                                                                           \
+    } while (0)
+
+// One 64-sample pass of a march: lane l's weight `wi` = alpha * (exclusive prefix product of the factors), `carry` = the product so far,
+// `incl64` = the pass's fp64 prefixes (their last lane is the next carry).  Statements for the same reason.  DECLARATIONS in the caller's
+// scope, so never the body of an unbraced if / for, once per scope: `wi`, `incl64` (named at the call) and `incl`, `excl` (not named there).
+// transmittance = torch.cumprod on the CPU: prefixes accumulated in fp64, each rounded to fp32.  The fp64 DPP
+// scan (6 steps of 2 moves + 1 v_mul_f64) rounds to the same fp32 prefix as the sequential fp64 product except with probability
+// ~2^-29 per element.  Round 5: the fp32 scan used since round 2 left the composited depth 2.4e-7 (2 ulp) from the reference's
+// float64 image on average where the reference's own fp32 run sits at 0.9e-7 (e2e_full_c3) -- with this it is level.
+#define TDGP_MARCH_PASS(wi, incl64, alpha, fac, carry)                   \
+    const double incl64 = wave_scan_f64<true>((double)(fac)) * (carry);  \
+    const float incl = (float)incl64;                                    \
+    const float excl = wave_shr1_f32(incl, (float)(carry));              \
+    const float wi = (alpha) * excl;
+// Two passes (a list of 65..128 samples) SIDE BY SIDE: both chunks' prefix products are two independent dependency chains the scheduler
+// interleaves, joined by the one multiplication that couples them, where two TDGP_MARCH_PASS run one after the other -- and these kernels
+// are bound by the length of a wave's dependent chain at the SIMD's 8-wave occupancy.  Same operations on the same values
+// (the first chunk's `* carry` is `* 1.0`): same bits.  `i1` = the second chunk's fp64 prefixes.  `alpha` and `fac` are float[2].  Declares `wi0`,
+// `wi1`, `i1` (named at the call) and `s0`, `s1`, `c1`, `incl0`, `incl1` (not named there) in the caller's scope, under the same rules.
+#define TDGP_MARCH_PASS2(wi0, wi1, i1, alpha, fac)                                                                          \
+    const double s0 = wave_scan_f64<true>((double)fac[0]), s1 = wave_scan_f64<true>((double)fac[1]);                        \
+    const double c1 = wave_last_f64(s0);                                                                                    \
+    const double i1 = s1 * c1;                                                                                              \
+    const float incl0 = (float)s0, incl1 = (float)i1;                                                                       \
+    const float wi0 = alpha[0] * wave_shr1_f32(incl0, 1.0f), wi1 = alpha[1] * wave_shr1_f32(incl1, (float)c1);
+
 template <bool LONGX = false>
 __device__ void march_classical_lds(const float* z, const float* sig, float* w, int S, int flags, float cut_thr, float& final_T, float& wagg) {
     const int l = lane_id();
     double carry = 1.0;
     float wsum = 0.0f;
     if (S > 64 && S <= 128) {
-        // Two chunks of 64 samples (the merged 64 + 64 list): both chunks' softplus / exp / prefix products are evaluated SIDE BY SIDE -- two independent
-        // dependency chains the scheduler interleaves -- and joined by the one multiplication that couples them.  The loop below runs them one after the
-        // other, and these kernels are bound by the length of a wave's dependent chain at the SIMD's 8-wave occupancy.  Same operations on
-        // the same values (the first chunk's `* carry` is `* 1.0`): same bits.
+        // two chunks of 64 samples (the merged 64 + 64 list): their softplus / exp / prefix products side by side (TDGP_MARCH_PASS2)
         float alpha[2], fac[2];
 #pragma unroll
         for (int c = 0; c < 2; c++) {
             const int i = 64 * c + l;
-            alpha[c] = 0.f; fac[c] = 1.0f;
-            if (i < S) {
-                const float delta = (i < S - 1) ? (z[i + 1] - z[i]) : ((flags & 1) ? 1e10f : 1e-3f);
-                float sp = (flags & 8) ? (sig[i] > 0.f ? sig[i] : 0.f) : softplus20f(sig[i]);
-                if (sp < cut_thr) sp = 0.f;
-                alpha[c] = 1.0f - exp_neg<LONGX>(delta * sp);
-                fac[c] = (1.0f - alpha[c]) + 1e-10f;
-            }
+            TDGP_CLASSICAL_ALPHA(LONGX, z, sig, i, S, flags, cut_thr, alpha[c], fac[c]);
         }
-        const double s0 = wave_scan_f64<true>((double)fac[0]), s1 = wave_scan_f64<true>((double)fac[1]);
-        const double c1 = wave_last_f64(s0);
-        const double i1 = s1 * c1;
-        const float incl0 = (float)s0, incl1 = (float)i1;
-        const float wi0 = alpha[0] * wave_shr1_f32(incl0, 1.0f), wi1 = alpha[1] * wave_shr1_f32(incl1, (float)c1);
+        TDGP_MARCH_PASS2(wi0, wi1, i1, alpha, fac)
         w[l] = wi0; wsum += wi0;
         if (64 + l < S) { w[64 + l] = wi1; wsum += wi1; }
         carry = wave_last_f64(i1);
     } else
     for (int base = 0; base < S; base += 64) {
         const int i = base + l;
-        float alpha = 0.f, fac = 1.0f;
-        if (i < S) {
-            float delta = (i < S - 1) ? (z[i + 1] - z[i]) : ((flags & 1) ? 1e10f : 1e-3f);
-            float sp = (flags & 8) ? (sig[i] > 0.f ? sig[i] : 0.f) : softplus20f(sig[i]);
-            if (sp < cut_thr) sp = 0.f;                        // cut_quantile (:366-368); cut_thr = 0 never cuts (sp >= 0)
-            alpha = 1.0f - exp_neg<LONGX>(delta * sp);
-            fac = (1.0f - alpha) + 1e-10f;
-        }
-        // transmittance = torch.cumprod on the CPU: prefixes accumulated in fp64, each rounded to fp32.  The fp64 DPP
-        // scan (6 steps of 2 moves + 1 v_mul_f64) rounds to the same fp32 prefix as the sequential fp64 product except with probability
-        // ~2^-29 per element.  Round 5: the fp32 scan used since round 2 left the composited depth 2.4e-7 (2 ulp) from the reference's
-        // float64 image on average where the reference's own fp32 run sits at 0.9e-7 (e2e_full_c3) -- with this it is level.
-        const double incl64 = wave_scan_f64<true>((double)fac) * carry;
-        const float incl = (float)incl64;
-        const float excl = wave_shr1_f32(incl, (float)carry);
-        const float wi = alpha * excl;
+        float alpha, fac;
+        TDGP_CLASSICAL_ALPHA(LONGX, z, sig, i, S, flags, cut_thr, alpha, fac);
+        TDGP_MARCH_PASS(wi, incl64, alpha, fac, carry)
         if (i < S) { w[i] = wi; wsum += wi; }
         carry = wave_last_f64(incl64);
     }
@@ -137,21 +182,9 @@ __device__ void march_mip_lds(const float* z, const float* sig, float* w, int S,
     float wsum = 0.0f;
     for (int base = 0; base < M; base += 64) {
         const int i = base + l;
-        float alpha = 0.f, fac = 1.0f;
-        if (i < M) {
-            float delta, smid;
-            if (i < S - 1) { delta = z[i + 1] - z[i]; smid = (sig[i] + sig[i + 1]) / 2.f; }
-            else { delta = 1e10f; smid = sig[S - 1]; }
-            float sp = softplus20f(smid + density_bias);
-            if (sp < cut_thr) sp = 0.f;                        // cut_quantile (:324-326)
-            float dd = sp * delta;
-            alpha = 1.0f - exp_neg<LONGX>(dd);
-            fac = (1.0f - alpha) + 1e-10f;
-        }
-        const double incl64 = wave_scan_f64<true>((double)fac) * carry;        // fp64 prefixes rounded to fp32: see march_classical_lds
-        const float incl = (float)incl64;
-        const float excl = wave_shr1_f32(incl, (float)carry);
-        const float wi = alpha * excl;
+        float alpha, fac;
+        TDGP_MIP_ALPHA(LONGX, z, sig, i, S, M, density_bias, cut_thr, alpha, fac);
+        TDGP_MARCH_PASS(wi, incl64, alpha, fac, carry)
         if (i < M) { w[i] = wi; wsum += wi; }
         carry = wave_last_f64(incl64);
     }
@@ -201,71 +234,129 @@ __device__ float torch_order_sum_lds(const float* w1, int n, float eps) {
     return acc[0];
 }
 
+// torch_order_sum_lds for 56 <= n <= 62 (a pdf row of 61 or 62 entries): nv = 7 vectors, one interleaved group, vectors 4..6 into accumulator 0, n - 56 tail elements
+__device__ __forceinline__ float torch_order_sum_62(const float* w1, int n, float eps) {
+    const int l = lane_id();
+    const int col = l & 7, a = (l >> 3) & 3;
+    float acc = 0.f;
+    acc = __fadd_rn(acc, __fadd_rn(w1[a * 8 + col], eps));
+#pragma unroll
+    for (int j = 4; j < 7; j++) {
+        const float v = __fadd_rn(w1[j * 8 + col], eps);
+        if (a == 0) acc = __fadd_rn(acc, v);
+    }
+    float p = __shfl(acc, col, 64);
+    p = __fadd_rn(p, __shfl(acc, col + 8, 64));
+    p = __fadd_rn(p, __shfl(acc, col + 16, 64));
+    p = __fadd_rn(p, __shfl(acc, col + 24, 64));
+    float fin = 0.f;
+#pragma unroll
+    for (int k = 56; k < 62; k++) {
+        const float t = __fadd_rn(fin, __fadd_rn(w1[k], eps));
+        fin = k < n ? t : fin;
+    }
+#pragma unroll
+    for (int c = 0; c < 8; c++) fin = __fadd_rn(fin, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), c)));
+    return fin;
+}
+
 // ------------------------------------------------------------------------------------------------
-// sample_importance + sample_pdf on LDS-resident z[S] (s-space) and weights w[Wn].
-// tri_plane_renderer.py:237-295.  Clobbers sc.w / sc.cdf / sc.bins.
-// Lane j produces sample j (strided by 64).  `emit(j, sample, ind, below, above)` consumes the results.
+// sample_importance + sample_pdf (tri_plane_renderer.py:237-295) on one ray's LDS-resident z[S] (s-space)
+// and weights w[Wn], as fence-free stages: the caller puts a wave_sync() between them (importance_lds below; the pair kernel for two rays).
 // ------------------------------------------------------------------------------------------------
-template <typename SC, typename GetU, typename Emit>
-__device__ void importance_lds(SC& sc, int S, int Wn, GetU getu, int N, int mip, Emit emit) {
+// mip smoothing of the weights, in two stages through registers (slot c of lane l = weight l + 64 c):
+// max_pool1d(2,1,pad 1) -> Wn+1, avg_pool1d(2,1) -> Wn, + 0.01
+template <int NV>
+__device__ __forceinline__ void smooth_read(const float* w, int Wn, float (&nv)[NV]) {
+    const int l = lane_id();
+#pragma unroll
+    for (int c = 0; c < NV; c++) {
+        const int i = l + 64 * c;
+        if (i < Wn) {
+            float a = (i - 1 >= 0) ? w[i - 1] : -INFINITY, b = w[i], d = (i + 1 < Wn) ? w[i + 1] : -INFINITY;
+            float t0 = a > b ? a : b;      // tmp[i]   = max(w[i-1], w[i])
+            float t1 = b > d ? b : d;      // tmp[i+1] = max(w[i], w[i+1])
+            nv[c] = (t0 + t1) / 2.f + 0.01f;
+        }
+    }
+}
+template <int NV>
+__device__ __forceinline__ void smooth_write(float* w, int Wn, const float (&nv)[NV]) {
+    const int l = lane_id();
+#pragma unroll
+    for (int c = 0; c < NV; c++) {
+        const int i = l + 64 * c;
+        if (i < Wn) w[i] = nv[c];
+    }
+}
+// the classical marcher's weights + 1e-5
+__device__ __forceinline__ void offset_weights(float* w, int Wn) {
+    for (int i = lane_id(); i < Wn; i += 64) w[i] = w[i] + 1e-5f;
+}
+// bins, the pdf normaliser in torch's fp32 accumulation order (not the exactly rounded sum: the integer rows depend on it), cdf = [0, cumsum(pdf)]
+// as the fp64 scan rounded per prefix.  ROW62: the row has 56..62 entries (S = 64) and the normaliser is torch_order_sum_62.
+template <bool ROW62>
+__device__ __forceinline__ void pdf_cdf(const float* z, const float* w, float* bins, float* cdf, int S, int Wn) {
     const int l = lane_id();
     const float eps = 1e-5f;
-    float* w = sc.w;
-    constexpr int CAP = sizeof(sc.z) / sizeof(float), NV = (CAP > MAXS ? CAP : MAXS) / 64;
-    // smoothed / offset weights, in place (two passes through registers)
-    if (mip) {
-        // max_pool1d(2,1,pad 1) -> Wn+1, avg_pool1d(2,1) -> Wn, + 0.01
-        float nv[NV];
-#pragma unroll
-        for (int c = 0; c < NV; c++) {
-            const int i = l + 64 * c;
-            if (i < Wn) {
-                float a = (i - 1 >= 0) ? w[i - 1] : -INFINITY, b = w[i], d = (i + 1 < Wn) ? w[i + 1] : -INFINITY;
-                float t0 = a > b ? a : b;      // tmp[i]   = max(w[i-1], w[i])
-                float t1 = b > d ? b : d;      // tmp[i+1] = max(w[i], w[i+1])
-                nv[c] = (t0 + t1) / 2.f + 0.01f;
-            }
-        }
-        wave_sync();
-#pragma unroll
-        for (int c = 0; c < NV; c++) {
-            const int i = l + 64 * c;
-            if (i < Wn) w[i] = nv[c];
-        }
-    } else {
-        for (int i = l; i < Wn; i += 64) w[i] = w[i] + 1e-5f;
-    }
-    wave_sync();
-    const int nb = S - 1, ns = Wn - 2, nc = ns + 1;
-    for (int i = l; i < nb; i += 64) sc.bins[i] = 0.5f * (sc.z[i] + sc.z[i + 1]);
-    // pdf normaliser: torch's fp32 accumulation order, not the exactly rounded sum (the integer rows depend on it)
-    const float totf = torch_order_sum_lds(w + 1, ns, eps);
-    // cdf = [0, cumsum(pdf)]
+    const int nb = S - 1, ns = Wn - 2;
+    for (int i = l; i < nb; i += 64) bins[i] = 0.5f * (z[i] + z[i + 1]);
+    const float totf = ROW62 ? torch_order_sum_62(w + 1, ns, eps) : torch_order_sum_lds(w + 1, ns, eps);
     double carry = 0.0;
-    if (l == 0) sc.cdf[0] = 0.f;
+    if (l == 0) cdf[0] = 0.f;
     for (int base = 0; base < ns; base += 64) {
         const int i = base + l;
         float pdf = (i < ns) ? (w[1 + i] + eps) / totf : 0.f;
         double incl = wave_scan_f64<false>((double)pdf) + carry;
-        if (i < ns) sc.cdf[i + 1] = (float)incl;
+        if (i < ns) cdf[i + 1] = (float)incl;
         carry = wave_last_f64(incl);
     }
+}
+// searchsorted(right=True): the first of the nc knots with cdf > u
+__device__ __forceinline__ int cdf_search(const float* cdf, int nc, float uu) {
+    int lo = 0, hi = nc;
+    while (lo < hi) {
+        int mid = (lo + hi) >> 1;
+        if (cdf[mid] <= uu) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// the sample of draw u behind knot `ind`: linear in its bin
+__device__ __forceinline__ float cdf_sample(const float* cdf, const float* bins, int nb, int ns, int ind, float uu, int& below, int& above) {
+    const float eps = 1e-5f;
+    below = ind - 1 < 0 ? 0 : ind - 1;
+    above = ind > ns ? ns : ind;
+    const float cb = cdf[below], ca = cdf[above];
+    const float bb = bins[below < nb ? below : nb - 1], ba = bins[above < nb ? above : nb - 1];
+    float denom = ca - cb;
+    if (denom < eps) denom = 1.f;
+    return bb + (uu - cb) / denom * (ba - bb);
+}
+
+// All stages on one ray.  Clobbers sc.w / sc.cdf / sc.bins.  Lane j produces sample j (strided by 64).  `emit(j, sample, ind, below, above)`
+// consumes the results.
+template <typename SC, typename GetU, typename Emit>
+__device__ void importance_lds(SC& sc, int S, int Wn, GetU getu, int N, int mip, Emit emit) {
+    const int l = lane_id();
+    float* w = sc.w;
+    constexpr int CAP = sizeof(sc.z) / sizeof(float), NV = (CAP > MAXS ? CAP : MAXS) / 64;
+    if (mip) {
+        float nv[NV];
+        smooth_read<NV>(w, Wn, nv);
+        wave_sync();
+        smooth_write<NV>(w, Wn, nv);
+    } else {
+        offset_weights(w, Wn);
+    }
+    wave_sync();
+    const int nb = S - 1, ns = Wn - 2, nc = ns + 1;
+    pdf_cdf<false>(sc.z, w, sc.bins, sc.cdf, S, Wn);
     wave_sync();
     for (int j = l; j < N; j += 64) {
         const float uu = getu(j);
-        int lo = 0, hi = nc;                       // searchsorted(right=True): first index with cdf > u
-        while (lo < hi) {
-            int mid = (lo + hi) >> 1;
-            if (sc.cdf[mid] <= uu) lo = mid + 1; else hi = mid;
-        }
-        const int ind = lo;
-        const int below = ind - 1 < 0 ? 0 : ind - 1;
-        const int above = ind > ns ? ns : ind;
-        const float cb = sc.cdf[below], ca = sc.cdf[above];
-        const float bb = sc.bins[below < nb ? below : nb - 1], ba = sc.bins[above < nb ? above : nb - 1];
-        float denom = ca - cb;
-        if (denom < eps) denom = 1.f;
-        const float smp = bb + (uu - cb) / denom * (ba - bb);
+        const int ind = cdf_search(sc.cdf, nc, uu);
+        int below, above;
+        const float smp = cdf_sample(sc.cdf, sc.bins, nb, ns, ind, uu, below, above);
         emit(j, smp, ind, below, above);
     }
 }
@@ -401,30 +492,31 @@ __device__ __forceinline__ void stable_ranks_n(const float* key, int M, int* ran
         }
     }
 }
-__device__ __forceinline__ void stable_ranks(const float* key, int M, int* rank /* per-lane, MAXS/64 entries */) {
-#pragma unroll
-    for (int c = 0; c < MAXS / 64; c++) rank[c] = 0;
-    if (M <= 64) stable_ranks_n<1>(key, M, rank);
-    else if (M <= 128) stable_ranks_n<2>(key, M, rank);
-    else if (M <= 192) stable_ranks_n<3>(key, M, rank);
-    else stable_ranks_n<4>(key, M, rank);
-}
-
-// The same for the long lists (M <= MAXS_LONG): 8 or 16 value slots per lane.  O(M^2 / 64) per lane -- the fallback for lists that
-// are not ascending, and unify_samples' rank (not on the renderer's forward).
+// The dispatcher over NS for a lane's NR rank slots: NR = MAXS / 64 (the short kernels: 1..4 slots in use), or 8 / 16 for the long lists
+// (M <= MAXS_LONG).  O(M^2 / 64) per lane -- the fallback for lists that are not ascending, and unify_samples' rank (not on the
+// renderer's forward).
 template <int NR>
-__device__ __forceinline__ void stable_ranks_long(const float* key, int M, int (&rank)[NR]) {
-    static_assert(NR == MAXS_PASS / 64 || NR == MAXS_LONG / 64, "stable_ranks_long: 8 or 16 slots");
+__device__ __forceinline__ void stable_ranks(const float* key, int M, int (&rank)[NR]) {
+    static_assert(NR == MAXS / 64 || NR == MAXS_PASS / 64 || NR == MAXS_LONG / 64, "stable_ranks: 4, 8 or 16 slots");
 #pragma unroll
     for (int c = 0; c < NR; c++) rank[c] = 0;
-    if (M <= MAXS_PASS) stable_ranks_n<MAXS_PASS / 64>(key, M, rank);
-    else stable_ranks_n<NR>(key, M, rank);
+    if constexpr (NR == MAXS / 64) {
+        if (M <= 64) stable_ranks_n<1>(key, M, rank);
+        else if (M <= 128) stable_ranks_n<2>(key, M, rank);
+        else if (M <= 192) stable_ranks_n<3>(key, M, rank);
+        else stable_ranks_n<4>(key, M, rank);
+    } else {
+        if (M <= MAXS_PASS) stable_ranks_n<MAXS_PASS / 64>(key, M, rank);
+        else stable_ranks_n<NR>(key, M, rank);
+    }
 }
 
-// Bitonic sort of 64 * NS (key, index) pairs, NS per lane (element e = 64 c + lane), ascending by (key, index): the network of
-// wave_bitonic_sort2 below for any power-of-two NS.  Stages with j >= 64 are compare-exchanges between two slots of the same lane,
-// the others one pair of cross-lane permutes per slot.  Indices are unique, so the order is total and the result is the stable sort.
-// For 128 < N <= 512 fine samples (long rays): 45 stages at NS = 8, against 512 broadcasts x 8 slots of the brute-force rank.
+// Bitonic sort of 64 * NS (key, index) pairs, NS per lane (element e = 64 c + lane), ascending by (key, index), for any power-of-two NS.
+// Stages with j >= 64 are compare-exchanges between two slots of the same lane, the others one pair of cross-lane permutes (ds_bpermute,
+// LDS pipe) + ~5 VALU per slot.  Indices are unique, so the order is total and the result is the stable sort.
+//   NS = 1: 21 stages -- a third of the vector work of the brute-force rank above for 64 keys;
+//   NS = 2: 28 stages, for 64 < N <= 128 fine samples (BASELINE configs[4]: 96) instead of N broadcasts x 2 slots;
+//   NS = 4, 8: 128 < N <= 512 fine samples (long rays): 45 stages at NS = 8, against 512 broadcasts x 8 slots of the brute-force rank.
 template <int NS, int CAP>
 __device__ __forceinline__ void wave_bitonic_sort_n(float (&key)[CAP], int (&idx)[CAP]) {
     static_assert(NS <= CAP && (NS & (NS - 1)) == 0, "wave_bitonic_sort_n: NS a power of two within the arrays");
@@ -449,50 +541,6 @@ __device__ __forceinline__ void wave_bitonic_sort_n(float (&key)[CAP], int (&idx
                     const float pk = __shfl_xor(key[c], j, 64);
                     const int pi = __shfl_xor(idx[c], j, 64);
                     const bool asc = ((64 * c + l) & k) == 0;
-                    const bool keep_min = ((l & j) == 0) == asc;
-                    const bool partner_less = pk < key[c] || (pk == key[c] && pi < idx[c]);
-                    if (partner_less == keep_min) { key[c] = pk; idx[c] = pi; }
-                }
-            }
-        }
-    }
-}
-
-// Bitonic sort of one (key, index) pair per lane across the 64 lanes of a wave, ascending by (key, index): 21 compare-exchange
-// stages, each two ds_bpermute (LDS pipe) + ~5 VALU -- a third of the vector work of the brute-force rank above for 64 keys.
-// Indices are unique, so the order is total and the result is the stable sort.
-__device__ __forceinline__ void wave_bitonic_sort(float& key, int& idx) {
-    const int l = lane_id();
-#pragma unroll
-    for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const float pk = __shfl_xor(key, j, 64);
-            const int pi = __shfl_xor(idx, j, 64);
-            const bool keep_min = ((l & j) == 0) == ((l & k) == 0);        // lower lane of an ascending pair / upper lane of a descending one
-            const bool partner_less = pk < key || (pk == key && pi < idx);
-            if (partner_less == keep_min) { key = pk; idx = pi; }
-        }
-    }
-}
-
-// The same network over 128 (key, index) pairs, two per lane (element e = 64 c + lane): 28 stages, the j = 64 stage is a compare-exchange
-// inside the lane.  For 64 < N <= 128 fine samples (BASELINE configs[4]: 96) instead of the brute-force rank (N broadcasts x 2 slots).
-__device__ __forceinline__ void wave_bitonic_sort2(float (&key)[2], int (&idx)[2]) {
-    const int l = lane_id();
-#pragma unroll
-    for (int k = 2; k <= 128; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            if (j == 64) {                                  // k = 128: ascending everywhere; slot 0 keeps the smaller
-                const bool less1 = key[1] < key[0] || (key[1] == key[0] && idx[1] < idx[0]);
-                if (less1) { const float tk = key[0]; key[0] = key[1]; key[1] = tk; const int ti = idx[0]; idx[0] = idx[1]; idx[1] = ti; }
-            } else {
-#pragma unroll
-                for (int c = 0; c < 2; c++) {
-                    const float pk = __shfl_xor(key[c], j, 64);
-                    const int pi = __shfl_xor(idx[c], j, 64);
-                    const bool asc = k == 128 ? true : (k == 64 ? c == 0 : ((l & k) == 0));     // (e & k) == 0: bit 6 of e is the slot, bit 7 is never set
                     const bool keep_min = ((l & j) == 0) == asc;
                     const bool partner_less = pk < key[c] || (pk == key[c] && pi < idx[c]);
                     if (partner_less == keep_min) { key[c] = pk; idx[c] = pi; }
@@ -582,11 +630,12 @@ __global__ __launch_bounds__(256) void importance_from_coarse_kernel(const float
                 return;
             }
         }
-        int idx = l;
-        wave_bitonic_sort(key, idx);
+        float k1[1] = {key};
+        int idx[1] = {l};
+        wave_bitonic_sort_n<1>(k1, idx);
         if (l < N) {
-            tfine[r * N + l] = key;
-            if (fine_perm) fine_perm[r * N + l] = idx;
+            tfine[r * N + l] = k1[0];
+            if (fine_perm) fine_perm[r * N + l] = idx[0];
         }
         return;
     }
@@ -622,7 +671,7 @@ __global__ __launch_bounds__(256) void importance_from_coarse_kernel(const float
             }
         }
         int idx[2] = {l, l + 64};
-        wave_bitonic_sort2(key, idx);
+        wave_bitonic_sort_n<2>(key, idx);
 #pragma unroll
         for (int c = 0; c < 2; c++) {
             const int pos = l + 64 * c;
@@ -679,8 +728,7 @@ __global__ __launch_bounds__(256) void unify_kernel(const float* __restrict__ d1
     for (int i = l; i < M; i += 64) sc.z[i] = i < S1 ? d1[r * S1 + i] : d2[r * S2 + (i - S1)];
     wave_sync();
     int rank[MS / 64];
-    if constexpr (MS > MAXS) stable_ranks_long(sc.z, M, rank);
-    else stable_ranks(sc.z, M, rank);
+    stable_ranks(sc.z, M, rank);
 #pragma unroll
     for (int cc = 0; cc < MS / 64; cc++) {
         const int i = l + 64 * cc;
@@ -727,8 +775,7 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(const float* __res
     constexpr int RK = (MS > MAXS ? MS : MAXS) / 64;
     int rank[RK];
     if (__any(bad)) {
-        if constexpr (MS > MAXS) stable_ranks_long(sc.cdf, M, rank);
-        else stable_ranks(sc.cdf, M, rank);
+        stable_ranks(sc.cdf, M, rank);
     } else {
         // Ranks of a stable merge of two ascending lists (coarse wins ties).
         //   fine element j:    its own index + #coarse <= f_j  =: j + cnt_j     -- a binary search in the coarse list;
@@ -841,34 +888,13 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(const float* __res
 // hardware's 8 waves per SIMD with half the register file empty, and what bounds them is the length of one ray's chain of dependent
 // LDS / cross-lane steps; here every phase is a function of ONE ray's state, fence-free inside, called for ray A and then for ray B
 // with the wave fence after both, so the scheduler has two independent chains to interleave and the global loads of both rays are
-// out before anything waits.  Per ray the operations and their order are those of the one-ray kernels (the loops below are the
-// same loops with their trip counts at 64 / 128 written out and their branches as selects): the same bits.  The slow paths (the
+// out before anything waits.  The importance phases and the marches are the one-ray kernels' stage functions / statements at S = N = 64 and
+// M = 128; the file header names the specialised copies that remain and why.  Per ray the same operations in the same order: the same bits.
+// The slow paths (the
 // bitonic network after a key collision, the brute-force rank of a list that is not ascending) are wave-uniform branches per ray.
 // An odd last ray: its wave computes it twice (B = A) and B stores nothing.
 // ------------------------------------------------------------------------------------------------
 constexpr int PAIR_RAYS_PER_BLOCK = 8;
-
-// alpha_i and the transmittance factor of sample i of an LDS-resident list of S samples: march_classical_lds' / march_mip_lds' own expressions.
-__device__ __forceinline__ void classical_alpha(const float* z, const float* sig, int i, int S, int flags, float cut_thr, float& alpha, float& fac) {
-    const float delta = (i < S - 1) ? (z[i + 1] - z[i]) : ((flags & 1) ? 1e10f : 1e-3f);
-    float sp = (flags & 8) ? (sig[i] > 0.f ? sig[i] : 0.f) : softplus20f(sig[i]);
-    if (sp < cut_thr) sp = 0.f;
-    alpha = 1.0f - expf(-(delta * sp));
-    fac = (1.0f - alpha) + 1e-10f;
-}
-__device__ __forceinline__ void mip_alpha(const float* z, const float* sig, int i, int S, int M, float density_bias, float cut_thr, float& alpha, float& fac) {
-    alpha = 0.f; fac = 1.0f;
-    if (i < M) {
-        float delta, smid;
-        if (i < S - 1) { delta = z[i + 1] - z[i]; smid = (sig[i] + sig[i + 1]) / 2.f; }
-        else { delta = 1e10f; smid = sig[S - 1]; }
-        float sp = softplus20f(smid + density_bias);
-        if (sp < cut_thr) sp = 0.f;
-        const float dd = sp * delta;
-        alpha = 1.0f - expf(-dd);
-        fac = (1.0f - alpha) + 1e-10f;
-    }
-}
 
 // Importance form.  Scratch: z, sig, w, cdf, bins and the key column at 64 entries = 1552 B per ray, 12.4 KB per block; 8 blocks per CU
 // (99 KB of LDS) = 8 waves = 16 rays per SIMD, twice the one-ray form's.
@@ -879,9 +905,9 @@ struct ImpRay {
     int64_t r;          // the ray (B of an odd last pair: A's ray again)
     bool live;          // this ray stores its results
     float zl, sg, u;    // lane l's coarse depth, density and draw
-    float nv;           // mip: the smoothed weight between its read and its write
-    float key;          // lane l's fine sample in t-space (draw order), then the sample sorted to position l
-    int cnt, idx;       // the number of smaller keys; the draw index sorted to position l
+    float nv[1];        // mip: the smoothed weight between its read and its write
+    float key[1];       // lane l's fine sample in t-space (draw order), then the sample sorted to position l
+    int cnt, idx[1];    // the number of smaller keys; the draw index sorted to position l (key, idx: the one slot of wave_bitonic_sort_n<1>)
 };
 
 __device__ __forceinline__ void imp_load(ImpRay& R, const float* __restrict__ rgbs, const float* __restrict__ sdist, const float* __restrict__ u_fine) {
@@ -894,96 +920,27 @@ __device__ __forceinline__ float imp_march(ImpRay& R, int marcher, int flags, fl
     const int l = lane_id();
     const int M = (marcher == 0 || (flags & 1)) ? 64 : 63;
     float alpha, fac;
-    if (marcher == 0) classical_alpha(R.sc->z, R.sc->sig, l, 64, flags, cut_thr, alpha, fac);
-    else mip_alpha(R.sc->z, R.sc->sig, l, 64, M, density_bias, cut_thr, alpha, fac);
+    const float *z = R.sc->z, *sig = R.sc->sig;
+    if (marcher == 0) { TDGP_CLASSICAL_ALPHA(false, z, sig, l, 64, flags, cut_thr, alpha, fac); }
+    else { TDGP_MIP_ALPHA(false, z, sig, l, 64, M, density_bias, cut_thr, alpha, fac); }
     const double carry = 1.0;
-    const double incl64 = wave_scan_f64<true>((double)fac) * carry;
-    const float incl = (float)incl64;
-    const float excl = wave_shr1_f32(incl, (float)carry);
-    const float wi = alpha * excl;
+    TDGP_MARCH_PASS(wi, incl64, alpha, fac, carry)
     float wsum = 0.0f;
     if (l < M) { R.sc->w[l] = wi; wsum += wi; }
     return wave_sum_f32(wsum);
 }
 __device__ __forceinline__ void imp_last_back(ImpRay& R, float wagg) { if (lane_id() == 0) R.sc->w[63] += (1.0f - wagg); }
-// importance_lds' smoothing (mip: in two steps around a fence) or offset of the weights
-__device__ __forceinline__ void imp_smooth_read(ImpRay& R, int Wn) {
-    const int i = lane_id();
-    const float* w = R.sc->w;
-    if (i < Wn) {
-        const float a = (i - 1 >= 0) ? w[i - 1] : -INFINITY, b = w[i], d = (i + 1 < Wn) ? w[i + 1] : -INFINITY;
-        const float t0 = a > b ? a : b, t1 = b > d ? b : d;
-        R.nv = (t0 + t1) / 2.f + 0.01f;
-    }
-}
-__device__ __forceinline__ void imp_smooth_write(ImpRay& R, int Wn) { const int i = lane_id(); if (i < Wn) R.sc->w[i] = R.nv; }
-__device__ __forceinline__ void imp_offset(ImpRay& R, int Wn) { const int i = lane_id(); if (i < Wn) R.sc->w[i] = R.sc->w[i] + 1e-5f; }
-// torch_order_sum_lds for 56 <= n <= 62 (a pdf row of 61 or 62 entries): nv = 7 vectors, one interleaved group, vectors 4..6 into accumulator 0, n - 56 tail elements
-__device__ __forceinline__ float torch_order_sum_62(const float* w1, int n, float eps) {
-    const int l = lane_id();
-    const int col = l & 7, a = (l >> 3) & 3;
-    float acc = 0.f;
-    acc = __fadd_rn(acc, __fadd_rn(w1[a * 8 + col], eps));
-#pragma unroll
-    for (int j = 4; j < 7; j++) {
-        const float v = __fadd_rn(w1[j * 8 + col], eps);
-        if (a == 0) acc = __fadd_rn(acc, v);
-    }
-    float p = __shfl(acc, col, 64);
-    p = __fadd_rn(p, __shfl(acc, col + 8, 64));
-    p = __fadd_rn(p, __shfl(acc, col + 16, 64));
-    p = __fadd_rn(p, __shfl(acc, col + 24, 64));
-    float fin = 0.f;
-#pragma unroll
-    for (int k = 56; k < 62; k++) {
-        const float t = __fadd_rn(fin, __fadd_rn(w1[k], eps));
-        fin = k < n ? t : fin;
-    }
-#pragma unroll
-    for (int c = 0; c < 8; c++) fin = __fadd_rn(fin, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), c)));
-    return fin;
-}
-// bins, pdf normaliser (torch's order), cdf = [0, cumsum(pdf)] as the fp64 scan rounded per prefix
-__device__ __forceinline__ void imp_cdf(ImpRay& R, int Wn) {
-    const int l = lane_id();
-    const float eps = 1e-5f;
-    ImpPairScratch& sc = *R.sc;
-    const int ns = Wn - 2;
-    if (l < 63) sc.bins[l] = 0.5f * (sc.z[l] + sc.z[l + 1]);
-    const float totf = torch_order_sum_62(sc.w + 1, ns, eps);
-    const double carry = 0.0;
-    if (l == 0) sc.cdf[0] = 0.f;
-    const float pdf = (l < ns) ? (sc.w[1 + l] + eps) / totf : 0.f;
-    const double incl = wave_scan_f64<false>((double)pdf) + carry;
-    if (l < ns) sc.cdf[l + 1] = (float)incl;
-}
-// searchsorted(right=True) of lane l's draw in the nc <= 63 knots (6 halvings empty any such interval: the loop of importance_lds with a
-// fixed trip count), the sample, its t-space key into the key column
+// cdf_search of lane l's draw, the sample, its t-space key into the key column
 __device__ __forceinline__ void imp_search(ImpRay& R, int Wn, float t_near, float t_far, float* __restrict__ sfine, int32_t* __restrict__ inds) {
     const int l = lane_id();
-    const float eps = 1e-5f;
     ImpPairScratch& sc = *R.sc;
-    const int nb = 63, ns = Wn - 2, nc = ns + 1;
+    const int ns = Wn - 2, nc = ns + 1;
     const float uu = R.u;
-    int lo = 0, hi = nc;
-#pragma unroll
-    for (int it = 0; it < 6; it++) {
-        const bool open = lo < hi;
-        const int mid = (lo + hi) >> 1;
-        const bool right = sc.cdf[open ? mid : 0] <= uu;
-        lo = (open && right) ? mid + 1 : lo;
-        hi = (open && !right) ? mid : hi;
-    }
-    const int ind = lo;
-    const int below = ind - 1 < 0 ? 0 : ind - 1;
-    const int above = ind > ns ? ns : ind;
-    const float cb = sc.cdf[below], ca = sc.cdf[above];
-    const float bb = sc.bins[below < nb ? below : nb - 1], ba = sc.bins[above < nb ? above : nb - 1];
-    float denom = ca - cb;
-    if (denom < eps) denom = 1.f;
-    const float smp = bb + (uu - cb) / denom * (ba - bb);
-    R.key = s2t(smp, t_near, t_far);
-    sc.key[l] = R.key;
+    const int ind = cdf_search(sc.cdf, nc, uu);
+    int below, above;
+    const float smp = cdf_sample(sc.cdf, sc.bins, 63, ns, ind, uu, below, above);
+    R.key[0] = s2t(smp, t_near, t_far);
+    sc.key[l] = R.key[0];
     if (R.live) {
         if (sfine) sfine[R.r * 64 + l] = smp;
         if (inds) inds[R.r * 64 + l] = ind;
@@ -996,7 +953,7 @@ __device__ __forceinline__ void imp_count(ImpRay& R) {
 #pragma unroll
     for (int jj = 0; jj < 16; jj++) {
         const float4 k4 = *(const float4*)&R.sc->key[4 * jj];
-        cnt += (k4.x < R.key ? 1 : 0) + (k4.y < R.key ? 1 : 0) + (k4.z < R.key ? 1 : 0) + (k4.w < R.key ? 1 : 0);
+        cnt += (k4.x < R.key[0] ? 1 : 0) + (k4.y < R.key[0] ? 1 : 0) + (k4.z < R.key[0] ? 1 : 0) + (k4.w < R.key[0] ? 1 : 0);
     }
     R.cnt = cnt;
     ((int*)R.sc->bins)[cnt] = l;            // bins is free since imp_search
@@ -1007,15 +964,15 @@ __device__ __forceinline__ bool imp_gather(ImpRay& R) {
     const int* slot = (const int*)R.sc->bins;
     const bool ok = __all(slot[R.cnt] == l);
     const int src = ok ? slot[l] : l;
-    R.key = R.sc->key[src];
-    R.idx = src;
+    R.key[0] = R.sc->key[src];
+    R.idx[0] = src;
     return ok;
 }
 __device__ __forceinline__ void imp_store(const ImpRay& R, float* __restrict__ tfine, int32_t* __restrict__ fine_perm) {
     const int l = lane_id();
     if (R.live) {
-        tfine[R.r * 64 + l] = R.key;
-        if (fine_perm) fine_perm[R.r * 64 + l] = R.idx;
+        tfine[R.r * 64 + l] = R.key[0];
+        if (fine_perm) fine_perm[R.r * 64 + l] = R.idx[0];
     }
 }
 
@@ -1041,23 +998,23 @@ __global__ __launch_bounds__(256, 8) void importance_from_coarse_pair_kernel(con
     if (marcher == 0) {
         if (flags & 2) { imp_last_back(A, waA); imp_last_back(B, waB); }
         wave_sync();
-        imp_offset(A, Wn); imp_offset(B, Wn);
+        offset_weights(A.sc->w, Wn); offset_weights(B.sc->w, Wn);
     } else {
         Wn = (flags & 1) ? 64 : 63;
-        imp_smooth_read(A, Wn); imp_smooth_read(B, Wn);
+        smooth_read<1>(A.sc->w, Wn, A.nv); smooth_read<1>(B.sc->w, Wn, B.nv);
         wave_sync();
-        imp_smooth_write(A, Wn); imp_smooth_write(B, Wn);
+        smooth_write<1>(A.sc->w, Wn, A.nv); smooth_write<1>(B.sc->w, Wn, B.nv);
     }
     wave_sync();
-    imp_cdf(A, Wn); imp_cdf(B, Wn);
+    pdf_cdf<true>(A.sc->z, A.sc->w, A.sc->bins, A.sc->cdf, 64, Wn); pdf_cdf<true>(B.sc->z, B.sc->w, B.sc->bins, B.sc->cdf, 64, Wn);
     wave_sync();
     imp_search(A, Wn, t_near, t_far, sfine, inds); imp_search(B, Wn, t_near, t_far, sfine, inds);
     wave_sync();
     imp_count(A); imp_count(B);
     wave_sync();
     const bool okA = imp_gather(A), okB = imp_gather(B);
-    if (!okA) wave_bitonic_sort(A.key, A.idx);      // per ray: the other one is done
-    if (!okB) wave_bitonic_sort(B.key, B.idx);
+    if (!okA) wave_bitonic_sort_n<1>(A.key, A.idx);      // per ray: the other one is done
+    if (!okB) wave_bitonic_sort_n<1>(B.key, B.idx);
     imp_store(A, tfine, fine_perm); imp_store(B, tfine, fine_perm);
 }
 
@@ -1142,12 +1099,8 @@ __device__ __forceinline__ void mrg_march(MergeRay& R, int marcher, int flags, f
     if (marcher == 0) {
         float alpha[2], fac[2];
 #pragma unroll
-        for (int c = 0; c < 2; c++) classical_alpha(sc.z, sc.sig, 64 * c + l, 128, flags, cut_thr, alpha[c], fac[c]);
-        const double s0 = wave_scan_f64<true>((double)fac[0]), s1 = wave_scan_f64<true>((double)fac[1]);
-        const double c1 = wave_last_f64(s0);
-        const double i1 = s1 * c1;
-        const float incl0 = (float)s0, incl1 = (float)i1;
-        const float wi0 = alpha[0] * wave_shr1_f32(incl0, 1.0f), wi1 = alpha[1] * wave_shr1_f32(incl1, (float)c1);
+        for (int c = 0; c < 2; c++) { const int i = 64 * c + l; TDGP_CLASSICAL_ALPHA(false, sc.z, sc.sig, i, 128, flags, cut_thr, alpha[c], fac[c]); }
+        TDGP_MARCH_PASS2(wi0, wi1, i1, alpha, fac)
         w[l] = wi0; wsum += wi0;
         w[64 + l] = wi1; wsum += wi1;
         carry = wave_last_f64(i1);
@@ -1157,11 +1110,8 @@ __device__ __forceinline__ void mrg_march(MergeRay& R, int marcher, int flags, f
         for (int base = 0; base < 128; base += 64) {
             const int i = base + l;
             float alpha, fac;
-            mip_alpha(sc.z, sc.sig, i, 128, M, density_bias, cut_thr, alpha, fac);
-            const double incl64 = wave_scan_f64<true>((double)fac) * carry;
-            const float incl = (float)incl64;
-            const float excl = wave_shr1_f32(incl, (float)carry);
-            const float wi = alpha * excl;
+            TDGP_MIP_ALPHA(false, sc.z, sc.sig, i, 128, M, density_bias, cut_thr, alpha, fac);
+            TDGP_MARCH_PASS(wi, incl64, alpha, fac, carry)
             if (i < M) { w[i] = wi; wsum += wi; }
             carry = wave_last_f64(incl64);
         }
@@ -1243,8 +1193,14 @@ __global__ __launch_bounds__(256, 8) void merge_composite_pair_kernel(const floa
     mrg_composite(A, marcher, flags, waA, fTA, rgb, depth_o, wsum_o, final_T); mrg_composite(B, marcher, flags, waB, fTB, rgb, depth_o, wsum_o, final_T);
 }
 
-inline int ray_blocks(int64_t rays) { return (int)cdiv64(rays, RAYS_PER_BLOCK); }
-inline int pair_blocks(int64_t rays) { return (int)cdiv64(rays, PAIR_RAYS_PER_BLOCK); }
+// The launch of every per-ray kernel family: `kernel` is the instantiation the entry point selected (all instantiations of a family share
+// one signature), one wave per ray and RAYS_PER_BLOCK rays per block; the pair forms pass their own rays per block.  A statement of
+// the entry point: it reads its `rays` and `stream`, and like TDGP_LAUNCH_CHECK returns from it only on a launch error.
+#define TDGP_LAUNCH_RAYS(NAME, KERNEL, PER_BLOCK, ...)                                                                                   \
+    do {                                                                                                                                 \
+        TDGP_LAUNCH(NAME, KERNEL, dim3((int)cdiv64(rays, PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);                   \
+        TDGP_LAUNCH_CHECK();                                                                                                             \
+    } while (0)
 
 }  // namespace
 
@@ -1286,13 +1242,8 @@ TDGP_API int tdgp_ray_march(const float* colors, const float* densities, const f
     TDGP_CHECK(marcher == 0 || marcher == 1, TDGP_EINVAL, "ray_march: unknown ray marcher %d", marcher);
     TDGP_FAULT_CHECK("ray_march");
     if (rays == 0) return TDGP_OK;
-    if (S <= MAXS)
-        TDGP_LAUNCH("ray_march_kernel", ray_march_kernel<MAXS>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, colors, densities, depths, rgb, depth, weights,
-                    final_T, rays, S, C, marcher, flags, density_bias, cut_threshold);
-    else
-        TDGP_LAUNCH("ray_march_kernel", ray_march_kernel<MAXS_LONG>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, colors, densities, depths, rgb, depth,
-                    weights, final_T, rays, S, C, marcher, flags, density_bias, cut_threshold);
-    TDGP_LAUNCH_CHECK();
+    TDGP_LAUNCH_RAYS("ray_march_kernel", S <= MAXS ? ray_march_kernel<MAXS> : ray_march_kernel<MAXS_LONG>, RAYS_PER_BLOCK, colors, densities, depths, rgb, depth,
+                     weights, final_T, rays, S, C, marcher, flags, density_bias, cut_threshold);
     return TDGP_OK;
 }
 
@@ -1303,13 +1254,8 @@ TDGP_API int tdgp_sample_importance(const float* z, const float* weights, const 
     TDGP_CHECK(S >= 4 && S <= MAXS_PASS && Wn >= 3 && Wn <= S && N >= 1, TDGP_EUNSUPPORTED,
                "sample_importance: bad S=%d Wn=%d N=%d (S at most %d: beyond it torch's sum order is not restated)", S, Wn, N, MAXS_PASS);
     if (rays == 0) return TDGP_OK;
-    if (S <= MAXS)
-        TDGP_LAUNCH("sample_importance_kernel", sample_importance_kernel<MAXS>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, z, weights, u, samples, inds,
-                    below, above, cdf, rays, S, Wn, N, marcher);
-    else
-        TDGP_LAUNCH("sample_importance_kernel", sample_importance_kernel<MAXS_PASS>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, z, weights, u, samples,
-                    inds, below, above, cdf, rays, S, Wn, N, marcher);
-    TDGP_LAUNCH_CHECK();
+    TDGP_LAUNCH_RAYS("sample_importance_kernel", S <= MAXS ? sample_importance_kernel<MAXS> : sample_importance_kernel<MAXS_PASS>, RAYS_PER_BLOCK, z, weights, u,
+                     samples, inds, below, above, cdf, rays, S, Wn, N, marcher);
     return TDGP_OK;
 }
 
@@ -1318,12 +1264,8 @@ TDGP_API int tdgp_unify_samples(const float* d1, const float* c1, const float* s
     TDGP_CHECK(d1 && c1 && s1 && d2 && c2 && s2 && d && c && s, TDGP_EINVAL, "unify_samples: null pointer");
     TDGP_CHECK(S1 >= 1 && S2 >= 1 && S1 + S2 <= MAXS_LONG, TDGP_EUNSUPPORTED, "unify_samples: S1+S2=%d > %d", S1 + S2, MAXS_LONG);
     if (rays == 0) return TDGP_OK;
-    if (S1 + S2 <= MAXS)
-        TDGP_LAUNCH("unify_kernel", unify_kernel<MAXS>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, d1, c1, s1, S1, d2, c2, s2, S2, d, c, s, perm, rays, C);
-    else
-        TDGP_LAUNCH("unify_kernel", unify_kernel<MAXS_LONG>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, d1, c1, s1, S1, d2, c2, s2, S2, d, c, s, perm, rays,
-                    C);
-    TDGP_LAUNCH_CHECK();
+    TDGP_LAUNCH_RAYS("unify_kernel", S1 + S2 <= MAXS ? unify_kernel<MAXS> : unify_kernel<MAXS_LONG>, RAYS_PER_BLOCK, d1, c1, s1, S1, d2, c2, s2, S2, d, c, s, perm,
+                     rays, C);
     return TDGP_OK;
 }
 
@@ -1335,19 +1277,15 @@ TDGP_API int tdgp_importance_from_coarse(const float* rgbs_coarse, const float* 
     TDGP_CHECK(marcher == 0 || marcher == 1, TDGP_EINVAL, "importance_from_coarse: unknown ray marcher %d", marcher);
     TDGP_FAULT_CHECK("importance_from_coarse");
     if (rays == 0) return TDGP_OK;
-    if (S == 64 && N == 64)         // the generator's 64 + 64: two rays per wave
-        TDGP_LAUNCH("importance_from_coarse_kernel", importance_from_coarse_pair_kernel, dim3(pair_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, sdist,
-                    u_fine, tdist_fine, sdist_fine, inds, fine_perm, rays, marcher, flags, density_bias, cut_threshold, t_near, t_far);
-    else if (S <= 128 && N <= 128)
-        TDGP_LAUNCH("importance_from_coarse_kernel", importance_from_coarse_kernel<128>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, sdist,
-                           u_fine, tdist_fine, sdist_fine, inds, fine_perm, rays, S, N, marcher, flags, density_bias, cut_threshold, t_near, t_far);
-    else if (S <= MAXS && N <= MAXS)
-        TDGP_LAUNCH("importance_from_coarse_kernel", importance_from_coarse_kernel<MAXS>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, sdist,
-                           u_fine, tdist_fine, sdist_fine, inds, fine_perm, rays, S, N, marcher, flags, density_bias, cut_threshold, t_near, t_far);
-    else                            // long rays: 16.4 KB of scratch per wave
-        TDGP_LAUNCH("importance_from_coarse_kernel", importance_from_coarse_kernel<MAXS_PASS>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse,
-                    sdist, u_fine, tdist_fine, sdist_fine, inds, fine_perm, rays, S, N, marcher, flags, density_bias, cut_threshold, t_near, t_far);
-    TDGP_LAUNCH_CHECK();
+    if (S == 64 && N == 64) {       // the generator's 64 + 64: two rays per wave (the sizes are the kernel's own)
+        TDGP_LAUNCH_RAYS("importance_from_coarse_kernel", importance_from_coarse_pair_kernel, PAIR_RAYS_PER_BLOCK, rgbs_coarse, sdist, u_fine, tdist_fine, sdist_fine,
+                         inds, fine_perm, rays, marcher, flags, density_bias, cut_threshold, t_near, t_far);
+        return TDGP_OK;
+    }
+    const bool fits = S <= MAXS && N <= MAXS;       // else long rays: 16.4 KB of scratch per wave
+    const auto kernel = (S <= 128 && N <= 128) ? importance_from_coarse_kernel<128> : fits ? importance_from_coarse_kernel<MAXS> : importance_from_coarse_kernel<MAXS_PASS>;
+    TDGP_LAUNCH_RAYS("importance_from_coarse_kernel", kernel, RAYS_PER_BLOCK, rgbs_coarse, sdist, u_fine, tdist_fine, sdist_fine, inds, fine_perm, rays, S, N, marcher,
+                     flags, density_bias, cut_threshold, t_near, t_far);
     return TDGP_OK;
 }
 
@@ -1359,24 +1297,17 @@ TDGP_API int tdgp_merge_composite(const float* rgbs_coarse, const float* t_coars
     TDGP_CHECK(marcher == 0 || marcher == 1, TDGP_EINVAL, "merge_composite: unknown ray marcher %d", marcher);
     TDGP_FAULT_CHECK("merge_composite");
     if (rays == 0) return TDGP_OK;
-    if (S1 == 64 && S2 == 64)       // the generator's 64 + 64: two rays per wave
-        TDGP_LAUNCH("merge_composite_kernel", merge_composite_pair_kernel, dim3(pair_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, t_coarse, rgbs_fine,
-                    t_fine, rgb, depth, wsum, final_T, perm, fine_perm, rays, marcher, flags, density_bias, cut_threshold);
-    else if (S1 + S2 <= 128)
-        TDGP_LAUNCH("merge_composite_kernel", merge_composite_kernel<128>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, t_coarse, S1,
-                           rgbs_fine, t_fine, S2, rgb, depth, wsum, final_T, perm, fine_perm, rays, marcher, flags, density_bias, cut_threshold);
-    else if (S1 + S2 <= 192)        // BASELINE configs[4]: 96 + 96 samples -- three lane slots and 6.2 KB of scratch per wave instead of four and 8.2 KB
-        TDGP_LAUNCH("merge_composite_kernel", merge_composite_kernel<192>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, t_coarse, S1,
-                           rgbs_fine, t_fine, S2, rgb, depth, wsum, final_T, perm, fine_perm, rays, marcher, flags, density_bias, cut_threshold);
-    else if (S1 + S2 <= MAXS)
-        TDGP_LAUNCH("merge_composite_kernel", merge_composite_kernel<MAXS>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, t_coarse, S1,
-                           rgbs_fine, t_fine, S2, rgb, depth, wsum, final_T, perm, fine_perm, rays, marcher, flags, density_bias, cut_threshold);
-    else if (S1 + S2 <= MAXS_PASS)  // long rays up to 256 + 256: 16.4 KB of scratch per wave, twice the occupancy of the form below
-        TDGP_LAUNCH("merge_composite_kernel", merge_composite_kernel<MAXS_PASS>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, t_coarse, S1,
-                    rgbs_fine, t_fine, S2, rgb, depth, wsum, final_T, perm, fine_perm, rays, marcher, flags, density_bias, cut_threshold);
-    else                            // long rays: 32.8 KB of scratch per wave (last[] holds S1 + 1 <= MAXS_LONG entries)
-        TDGP_LAUNCH("merge_composite_kernel", merge_composite_kernel<MAXS_LONG>, dim3(ray_blocks(rays)), dim3(256), 0, (hipStream_t)stream, rgbs_coarse, t_coarse, S1,
-                    rgbs_fine, t_fine, S2, rgb, depth, wsum, final_T, perm, fine_perm, rays, marcher, flags, density_bias, cut_threshold);
-    TDGP_LAUNCH_CHECK();
+    if (S1 == 64 && S2 == 64) {     // the generator's 64 + 64: two rays per wave (the sizes are the kernel's own)
+        TDGP_LAUNCH_RAYS("merge_composite_kernel", merge_composite_pair_kernel, PAIR_RAYS_PER_BLOCK, rgbs_coarse, t_coarse, rgbs_fine, t_fine, rgb, depth, wsum, final_T,
+                         perm, fine_perm, rays, marcher, flags, density_bias, cut_threshold);
+        return TDGP_OK;
+    }
+    // 192: BASELINE configs[4], 96 + 96 samples -- three lane slots and 6.2 KB of scratch per wave instead of four and 8.2 KB.  Long rays: up to 256 + 256
+    // in 16.4 KB per wave, twice the occupancy of the last form's 32.8 KB (last[] holds S1 + 1 <= MAXS_LONG entries)
+    const int M = S1 + S2;
+    const auto kernel = M <= 128 ? merge_composite_kernel<128> : M <= 192 ? merge_composite_kernel<192> : M <= MAXS ? merge_composite_kernel<MAXS>
+                      : M <= MAXS_PASS ? merge_composite_kernel<MAXS_PASS> : merge_composite_kernel<MAXS_LONG>;
+    TDGP_LAUNCH_RAYS("merge_composite_kernel", kernel, RAYS_PER_BLOCK, rgbs_coarse, t_coarse, S1, rgbs_fine, t_fine, S2, rgb, depth, wsum, final_T, perm, fine_perm,
+                     rays, marcher, flags, density_bias, cut_threshold);
     return TDGP_OK;
 }

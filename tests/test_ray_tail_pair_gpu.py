@@ -9,7 +9,9 @@ pairwise tree of the DPP wave sum) -- fp32 additions of the chain's values, so s
 
 Shapes: ray counts around a pair and a block of 8 rays (1, 2, 3, 8, 9) and many blocks with an odd tail (1027); both marchers; every flag;
 planted rays that take a slow path or a degenerate pdf, each at an even and at an odd position of a pair next to an ordinary partner; and the
-neighbouring sizes (64, 32), (32, 64), (96, 96), which keep the one-ray kernels."""
+neighbouring sizes (64, 32), (32, 64), (96, 96), which keep the one-ray kernels.  The planted rays also go through (48, 48) and (96, 96): the
+stages the pair forms share with the one-ray kernels (alpha, march pass, importance stages, bitonic network, brute-force rank) get the same inputs from both
+kinds of caller."""
 import importlib
 
 import numpy as np
@@ -148,16 +150,22 @@ def test_pair_forms_equal_op_chain(native, marcher, flags):
             assert_same_bits(got, want, f'{marcher} flags={flags} rays={rays} cut={cut}')
 
 
+# The stages of the ray tail are written once and called from the pair form (64 + 64), the one-ray MS = 128 forms (48 + 48) and importance MS = 128
+# with merge MS = 192 (96 + 96): the same planted inputs go through every kind of caller.
+STAGE_CALLERS = [(64, 64), (48, 48), (96, 96)]
+
+
+@pytest.mark.parametrize('S,N', STAGE_CALLERS)
 @pytest.mark.parametrize('marcher', ['classical', 'mip'])
-def test_planted_rays_in_a_pair(native, marcher):
+def test_planted_rays(native, marcher, S, N):
     """(a) two equal fine keys from duplicate draws (the bitonic network), (c) an all-zero-density ray (uniform pdf), (d) all density in one
     sample (the fine samples crowd one bin): each at an even and at an odd position of its pair, its partner an ordinary ray."""
     rs = np.random.RandomState(7 + (marcher == 'mip'))
     rays = 16
-    inp = make_inputs(native, rs, rays, 64, 64, marcher)
+    inp = make_inputs(native, rs, rays, S, N, marcher)
     for r in (2, 5):
         inp['u2'][r, 5] = inp['u2'][r, 2]
-        inp['u2'][r, 63] = inp['u2'][r, 0]
+        inp['u2'][r, N - 1] = inp['u2'][r, 0]
     for r in (6, 9):
         inp['rgbs_c'][r, :, 3] = -100.0
     for r in (10, 13):
@@ -168,17 +176,18 @@ def test_planted_rays_in_a_pair(native, marcher):
     assert ties[2] and ties[5] and not ties[[3, 4]].any(), ties                      # exactly one ray of each of those pairs collides
     crowd = (want['inds'][:, :, None] == want['inds'][:, None, :]).sum(2).max(1).values.cpu().numpy()      # most draws sharing one bin, per ray
     assert crowd[10] >= 16 and crowd[13] >= 16 and (crowd[[11, 12]] < 16).all(), crowd
-    assert_same_bits(got, want, f'planted rays, {marcher}')
+    assert_same_bits(got, want, f'planted rays {S}+{N}, {marcher}')
 
 
+@pytest.mark.parametrize('S,N', STAGE_CALLERS)
 @pytest.mark.parametrize('marcher', ['classical', 'mip'])
-def test_unsorted_list_in_a_pair(native, marcher):
+def test_unsorted_list(native, marcher, S, N):
     """(b) tdgp_merge_composite handed lists that are not ascending (the brute-force stable rank): a fine list at an even and at an odd position,
     a coarse list, and a pair whose two rays both are; every partner ascending.  Ties across and inside the lists."""
     rs = np.random.RandomState(11 + (marcher == 'mip'))
     rays = 13
-    inp = make_inputs(native, rs, rays, 64, 64, marcher)
-    t2 = np.sort(rs.uniform(T_NEAR, T_FAR, (rays, 64)).astype(np.float32), axis=1)
+    inp = make_inputs(native, rs, rays, S, N, marcher)
+    t2 = np.sort(rs.uniform(T_NEAR, T_FAR, (rays, N)).astype(np.float32), axis=1)
     t2[:, 9] = s2t(inp['sd']).cpu().numpy()[:, 4]
     t2.sort(axis=1)
     for r in (2, 5, 8, 9):
@@ -189,8 +198,8 @@ def test_unsorted_list_in_a_pair(native, marcher):
     inp['sd'] = T(sd)
     t2 = T(t2)
     want, got = chain(native, inp, marcher, 1, t_fine=t2), fused(native, inp, marcher, 1, t_fine=t2)
-    assert set(want) == {'rgb', 'depth', 'wsum', 'final_T', 'perm'}
-    assert_same_bits(got, want, f'unsorted lists, {marcher}')
+    assert set(want) == {'rgb', 'depth', 'final_T', 'perm'} | ({'wsum'} if S + N <= 128 else set())      # the chain has a wsum up to 128 merged samples
+    assert_same_bits(got, want, f'unsorted lists {S}+{N}, {marcher}')
 
 
 @pytest.mark.parametrize('S,N', [(64, 32), (32, 64), (96, 96)])
