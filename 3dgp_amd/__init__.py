@@ -19,6 +19,7 @@ The directory name starts with a digit, so import it with ``importlib.import_mod
   step_tail            gradient pack / sanitise / norm / Adam and the EMA update as multi-tensor kernels (opt-in)
   dataset              ImageFolderDataset, InfiniteSampler, threaded batch iterator (host code: numpy + PIL)
   training_loop        the training driver: ticks, snapshots, metrics, resume (tools/train.py is its command line)
+  instance_selection   the dataset filter of the ImageNet recipe: Gaussian log-likelihood scores on the fp64 matrix pipe, top-k, folder copy
 """
 from . import config, weights  # noqa: F401  (numpy only)
 from .config import GeneratorConfig  # noqa: F401
@@ -26,7 +27,7 @@ from .config import GeneratorConfig  # noqa: F401
 
 def __getattr__(name):
     # torch-dependent submodules are imported on first use
-    if name in ('_lib', 'ops', 'renderer', 'generator', 'adaptors', 'metrics', 'inference', 'discriminator', 'training', 'compat', 'distributed', 'build', 'graphs', 'geometry', 'augment', 'step_tail', 'dataset', 'training_loop'):
+    if name in ('_lib', 'ops', 'renderer', 'generator', 'adaptors', 'metrics', 'inference', 'discriminator', 'training', 'compat', 'distributed', 'build', 'graphs', 'geometry', 'augment', 'step_tail', 'dataset', 'training_loop', 'instance_selection'):
         import importlib
         return importlib.import_module(f'{__name__}.{name}')
     raise AttributeError(name)

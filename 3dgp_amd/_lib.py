@@ -81,6 +81,9 @@ _PROTOTYPES = {
     'tdgp_pr_member': (c_int, [P, P, c_int64, P, P, P, c_int64, c_int, P, P, c_int64, P]),
     'tdgp_moments_workspace_bytes': (c_int64, [c_int64, c_int]),
     'tdgp_moments_add': (c_int, [P, c_int64, c_int, P, P, P, c_int64, P]),
+    'tdgp_gaussian_maha_mode': (c_int, [c_int64, c_int]),
+    'tdgp_gaussian_maha_workspace_bytes': (c_int64, [c_int64, c_int]),
+    'tdgp_gaussian_maha': (c_int, [P, c_int64, c_int, P, P, P, P, c_int64, P]),
     'tdgp_augment_params': (c_int, [POINTER(c_float), P, c_int, c_int, c_int, c_int, P, P, c_int, c_float, P, P, P, P, P, P]),
     'tdgp_augment_geom': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
     'tdgp_augment_geom_adj_workspace_bytes': (c_int64, [c_int, c_int, c_int, c_int]),

@@ -530,6 +530,33 @@ int     tdgp_pr_member(const uint16_t* probes, const float* probe_norms, int64_t
 int64_t tdgp_moments_workspace_bytes(int64_t n, int F);
 int     tdgp_moments_add(const float* rows, int64_t n, int F, double* s1, double* s2, void* workspace, int64_t workspace_bytes, tdgp_stream_t stream);
 
+/* Gaussian log-likelihood scores of feature rows ("Instance Selection for GANs", scripts/data_scripts/run_instance_selection.py:29-33: scikit-learn's
+ * one-component GaussianMixture, float32 throughout for float32 features): the Mahalanobis part on the device, csrc/gaussian.hip.
+ * rows [n,F] fp32 contiguous; mu [F] fp64; P [F,F] fp64 row-major, UPPER triangular: the precision Cholesky factor P = L^-T with L L^T = Sigma.
+ * No element of P below the diagonal is ever read (the caller may leave anything there).  maha [n] fp64 is overwritten:
+ *   maha[i] = sum_j ( sum_{k <= j} (rows[i,k] - mu[k]) * P[k,j] )^2.
+ * Arithmetic: every row value is widened fp32 -> fp64 (exact); d = x - mu is rounded once in fp64; the contraction runs on
+ *   v_mfma_f64_16x16x4_f64 with fp64 accumulation; squares and their sums are fp64; nothing is held in fp32.  Rows and columns past n or F enter as
+ *   zeros.  A NaN / Inf row value propagates as in IEEE arithmetic into that row's result (0 * Inf = NaN, as numpy's `d @ triu(P)`); no other row
+ *   sees it.
+ * A row's result is a fixed function of that row, mu, P and F: the same bits whatever n is, wherever the row stands in the call and whichever
+ *   mode runs, so a caller may pass rows in chunks of any size.  No atomics, one writer per value: the same bytes on every run.
+ * 64-row x 64-column tiles of y = d P; the K loop of column tile tj stops at min(F, 64 (tj + 1)): the zero half of the triangle costs nothing.
+ * Two modes, a function of (n, F) alone (tdgp_gaussian_maha_mode; -1 for a refused shape):
+ *   TDGP_MAHA_DIRECT  F <= 64, or at least 512 row tiles (n > 32704): one block per row tile walks the column tiles in order and adds each tile's
+ *                     per-row sum of squares q_t to the row's total; the workspace is not touched (16 bytes);
+ *   TDGP_MAHA_SPLIT   otherwise: one block per (row tile, column tile) writes q_t to workspace[t][row]; a merge kernel adds q_0 + q_1 + ... in the
+ *                     same order; the workspace is ceil(F / 64) * n * 8 bytes.
+ * 0 <= n < 2^31 (n = 0: nothing is done), 1 <= F <= 16384, no alignment requirement on F; rows 4-byte, mu / P / maha / workspace 8-byte aligned.
+ * workspace: tdgp_gaussian_maha_workspace_bytes(n, F) bytes (-1 for a shape it refuses), caller-owned.  A refused shape or a workspace that is too
+ * small returns TDGP_EINVAL before anything is launched. */
+#define TDGP_MAHA_DIRECT 0
+#define TDGP_MAHA_SPLIT 1
+int     tdgp_gaussian_maha_mode(int64_t n, int F);
+int64_t tdgp_gaussian_maha_workspace_bytes(int64_t n, int F);
+int     tdgp_gaussian_maha(const float* rows, int64_t n, int F, const double* mu, const double* P, double* maha, void* workspace,
+                           int64_t workspace_bytes, tdgp_stream_t stream);
+
 /* ADA augmentation pipe (src/training/augment.py of the reference), csrc/augment.hip.  All tensors fp32, contiguous, NCHW.
  * tdgp_augment_params: every per-sample parameter in one launch.  cfg: TDGP_AUGMENT_CFG_FLOATS floats on the HOST, the constructor's
  *   arguments in its order (xflip, rotate90, xint, xint_max, scale, rotate, aniso, xfrac, scale_std, rotate_max, aniso_std, xfrac_std,
