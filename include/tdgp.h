@@ -463,6 +463,50 @@ int     tdgp_mcubes_count(const float* volume, int D, int H, int W, float thresh
 int     tdgp_mcubes_emit(const float* volume, int D, int H, int W, float thresh, void* workspace, int64_t workspace_bytes,
                          float* vertices, int64_t V, int32_t* triangles, int64_t T, tdgp_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Shape frames (csrc/iso_surface.hip; nothing in the reference: its scripts/extract_geometry.py stops at a mesh file): the per-ray tail that
+ * turns densities along rays into a surface -- the first crossing of a density level, its refinement, a normal, a shade -- between passes of
+ * the field kernels:  field (ray mode, S) -> tdgp_iso_bracket -> field (ray mode, N) -> tdgp_iso_locate -> field (coords mode, 7 points
+ * per ray) -> tdgp_iso_shade.
+ * Arithmetic contract of all three: every fp32 operation is rounded once, in the order written below (no contraction into FMA); `/` and
+ * sqrtf are correctly rounded; comparisons are ordered (a NaN compares false); one writer per output element, no atomics, no workspace: the
+ * same bytes on every run.  Arguments are checked before any launch; rays == 0 is a no-op.  Limits: 2 <= S <= 512, 1 <= N <= 64 (outside:
+ * TDGP_EINVAL below the lower ends, TDGP_EUNSUPPORTED above the upper ones), rays <= 2^30.
+ * A `sigma` input is a pointer plus an element stride: value i is sigma[i * stride].  Stride 4 on a pointer to column 3 of rows [., 4] (the
+ * field kernels' rgbs) reads them in place, one dword per sample (the cache lines of the whole rows are fetched; nothing is gathered into a
+ * copy).
+ *
+ * tdgp_iso_bracket: sigma [rays,S] (strided), t [rays,S] ascending -> idx int32 [rays], t_fine [rays,N].
+ *   idx = min{k : sigma[k] >= level}, or S if there is none.
+ *   1 <= idx <= S-1, lo = t[idx-1], hi = t[idx]:  t_fine[j] = lo + (hi - lo) * (float(j+1) / float(N)) for j < N-1, t_fine[N-1] = hi exactly
+ *   (the known crossing is always the last fine sample).  idx == 0: every t_fine[j] = t[0].  idx == S: every t_fine[j] = t[S-1] (valid
+ *   depths, ignored later).
+ *
+ * tdgp_iso_locate: the coarse sigma / t, idx, the fine sigma_fine [rays,N] (strided) / t_fine, ray_o / ray_d [rays,3] -> t_hit [rays],
+ *   status int32 [rays], points [rays,7,3].
+ *   idx == S: status 0 (miss), t_hit = t_miss.  idx == 0: status 2 (the level is met at the near plane), t_hit = t[0].  Otherwise status 1:
+ *   j = first fine sample with sigma_fine >= level, else N-1; the high side is fine sample j, the low side fine sample j-1, or the coarse
+ *   sample idx-1 when j == 0;  a = (level - s_lo) / (s_hi - s_lo);  if not (a >= 0 && a <= 1) then a = 1;  t_hit = t_lo + (t_hi - t_lo) * a.
+ *   For every ray, misses included: x_c = o_c + d_c * t_hit; points[0] = x, points[1+2i] = x + h e_i, points[2+2i] = x - h e_i (only
+ *   component i is changed), so that the next field pass is dense.  (An idx outside [0, S] is clamped into it.)
+ *
+ * tdgp_iso_shade: stencil [rays,7,4] (the field's rgbs at `points`), status, ray_d -> rgb [rays,3], normal [rays,3] (may
+ *   be NULL).  light / albedo / background: HOST pointers to 3 floats; light == NULL is a headlight.
+ *   g_i = sigma(+i) - sigma(-i);  q = (gx*gx + gy*gy) + gz*gz;  if q > 0 and q < inf: n_i = (-g_i) / sqrtf(q), else
+ *   n_i = (-d_i) / sqrtf((dx*dx + dy*dy) + dz*dz);  l = light, or that same normalised -d;  c = (nx*lx + ny*ly) + nz*lz;  if not (c > 0)
+ *   then c = 0;  v = ambient + (1 - ambient) * c.
+ *   mode 0 (shaded): out_c = (albedo_c * v) * 2 - 1.  mode 1 (normals): out = n.  mode 2 (colour): k_c = stencil[0].rgb_c * 0.5 + 0.5;
+ *   if not (k_c > 0) then k_c = 0; if k_c > 1 then k_c = 1;  out_c = (k_c * v) * 2 - 1.
+ *   status 0: out = background, normal = 0.  Any other status is shaded as a hit.
+ * --------------------------------------------------------------------------------------------- */
+int tdgp_iso_bracket(const float* sigma, int64_t sigma_stride, const float* t, int64_t rays, int S, int N, float level, int32_t* idx,
+                     float* t_fine, tdgp_stream_t stream);
+int tdgp_iso_locate(const float* sigma, int64_t sigma_stride, const float* t, const int32_t* idx, const float* sigma_fine,
+                    int64_t sigma_fine_stride, const float* t_fine, const float* ray_o, const float* ray_d, int64_t rays, int S, int N,
+                    float level, float h, float t_miss, float* t_hit, int32_t* status, float* points, tdgp_stream_t stream);
+int tdgp_iso_shade(const float* stencil, const int32_t* status, const float* ray_d, int64_t rays, int mode, const float* light, float ambient,
+                   const float* albedo, const float* background, float* rgb, float* normal, tdgp_stream_t stream);
+
 /* Exact order statistics without a sort: the quantile behind the marchers' `cut_quantile` option (tri_plane_renderer.py:324-326, 366-368:
  * torch.quantile of the activated densities; the non-flatness score renders with 0.5, non_flatness_score.py:9-11).
  * out3[0] = sorted(x)[k_lo] and out3[1] = sorted(x)[k_hi], exact bits; out3[2] = torch.lerp(out3[0], out3[1], weight), i.e.

@@ -8,6 +8,8 @@
 in a make_grid (`--nrow auto` = ceil(sqrt(samples))); write it as .gif, .npy or -- with PyAV or torchvision installed -- .mp4.  `--vis image_grid`:
 one strip per sample, its views side by side; .png (the strips stacked into one image) or .npy.  The tri-plane backbone runs once per sample
 (`--plane-batch` samples at a time), every frame is rendered from its sample's planes, and the frames become the uint8 grid on the device.
+`--vis shape_grid` / `--vis shape_strips`: the same two layouts of SHAPE frames -- the surface where the raw density reaches `--level`, found on
+the rays and shaded (`--shape-mode shaded | normals | colour`, `--num-refine`, `--ambient`, `--background`; `--depth` shows the hit depths).
 """
 import argparse
 import importlib
@@ -70,10 +72,15 @@ def build_parser():
     p.add_argument('--pitch-start', type=float, default=np.pi / 2)
     p.add_argument('--pitch-end', type=float, default=np.pi / 2)
     p.add_argument('--posterior-camera', action='store_true', help='a posterior camera sample per seed instead of the mean camera')
-    p.add_argument('--vis', choices=['video_grid', 'image_grid'], default='video_grid')
+    p.add_argument('--vis', choices=['video_grid', 'image_grid', 'shape_grid', 'shape_strips'], default='video_grid')
     p.add_argument('--nrow', default='auto', help="'auto' or an integer (video_grid)")
     p.add_argument('--fps', type=float, default=25)
     p.add_argument('--depth', action='store_true', help='show the depth maps (normalised by the ray range) instead of the colours')
+    p.add_argument('--level', type=float, default=25.0, help='shape frames: the raw density whose surface is shown (extract_geometry\'s thresh_value)')
+    p.add_argument('--shape-mode', choices=['shaded', 'normals', 'colour'], default='shaded')
+    p.add_argument('--num-refine', type=int, default=16, help='shape frames: refinement depths inside the bracket of the first crossing (1..64)')
+    p.add_argument('--ambient', type=float, default=0.2, help='shape frames: ambient share of the shade')
+    p.add_argument('--background', type=float, default=1.0, help='shape frames: grey level of the rays that miss, in [-1, 1]')
     p.add_argument('--img-resolution', type=int, default=None, help='default: the checkpoint\'s')
     p.add_argument('--ray-step-multiplier', type=int, default=1)
     p.add_argument('--force-whiteback', action='store_true')
@@ -82,6 +89,11 @@ def build_parser():
     p.add_argument('--seed', type=int, default=0, help='fixes the non-z randomness (stratified / importance draws, posterior cameras)')
     p.add_argument('--out', required=True, metavar='PATH', help='.gif / .npy / .mp4 (video_grid), .png / .npy (image_grid)')
     return p
+
+
+def shape_options(args):
+    """The options of shapes.render_shape_views, from the command line."""
+    return dict(level=args.level, mode=args.shape_mode, num_refine=args.num_refine, ambient=args.ambient, background=(args.background,) * 3)
 
 
 def main(argv=None):
@@ -104,16 +116,25 @@ def main(argv=None):
     with torch.no_grad():
         ws, z, c = I.sample_ws_from_seeds(G, args.seeds, truncation_psi=args.truncation_psi, device='cuda', classes=args.classes)
         cams = I.generate_camera_params(G, z, c, build_trajectory(args))
+        show = 'depth' if args.depth else 'rgb'
         if args.vis == 'video_grid':
             block = I.render_video_grid(G, ws, cams, nrow=nrow, depth=args.depth, plane_batch=args.plane_batch, as_numpy=True)
+        elif args.vis == 'shape_grid':
+            block = tdgp.shapes.render_shape_video_grid(G, ws, cams, nrow=nrow, show=show, plane_batch=args.plane_batch, as_numpy=True, **shape_options(args))
         else:
-            block = I.render_image_strips(G, ws, cams, depth=args.depth, plane_batch=args.plane_batch, as_numpy=True)
+            if args.vis == 'shape_strips':
+                block = tdgp.shapes.render_shape_strips(G, ws, cams, show=show, plane_batch=args.plane_batch, as_numpy=True, **shape_options(args))
+            else:
+                block = I.render_image_strips(G, ws, cams, depth=args.depth, plane_batch=args.plane_batch, as_numpy=True)
             if not args.out.lower().endswith('.npy'):
                 block = block.reshape(1, -1, *block.shape[2:])                  # the strips under each other: one image
     seconds = time.perf_counter() - t0
     I.save_video(block, args.out, fps=args.fps)
-    print(json.dumps(dict(out=args.out, vis=args.vis, shape=list(block.shape), samples=len(ws), frames=len(cams) // len(ws), trajectory=args.trajectory,
-                          img_resolution=G.synthesis.test_resolution, ray_steps=G.cfg.num_ray_steps, depth=args.depth, seconds=seconds, ckpt=args.ckpt)))
+    line = dict(out=args.out, vis=args.vis, shape=list(block.shape), samples=len(ws), frames=len(cams) // len(ws), trajectory=args.trajectory,
+                img_resolution=G.synthesis.test_resolution, ray_steps=G.cfg.num_ray_steps, depth=args.depth, seconds=seconds, ckpt=args.ckpt)
+    if args.vis.startswith('shape_'):
+        line.update(level=args.level, shape_mode=args.shape_mode, num_refine=args.num_refine)
+    print(json.dumps(line))
 
 
 if __name__ == '__main__':
