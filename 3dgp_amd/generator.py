@@ -597,23 +597,21 @@ class SynthesisNetwork(torch.nn.Module):
                     white_back=cfg.white_back, max_batch_res=render_opts['max_batch_res'], cut_quantile=render_opts['cut_quantile'],
                     density_bias=render_opts['density_bias'])
 
-    def _render_within_field_bound(self, planes, ray_o, ray_d, opts, w):
-        """self.renderer on [B, R = h*w] rays, split where one call would exceed the field kernel's index bound (B * R * max(S, N) points,
-        csrc/field.hip: tdgp_triplane_field): by images first, then -- for an image too large for one call -- by runs of whole image rows
-        (the field kernel keeps walking 4x4-pixel tiles of each run).  Rays are independent: the result is the unsplit call's, bit for bit.
-        -> (rgb [B,R,C], depth [B,R,1])."""
+    def _render_within_field_bound(self, planes, ray_o, ray_d, draws, opts, w):
+        """self.renderer on [B, R = h*w] rays with their explicit `draws` (renderer.Draws), split where one call would exceed the field kernel's
+        index bound (B * R * max(S, N) points, csrc/field.hip: tdgp_triplane_field): by images first, then -- for an image too large for one
+        call -- by runs of whole image rows (the field kernel keeps walking 4x4-pixel tiles of each run).  Rays are independent: the result is
+        the unsplit call's, bit for bit.  -> (rgb [B,R,C], depth [B,R,1])."""
         B, R = ray_o.shape[:2]
         per_ray = max(int(opts['num_proposal_steps']), int(opts['num_fine_steps']))
         if B * R * per_ray <= FIELD_POINTS_MAX:
-            rgb, depth, _w, _T = self.renderer(planes, self.tri_plane_mlp, ray_o, ray_d, opts)
+            rgb, depth, _w, _T = self.renderer(planes, self.tri_plane_mlp, ray_o, ray_d, dict(opts, **draws.opts()))
             return rgb, depth
         if float(opts.get('cut_quantile', 0.0)) > 0.0:
             raise NotImplementedError(f'cut_quantile thresholds over one renderer call; {B} x {R} rays x {per_ray} samples exceed the field kernel\'s '
                                       f'{FIELD_POINTS_MAX} points per call')
         if not isinstance(planes, _renderer.HWCPlanes):
             planes = _renderer.planes_to_hwc(planes)
-        draws = {k: (None if opts.get(k) is None else opts[k].reshape(B, R, -1)) for k in ('u_coarse', 'u_fine', 'n_coarse', 'n_fine')}
-        rgb = depth = None
         h = R // w
         imgs = FIELD_POINTS_MAX // (R * per_ray)
         if imgs >= 1:
@@ -623,19 +621,12 @@ class SynthesisNetwork(torch.nn.Module):
             rows = rows - rows % 4 if rows >= 4 else rows              # whole 4-row tile strips where the bound allows
             assert rows >= 1, f'one image row of {w} rays x {per_ray} samples exceeds the field kernel\'s {FIELD_POINTS_MAX} points per call'
             parts = [(slice(b, b + 1), slice(a * w, min(a + rows, h) * w)) for b in range(B) for a in range(0, h, rows)]
+        out = _renderer.Gather(B, R)
         for bs, rs in parts:
-            o = dict(opts, ray_grid_w=w)
-            for k, t in draws.items():            # the draws of these rays, in the layouts the renderer takes
-                if t is not None:
-                    tc = t[bs, rs].contiguous()
-                    o[k] = tc.reshape(-1, tc.shape[-1]) if k == 'u_fine' else (tc.reshape(tc.shape[0], -1, 1) if k in ('n_coarse', 'n_fine') else tc)
             rgb_c, depth_c, _w, _T = self.renderer(_renderer.HWCPlanes(planes.t[bs]), self.tri_plane_mlp, ray_o[bs, rs].contiguous(),
-                                                   ray_d[bs, rs].contiguous(), o)
-            if rgb is None:
-                rgb = torch.empty([B, R, rgb_c.shape[-1]], dtype=torch.float32, device=ray_o.device)
-                depth = torch.empty([B, R, 1], dtype=torch.float32, device=ray_o.device)
-            rgb[bs, rs], depth[bs, rs] = rgb_c, depth_c
-        return rgb, depth
+                                                   ray_d[bs, rs].contiguous(), dict(opts, ray_grid_w=w, **draws.take(bs, rs).opts()))
+            out.put(bs, rs, rgb=rgb_c, depth=depth_c)
+        return out.result()
 
     @torch.no_grad()
     def compute_densities(self, ws, coords, max_batch_res=32, **block_kwargs):
@@ -692,12 +683,8 @@ class SynthesisNetwork(torch.nn.Module):
             raise RuntimeError('return_depth_adapted / concat_depth need cfg.depth_adaptor')
         if not isinstance(planes, _renderer.HWCPlanes):
             raise TypeError('render_views takes the HWCPlanes that tri_planes returns')
-        cam = camera_params
-        get = (lambda k: cam[k]) if isinstance(cam, dict) else (lambda k: getattr(cam, k))
-        B, BV = int(planes.t.shape[0]), int(get('angles').shape[0])
-        if B < 1 or BV < B or BV % B != 0:
-            raise ValueError(f'{BV} cameras are not a multiple of the plane batch {B} (sample-major: camera n * V + v is view v of sample n)')
-        V = BV // B
+        B, BV = int(planes.t.shape[0]), int(_renderer.cam_get(camera_params)('angles').shape[0])
+        V = _renderer.views_per_sample(BV, B, f'plane batch {B} (sample-major: camera n * V + v is view v of sample n)')
         adapt = (not ray_major and self.depth_adaptor is not None
                  and bool(render_opts['concat_depth'] or render_opts['return_depth_adapted'] or self.strict_nan_propagation))
         if adapt and (ws is None or ws.shape[0] != B):
@@ -706,60 +693,27 @@ class SynthesisNetwork(torch.nn.Module):
             raise ValueError(f'max_rays_per_call must be positive, got {max_rays_per_call!r}')
         h = w = self.test_resolution
         R = h * w
-        dev = planes.t.device
         _lib.require_cuda(planes.t, 'planes')
-        c2w = _renderer.compute_cam2world_matrix(cam)
-        ray_o, ray_d = _renderer.sample_rays(c2w, fov=get('fov'), resolution=(h, w), device=dev)
-        ray_o, ray_d = ray_o.reshape(B, V * R, 3), ray_d.reshape(B, V * R, 3)
+        ray_o, ray_d = (t.reshape(B, V * R, 3) for t in _renderer.camera_rays(camera_params, (h, w)))
         opts = self.rendering_options(render_opts)
         opts['ray_grid_w'] = w                      # V frames of h rows each: one image of V * h rows of w rays per sample
-        opts['n_coarse'] = opts['n_fine'] = None
         S, N = int(opts['num_proposal_steps']), int(opts['num_fine_steps'])
-        uc = None if u_coarse is None else u_coarse.reshape(B, V, R, -1)
-        uf = None if u_fine is None else u_fine.reshape(B, V, R, -1)
+        draws = _renderer.Draws(B, V * R, u_coarse, u_fine)
         max_rays = 16 * R if max_rays_per_call is None else int(max_rays_per_call)
         bstep = B if B * R <= max_rays else max(1, max_rays // R)          # a plane batch too large for one view per call is split by samples
-        vstep = self._views_per_call(bstep, R, S, N, max_rays, dev)
-        C = self.img_channels
-        rgb = depth = None
+        vstep = self._views_per_call(bstep, R, S, N, max_rays, planes.t.device)
+        out = _renderer.Gather(B, V * R)
         for b0 in range(0, B, bstep):
             bs = slice(b0, min(b0 + bstep, B))
-            nb = bs.stop - bs.start
+            p_c = planes if bs.stop - bs.start == B else _renderer.HWCPlanes(planes.t[bs])
             for v0 in range(0, V, vstep):
-                vs = slice(v0, min(v0 + vstep, V))
-                nv = vs.stop - vs.start
-                whole = nb == B and nv == V
-                o = dict(opts, u_coarse=None if uc is None else uc[bs, vs].reshape(nb, nv * R, -1),
-                         u_fine=None if uf is None else uf[bs, vs].reshape(nb * nv * R, -1))
-                p_c = planes if nb == B else _renderer.HWCPlanes(planes.t[bs])
-                ro, rd = (ray_o, ray_d) if whole else (t.reshape(B, V, R, 3)[bs, vs].reshape(nb, nv * R, 3) for t in (ray_o, ray_d))
-                rgb_c, depth_c = self._render_within_field_bound(p_c, ro, rd, o, w)
-                if whole:
-                    rgb, depth = rgb_c.reshape(BV, R, C), depth_c.reshape(BV, R, 1)
-                    break
-                if rgb is None:
-                    rgb = torch.empty([B, V, R, C], dtype=torch.float32, device=dev)
-                    depth = torch.empty([B, V, R, 1], dtype=torch.float32, device=dev)
-                rgb[bs, vs], depth[bs, vs] = rgb_c.reshape(nb, nv, R, C), depth_c.reshape(nb, nv, R, 1)
-        rgb, depth = rgb.reshape(BV, R, C), depth.reshape(BV, R, 1)
+                rs = slice(v0 * R, min(v0 + vstep, V) * R)                  # views v0 .. of these samples: a run of their rays
+                rgb_c, depth_c = self._render_within_field_bound(p_c, ray_o[bs, rs], ray_d[bs, rs], draws.take(bs, rs), opts, w)
+                out.put(bs, rs, rgb=rgb_c, depth=depth_c)
+        rgb, depth = (t.reshape(BV, R, -1) for t in out.result())
         if ray_major:
             return TensorGroup(rgb=rgb, depth=depth)
-        img = torch.empty([BV, C, h, w], dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call('tdgp_rays_to_image', rgb.data_ptr(), img.data_ptr(), BV, h * w, _lib.stream_of(rgb))
-        depth = depth.reshape(BV, 1, h, w)
-        depth_adapted = None
-        if adapt:                                                           # networks_epigraf.py:246-253, elided as in `forward` when not needed
-            depth_adapted = self.depth_adaptor(depth, ws[:, 0].repeat_interleave(V, dim=0))
-            img = torch.cat([img, depth_adapted], dim=1) if render_opts['concat_depth'] else img + 0.0 * depth_adapted.max()
-        if render_opts['return_depth'] or render_opts['return_depth_adapted']:
-            out = TensorGroup(img=img)
-            if render_opts['return_depth']:
-                out.depth = depth
-            if render_opts['return_depth_adapted']:
-                out.depth_adapted = depth_adapted
-            return out
-        return img
+        return self._image_tail(rgb, depth, ws[:, 0].repeat_interleave(V, dim=0) if adapt else None, render_opts, h, w, adapt)
 
     def forward_autograd(self, ws, camera_params, patch_params=None, render_opts={}, u_coarse=None, u_fine=None, n_coarse=None, n_fine=None,
                          **block_kwargs):
@@ -772,27 +726,31 @@ class SynthesisNetwork(torch.nn.Module):
         render_opts = {**self._default_render_options, **render_opts}
         if (render_opts['return_depth_adapted'] or render_opts['concat_depth']) and self.depth_adaptor is None:
             raise RuntimeError('return_depth_adapted / concat_depth need cfg.depth_adaptor')
-        B = ws.shape[0]
         planes = self.tri_plane_decoder.forward_autograd(ws[:, :self.tri_plane_decoder.num_ws], **block_kwargs)
         h = w = self.train_resolution if self.training else self.test_resolution
-        cam = camera_params
-        get = (lambda k: cam[k]) if isinstance(cam, dict) else (lambda k: getattr(cam, k))
+        get = _renderer.cam_get(camera_params)
         cam_trained = any(isinstance(get(k), torch.Tensor) and get(k).requires_grad for k in ('angles', 'fov', 'radius', 'look_at'))
         if cam_trained:                          # cameras from a trained CameraAdaptor (loss.py:76-77): rays as a differentiable graph
-            ray_o, ray_d = _renderer.camera_rays_autograd(cam, (h, w), patch_params=patch_params)
+            ray_o, ray_d = _renderer.camera_rays_autograd(camera_params, (h, w), patch_params=patch_params)
         else:
             with torch.no_grad():
-                c2w = _renderer.compute_cam2world_matrix(cam)
-                ray_o, ray_d = _renderer.sample_rays(c2w, fov=get('fov'), resolution=(h, w), patch_params=patch_params, device=ws.device)
+                ray_o, ray_d = _renderer.camera_rays(camera_params, (h, w), patch_params)
         opts = self.rendering_options(render_opts)
         opts['u_coarse'], opts['u_fine'], opts['n_coarse'], opts['n_fine'] = u_coarse, u_fine, n_coarse, n_fine
         opts['ray_grid_w'] = w
         rgb, depth = _renderer.render_autograd(self.renderer, planes, self.tri_plane_mlp, ray_o, ray_d, opts)
-        img = rgb.reshape(B, h, w, self.img_channels).permute(0, 3, 1, 2).contiguous()
+        return self._image_tail(rgb, depth, ws[:, 0], render_opts, h, w, adapt=self.depth_adaptor is not None, differentiable=True)
+
+    def _image_tail(self, rgb, depth, ws0, render_opts, h, w, adapt, differentiable=False):
+        """What the forwards return from the renderer's ray-major rgb [B,R,C] / depth [B,R,1] (networks_epigraf.py:242-261): the image [B,C,h,w]
+        (tdgp_rays_to_image; `differentiable`: the reshape + permute autograd follows), the depth map [B,1,h,w], with `adapt` the depth adaptor
+        conditioned on `ws0` [B,w_dim] -- whether it runs is each caller's decision -- and the TensorGroup when a depth is asked for."""
+        B = rgb.shape[0]
+        img = rgb.reshape(B, h, w, -1).permute(0, 3, 1, 2).contiguous() if differentiable else _renderer.rays_to_image(rgb, h, w)
         depth = depth.reshape(B, 1, h, w)
         depth_adapted = None
-        if self.depth_adaptor is not None:                                  # networks_epigraf.py:246-253
-            depth_adapted = self.depth_adaptor(depth, ws[:, 0])
+        if adapt:                                                           # networks_epigraf.py:246-253
+            depth_adapted = self.depth_adaptor(depth, ws0)
             img = torch.cat([img, depth_adapted], dim=1) if render_opts['concat_depth'] else img + 0.0 * depth_adapted.max()
         if render_opts['return_depth'] or render_opts['return_depth_adapted']:
             out = TensorGroup(img=img)
@@ -814,14 +772,11 @@ class SynthesisNetwork(torch.nn.Module):
             raise RuntimeError('return_depth_adapted / concat_depth need cfg.depth_adaptor')
         B = ws.shape[0]
         h = w = self.train_resolution if self.training else self.test_resolution
-        cam = camera_params
-        get = (lambda k: cam[k]) if isinstance(cam, dict) else (lambda k: getattr(cam, k))
-        c2w = _renderer.compute_cam2world_matrix(cam)
-        ray_o, ray_d = _renderer.sample_rays(c2w, fov=get('fov'), resolution=(h, w), patch_params=patch_params, device=ws.device)
+        ray_o, ray_d = _renderer.camera_rays(camera_params, (h, w), patch_params)
         opts = self.rendering_options(render_opts)
         opts['ray_grid_w'] = w                      # rays are the row-major pixels of an h x w image (sample_rays)
         R = h * w
-        draws = dict(u_coarse=(u_coarse, [B, R, -1]), u_fine=(u_fine, [B, R, -1]), n_coarse=(n_coarse, [B, -1]), n_fine=(n_fine, [B, -1]))
+        draws = _renderer.Draws(B, R, u_coarse, u_fine, n_coarse, n_fine)
         # cut_quantile thresholds at a quantile over every ray and sample of ONE renderer call (tri_plane_renderer.py:366-368): never
         # batch-chunked here.  The reference itself splits such a call -- by RAYS -- when the eval resolution exceeds max_batch_res
         # (networks_epigraf.py:232-239: run_batchwise over 2**24 // (B * num_ray_steps * 3) rays, "cut_quantile fails on large tensors"),
@@ -834,69 +789,30 @@ class SynthesisNetwork(torch.nn.Module):
             assert ray_step >= 1, f'Wrong batch_size: {ray_step}'        # training_utils.py:180
             if ray_step >= R:
                 ray_step = None                                         # run_batchwise's early exit (:185-186)
-        rgb = depth = None
+        out = _renderer.Gather(B, R)
         for sl, planes in self.tri_plane_decoder.forward_chunks(ws[:, :self.tri_plane_decoder.num_ws], hwc=True, chunk=chunk, chunk_from=self.chunk_from,
                                                                 **block_kwargs):
-            whole = sl.start == 0 and sl.stop == B
-            o = dict(opts)
-            for k, (t, shape) in draws.items():          # the explicit draws of this batch slice, in the layouts the renderer takes
-                if t is None:
-                    o[k] = None
-                elif whole:
-                    o[k] = t
-                else:
-                    tc = t.reshape(shape)[sl]
-                    o[k] = tc.reshape(-1, tc.shape[-1]) if k == 'u_fine' else tc
-            if ray_step is not None:
-                assert whole
-                rgb = torch.empty([B, R, self.img_channels], dtype=torch.float32, device=ws.device)
-                depth = torch.empty([B, R, 1], dtype=torch.float32, device=ws.device)
-                for a in range(0, R, ray_step):
-                    rs = slice(a, min(a + ray_step, R))
-                    oc = dict(o, ray_grid_w=0)           # a run of rays, not an image: the field kernel takes the linear point order
-                    for k in ('u_coarse', 'u_fine'):
-                        if o[k] is not None:
-                            tc = o[k].reshape(B, R, -1)[:, rs].contiguous()
-                            oc[k] = tc.reshape(-1, tc.shape[-1]) if k == 'u_fine' else tc
-                    rgb[:, rs], depth[:, rs], _w, _T = self.renderer(planes, self.tri_plane_mlp, ray_o[:, rs].contiguous(), ray_d[:, rs].contiguous(), oc)
+            if ray_step is None:
+                rgb_c, depth_c = self._render_within_field_bound(planes, ray_o[sl], ray_d[sl], draws.take(sl), opts, w)
+                out.put(sl, slice(0, R), rgb=rgb_c, depth=depth_c)
                 continue
-            rgb_c, depth_c = self._render_within_field_bound(planes, ray_o[sl], ray_d[sl], o, w)
-            if whole:
-                rgb, depth = rgb_c, depth_c
-            else:
-                if rgb is None:
-                    rgb = torch.empty([B, R, rgb_c.shape[-1]], dtype=torch.float32, device=ws.device)
-                    depth = torch.empty([B, R, 1], dtype=torch.float32, device=ws.device)
-                rgb[sl], depth[sl] = rgb_c, depth_c
-        img = torch.empty([B, self.img_channels, h, w], dtype=torch.float32, device=ws.device)
-        with torch.cuda.device(ws.device):
-            _lib.call('tdgp_rays_to_image', rgb.data_ptr(), img.data_ptr(), B, h * w, _lib.stream_of(rgb))
-        depth = depth.reshape(B, 1, h, w)
-        depth_adapted = None
-        if self.depth_adaptor is not None:                                  # networks_epigraf.py:246-253
-            # (self.training: DepthAdaptor.forward with out_strategy='random' draws np.random.choice in training mode -- the host RNG
-            #  stream must advance exactly as the reference's, which always evaluates the adaptor: networks_depth_adaptor.py:86-92)
-            needed = render_opts['concat_depth'] or render_opts['return_depth_adapted'] or self.strict_nan_propagation or self.training
-            if needed:
-                depth_adapted = self.depth_adaptor(depth, ws[:, 0])
-                if render_opts['concat_depth']:
-                    img = torch.cat([img, depth_adapted], dim=1)
-                else:
-                    img = img + 0.0 * depth_adapted.max()
-            # else: ELIDED.  The reference evaluates the adaptor (27 GFLOP per 256^2 image: three 5x5 convolutions at 64 channels) and then adds
-            # `0.0 * depth_adapted.max()` to the image (:253, "to avoid potential DataParallel issues") -- for finite values that is `img`, bit
-            # for bit (x + 0.0 == x for every finite and infinite x; only -0.0 pixels would become +0.0, and a raw MLP output is never -0.0
-            # after `+ b1`... either way equal under ==).  The adaptor draws no random numbers in eval mode, so skipping it leaves every RNG
-            # stream where the reference's is.  What IS lost: a NaN / Inf inside the adaptor (non-finite adaptor weights) no longer poisons the
-            # image; `strict_nan_propagation = True` (or TDGP_STRICT_NAN=1) restores the literal forward.  Training-mode forwards are never elided.
-        if render_opts['return_depth'] or render_opts['return_depth_adapted']:
-            out = TensorGroup(img=img)
-            if render_opts['return_depth']:
-                out.depth = depth
-            if render_opts['return_depth_adapted']:
-                out.depth_adapted = depth_adapted
-            return out
-        return img
+            for a in range(0, R, ray_step):
+                rs = slice(a, min(a + ray_step, R))
+                oc = dict(opts, ray_grid_w=0, **draws.take(sl, rs).opts())      # a run of rays, not an image: the field kernel takes the linear point order
+                rgb_c, depth_c, _w, _T = self.renderer(planes, self.tri_plane_mlp, ray_o[sl, rs].contiguous(), ray_d[sl, rs].contiguous(), oc)
+                out.put(sl, rs, rgb=rgb_c, depth=depth_c)
+        # The depth adaptor (networks_epigraf.py:246-253) runs when its output is asked for, and in training mode (DepthAdaptor.forward with
+        # out_strategy='random' draws np.random.choice there -- the host RNG stream must advance exactly as the reference's, which always
+        # evaluates the adaptor: networks_depth_adaptor.py:86-92).
+        # Otherwise it is ELIDED.  The reference evaluates the adaptor (27 GFLOP per 256^2 image: three 5x5 convolutions at 64 channels) and then adds
+        # `0.0 * depth_adapted.max()` to the image (:253, "to avoid potential DataParallel issues") -- for finite values that is `img`, bit
+        # for bit (x + 0.0 == x for every finite and infinite x; only -0.0 pixels would become +0.0, and a raw MLP output is never -0.0
+        # after `+ b1`... either way equal under ==).  The adaptor draws no random numbers in eval mode, so skipping it leaves every RNG
+        # stream where the reference's is.  What IS lost: a NaN / Inf inside the adaptor (non-finite adaptor weights) no longer poisons the
+        # image; `strict_nan_propagation = True` (or TDGP_STRICT_NAN=1) restores the literal forward.  Training-mode forwards are never elided.
+        adapt = self.depth_adaptor is not None and bool(render_opts['concat_depth'] or render_opts['return_depth_adapted'] or self.strict_nan_propagation
+                                                        or self.training)
+        return self._image_tail(*out.result(), ws[:, 0], render_opts, h, w, adapt)
 
 
 class Generator(torch.nn.Module):

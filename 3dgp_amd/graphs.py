@@ -15,6 +15,8 @@ torch's graph-safe Philox state: every replay draws fresh numbers, as the eager 
 """
 import torch
 
+from .renderer import cam_get
+
 
 class GraphedGenerator:
     def __init__(self, G, batch, noise_mode='const', explicit_draws=False, truncation_psi=1, truncation_cutoff=None, render_opts=None, warmup=2):
@@ -56,7 +58,7 @@ class GraphedGenerator:
 
     def load(self, z, c, camera_params, u_coarse=None, u_fine=None):
         """Copy one batch of inputs into the graph's static buffers (device-to-device when they are resident already)."""
-        get = (lambda k: camera_params[k]) if isinstance(camera_params, dict) else (lambda k: getattr(camera_params, k))
+        get = cam_get(camera_params)
         self.z.copy_(z)
         self.c.copy_(c)
         for k in self.cam:

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import renderer as _renderer
 from .generator import TensorGroup
 from .metrics import camera_base, sample_camera_params
 
@@ -70,20 +71,17 @@ def _plane_batches(G, ws, camera_params, plane_batch, u_coarse=None, u_fine=None
     """The shared-planes route: `tri_planes` on `plane_batch` samples at a time (block kwargs and noise_mode='const' go there), `render_views` on
     their cameras.  Yields what render_views returns, per plane batch, sample-major.  `batch_size` (the per-frame route's chunk) has no role here."""
     num_samples = len(ws)
-    if num_samples < 1 or len(camera_params) % num_samples != 0 or len(camera_params) < num_samples:
-        raise ValueError(f'{len(camera_params)} cameras are not a multiple of the {num_samples} samples')
+    V = _renderer.views_per_sample(len(camera_params), num_samples, f'{num_samples} samples')
     if int(plane_batch) < 1:
         raise ValueError(f'plane_batch must be positive, got {plane_batch!r}')
-    V = len(camera_params) // num_samples
     camera_params = camera_params.to(dtype=torch.float32, device=ws.device)
     syn = G.synthesis
-    R = syn.test_resolution ** 2
+    draws = _renderer.Draws(num_samples, V * syn.test_resolution ** 2, u_coarse, u_fine)
     for n0 in range(0, num_samples, int(plane_batch)):
         n1 = min(n0 + int(plane_batch), num_samples)
         planes = syn.tri_planes(ws[n0:n1], noise_mode='const', **block_kwargs)
-        yield syn.render_views(planes, camera_params[n0 * V:n1 * V], ws=ws[n0:n1], render_opts=render_opts,
-                               u_coarse=None if u_coarse is None else u_coarse.reshape(num_samples * V, R, -1)[n0 * V:n1 * V],
-                               u_fine=None if u_fine is None else u_fine.reshape(num_samples * V * R, -1)[n0 * V * R:n1 * V * R],
+        d = draws.take(slice(n0, n1)).opts()
+        yield syn.render_views(planes, camera_params[n0 * V:n1 * V], ws=ws[n0:n1], render_opts=render_opts, u_coarse=d['u_coarse'], u_fine=d['u_fine'],
                                max_rays_per_call=max_rays_per_call, ray_major=ray_major)
 
 

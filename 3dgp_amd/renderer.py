@@ -18,6 +18,7 @@ renderer.  Here they may be supplied explicitly as `rendering_options['u_coarse'
 is defined); when absent they are drawn on the device in the same order and shapes.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -160,9 +161,21 @@ def _cut_threshold(sigma, opts, marcher, flags):
 
 # ------------------------------------------------------------------------------------------------ camera + rays
 
+def cam_get(cam):
+    """The field getter of camera parameters, which arrive as a dict or as an attribute bag (TensorGroup)."""
+    return (lambda k: cam[k]) if isinstance(cam, dict) else (lambda k: getattr(cam, k))
+
+
+def views_per_sample(num_cameras, num_samples, of_what):
+    """V of `num_cameras` = num_samples * V sample-major cameras (camera n * V + v is view v of sample n); `of_what` words the refusal."""
+    if num_samples < 1 or num_cameras < num_samples or num_cameras % num_samples != 0:
+        raise ValueError(f'{num_cameras} cameras are not a multiple of the {of_what}')
+    return num_cameras // num_samples
+
+
 def compute_cam2world_matrix(camera_params):
     """camera_params: mapping/attribute bag with angles [B,3], radius [B], look_at [B,3] -> c2w [B,4,4]."""
-    get = (lambda k: camera_params[k]) if isinstance(camera_params, dict) else (lambda k: getattr(camera_params, k))
+    get = cam_get(camera_params)
     angles, radius, look_at = (_lib.f32c(get(k)) for k in ('angles', 'radius', 'look_at'))
     _lib.require_cuda(angles, 'camera_params.angles')
     B = angles.shape[0]
@@ -180,7 +193,7 @@ def camera_rays_autograd(camera_params, resolution, patch_params=None):
     cos(pitch), sin(pitch) cos(yaw)), the look-at point likewise from `look_at` = (yaw, pitch, radius); the camera looks down -z with the
     world's +y as its up hint; pixel (row, col) of an h x w image shoots through x = -1 + 2 col / (w - 1), y = 1 - 2 row / (h - 1),
     z = -1 / tan(fov / 2), optionally restricted to a patch (scale, offset in [0, 1] units)."""
-    get = (lambda k: camera_params[k]) if isinstance(camera_params, dict) else (lambda k: getattr(camera_params, k))
+    get = cam_get(camera_params)
     angles, radius, look_at, fov = get('angles').float(), get('radius').float(), get('look_at').float(), get('fov')
     B, dev = angles.shape[0], angles.device
     w, h = resolution
@@ -239,6 +252,86 @@ def sample_rays(c2w, fov, resolution, patch_params=None, device=None):
         _lib.call('tdgp_sample_rays', c2w.data_ptr(), fov_t.data_ptr(), stride, _lib.ptr(ps), _lib.ptr(po), ray_o.data_ptr(), ray_d.data_ptr(),
                   B, h, w, _lib.stream_of(c2w))
     return ray_o, ray_d
+
+
+def camera_rays(cam, resolution, patch_params=None):
+    """`sample_rays` of the cameras' `compute_cam2world_matrix` (networks_epigraf.py:223-224) -> (ray_o, ray_d) [B, h*w, 3]."""
+    return sample_rays(compute_cam2world_matrix(cam), fov=cam_get(cam)('fov'), resolution=resolution, patch_params=patch_params)
+
+
+def rays_to_image(x, h, w):
+    """Ray-major [B, h*w, 3] -> image [B,3,h,w] (tdgp_rays_to_image: the reshape + permute at networks_epigraf.py:242)."""
+    x = _lib.f32c(x)
+    B = x.shape[0]
+    img = torch.empty([B, 3, h, w], dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call('tdgp_rays_to_image', x.data_ptr(), img.data_ptr(), B, h * w, _lib.stream_of(x))
+    return img
+
+
+# ------------------------------------------------------------------------------------------------ explicit draws and results of a split call
+
+class Draws:
+    """The four optional explicit draws of one renderer call over [B, R] rays (`u_coarse / u_fine`: uniform, stratification and inverse CDF;
+    `n_coarse / n_fine`: normal, density noise), each held as a [B,R,k] view of what the caller passed -- u_coarse [B,R,S] or [B,R,S,1], u_fine
+    [B*R,N] or [B,R,N], n_* [B,R*k,1] or [B,R*k] -- so that an element keeps its ray however the call is split.  None stays None; nothing is copied."""
+    KEYS = ('u_coarse', 'u_fine', 'n_coarse', 'n_fine')
+
+    def __init__(self, B, R, u_coarse=None, u_fine=None, n_coarse=None, n_fine=None):
+        self.B, self.R = B, R
+        self.t = {k: None if t is None else t.reshape(B, R, -1) for k, t in zip(self.KEYS, (u_coarse, u_fine, n_coarse, n_fine))}
+
+    def take(self, bs, rs=slice(None)):
+        """The draws of samples `bs` and rays `rs` (slices): views, the same storage when the range is whole."""
+        return Draws(len(range(self.B)[bs]), len(range(self.R)[rs]), *(None if t is None else t[bs, rs] for t in self.t.values()))
+
+    def opts(self):
+        """The `rendering_options` entries in the layouts `ImportanceRenderer.forward` takes: u_coarse [b,r,S], u_fine [b*r,N], n_* [b,r*k,1], contiguous."""
+        out = {}
+        for k, t in self.t.items():
+            if t is not None:
+                t = t.contiguous()
+                t = t if k == 'u_coarse' else (t.reshape(-1, t.shape[-1]) if k == 'u_fine' else t.reshape(self.B, -1, 1))
+            out[k] = t
+        return out
+
+    def filled(self, S, N, density_noise, device):
+        """These draws with the absent ones made, in the order and shapes of the reference's renderer (tri_plane_renderer.py:225, 279, 183-185):
+        u_coarse, u_fine if N > 0, then -- with density noise only -- n_coarse and n_fine."""
+        B, R, t = self.B, self.R, dict(self.t)
+
+        def fill(k, draw, shape):
+            if t[k] is None:
+                t[k] = draw(shape, device=device)
+
+        fill('u_coarse', torch.rand, [B, R, S, 1])
+        if N > 0:
+            fill('u_fine', torch.rand, [B * R, N])
+        if density_noise > 0.0:
+            fill('n_coarse', torch.randn, [B, R * S, 1])
+            if N > 0:
+                fill('n_fine', torch.randn, [B, R * N, 1])
+        return Draws(B, R, **t)
+
+
+class Gather:
+    """The named results of a [B, R]-ray call made in pieces: `put` a piece [b,r,...] per name at its (sample, ray) slices, `result()` -> the
+    [B,R,...] tensors in the order named.  One piece that covers everything comes back itself; otherwise the first piece allocates."""
+
+    def __init__(self, B, R):
+        self.B, self.R, self.out = B, R, None
+
+    def put(self, bs, rs, **pieces):
+        if self.out is None:
+            if all(tuple(t.shape[:2]) == (self.B, self.R) for t in pieces.values()):
+                self.out = pieces
+                return
+            self.out = {k: torch.empty([self.B, self.R, *t.shape[2:]], dtype=t.dtype, device=t.device) for k, t in pieces.items()}
+        for k, t in pieces.items():
+            self.out[k][bs, rs] = t
+
+    def result(self):
+        return tuple(self.out.values())
 
 
 # ------------------------------------------------------------------------------------------------ tri-plane field
@@ -734,10 +827,15 @@ class ImportanceRenderer(torch.nn.Module):
         flags = _marcher_flags(opts, marcher)
         mid, dbias = MARCHER_IDS[marcher], float(opts.get('density_bias', 0.0))
         dev = ray_o.device
-        u_coarse = opts.get('u_coarse')
-        u_coarse = torch.rand([B, R, S, 1], device=dev) if u_coarse is None else _lib.f32c(u_coarse.to(dev))
-        if u_coarse.numel() != B * R * S:
-            raise RuntimeError(f'u_coarse must have {B}x{R}x{S} elements')
+
+        def uniform(key, *shape):            # the explicit draw, or one made here: per call, where the reference's renderer draws it
+            u = opts.get(key)
+            u = torch.rand(shape, device=dev) if u is None else _lib.f32c(u.to(dev))
+            if u.numel() != math.prod(shape):
+                raise RuntimeError(f'{key} must have {"x".join(str(n) for n in shape[:3])} elements')
+            return u
+
+        u_coarse = uniform('u_coarse', B, R, S, 1)
         # rays of an h x w image in row-major order (sample_rays): let the field kernel walk 4x4-pixel tiles
         ray_w = opts.get('ray_grid_w')
         if ray_w is None:
@@ -747,10 +845,7 @@ class ImportanceRenderer(torch.nn.Module):
         cut_on = float(opts.get('cut_quantile', 0.0)) > 0.0
         if (self.fused_entry and fused_mlp and N > 0 and not return_intermediates and not cut_on and dnoise == 0.0 and B * R > 0):
             # the plain forward: ONE C-ABI call (tdgp_render_fused) -- the same five kernels the staged path below issues, same bits
-            u_fine = opts.get('u_fine')
-            u_fine = torch.rand([B * R, N], device=dev) if u_fine is None else _lib.f32c(u_fine.to(dev))
-            if u_fine.numel() != B * R * N:
-                raise RuntimeError(f'u_fine must have {B * R}x{N} elements')
+            u_fine = uniform('u_fine', B * R, N)
             p_ = planes.t
             _, _, H, W, F = p_.shape
             w0, b0, w1, b1, _ = mlp
@@ -771,10 +866,7 @@ class ImportanceRenderer(torch.nn.Module):
             _lib.call('tdgp_sample_stratified', u_coarse.data_ptr(), sdist.data_ptr(), tdist.data_ptr(), B * R, S, mid, t_near, t_far, stream)
             rgbs_c = field(tdist, n_coarse)
             if N > 0:
-                u_fine = opts.get('u_fine')
-                u_fine = torch.rand([B * R, N], device=dev) if u_fine is None else _lib.f32c(u_fine.to(dev))
-                if u_fine.numel() != B * R * N:
-                    raise RuntimeError(f'u_fine must have {B * R}x{N} elements')
+                u_fine = uniform('u_fine', B * R, N)
                 tfine = torch.empty([B, R, N], dtype=torch.float32, device=dev)
                 sfine = torch.empty([B, R, N], dtype=torch.float32, device=dev) if return_intermediates else None
                 inds = torch.empty([B * R, N], dtype=torch.int32, device=dev) if return_intermediates else None
@@ -826,16 +918,7 @@ class _RenderFunction(torch.autograd.Function):
         opts = dict(opts)
         B, R, _ = ray_o.shape
         S, N = int(opts['num_proposal_steps']), int(opts['num_fine_steps'])
-        dev = ray_o.device
-        if opts.get('u_coarse') is None:
-            opts['u_coarse'] = torch.rand([B, R, S, 1], device=dev)
-        if N > 0 and opts.get('u_fine') is None:
-            opts['u_fine'] = torch.rand([B * R, N], device=dev)
-        if float(opts.get('density_noise', 0.0)) > 0.0:
-            if opts.get('n_coarse') is None:
-                opts['n_coarse'] = torch.randn([B, R * S, 1], device=dev)
-            if N > 0 and opts.get('n_fine') is None:
-                opts['n_fine'] = torch.randn([B, R * N, 1], device=dev)
+        opts.update(Draws(B, R, *(opts.get(k) for k in Draws.KEYS)).filled(S, N, float(opts.get('density_noise', 0.0)), ray_o.device).opts())
         rgb, depth, _w, _t = renderer.forward(planes.detach(), decoder, ray_o.detach(), ray_d.detach(), opts)
         ctx.save_for_backward(planes)
         ctx.state = (renderer, decoder, ray_o.detach(), ray_d.detach(), opts)

@@ -163,12 +163,8 @@ def render_shape_views(G, planes, camera_params, level=25.0, mode='shaded', num_
         raise TypeError('render_shape_views takes the HWCPlanes that tri_planes returns')
     if max_rays_per_call is not None and int(max_rays_per_call) < 1:
         raise ValueError(f'max_rays_per_call must be positive, got {max_rays_per_call!r}')
-    cam = camera_params
-    get = (lambda k: cam[k]) if isinstance(cam, dict) else (lambda k: getattr(cam, k))
-    B, BV = int(planes.t.shape[0]), int(get('angles').shape[0])
-    if B < 1 or BV < B or BV % B != 0:
-        raise ValueError(f'{BV} cameras are not a multiple of the plane batch {B} (sample-major: camera n * V + v is view v of sample n)')
-    V = BV // B
+    B, BV = int(planes.t.shape[0]), int(_renderer.cam_get(camera_params)('angles').shape[0])
+    V = _renderer.views_per_sample(BV, B, f'plane batch {B} (sample-major: camera n * V + v is view v of sample n)')
     _lib.require_cuda(planes.t, 'planes')
     dev = planes.t.device
     h = w = syn.test_resolution
@@ -176,9 +172,7 @@ def render_shape_views(G, planes, camera_params, level=25.0, mode='shaded', num_
     T = V * R                                                          # rays per sample: V frames of h rows of w rays
     step = 2.0 * float(cfg.cube_scale) / int(cfg.tri_plane_res) if step is None else float(step)
     ray_field, point_field = field_functions(syn)
-    c2w = _renderer.compute_cam2world_matrix(cam)
-    ray_o, ray_d = _renderer.sample_rays(c2w, fov=get('fov'), resolution=(h, w), device=dev)
-    ray_o, ray_d = ray_o.reshape(B, T, 3), ray_d.reshape(B, T, 3)
+    ray_o, ray_d = (x.reshape(B, T, 3) for x in _renderer.camera_rays(camera_params, (h, w)))
     # rays per call: the caller's bound, and the field kernel's points per call (the 7-point pass is the largest per ray when S < 7)
     max_rays = min(16 * R if max_rays_per_call is None else int(max_rays_per_call), FIELD_POINTS_MAX // max(S, N, STENCIL))
     if B * T <= max_rays:
@@ -189,7 +183,7 @@ def render_shape_views(G, planes, camera_params, level=25.0, mode='shaded', num_
         bstep, rstep = 1, min(T, max_rays)
     if w < rstep < T:
         rstep -= rstep % w                                             # whole image rows, so the ray-mode passes keep their tile walk
-    out = t_coarse = None
+    out, t_coarse = _renderer.Gather(B, T), None
     for b0 in range(0, B, bstep):
         bs = slice(b0, min(b0 + bstep, B))
         nb = bs.stop - bs.start
@@ -209,30 +203,21 @@ def render_shape_views(G, planes, camera_params, level=25.0, mode='shaded', num_
             t_hit, status, points = iso_locate(sig_c, t_coarse, idx, rgbs_f.reshape(rays, N, 4)[..., 3], t_fine, o, d, level, step, float(cfg.ray_end))
             stencil = point_field(p_c, points.reshape(nb, n * STENCIL, 3))
             rgb, normal = iso_shade(stencil, status, d, mode=mode, light=light, ambient=ambient, albedo=albedo, background=background)
-            if nb == B and n == T:                                     # one call held everything
-                out = TensorGroup(rgb=rgb, depth=t_hit, normal=normal, status=status)
-                break
-            if out is None:
-                out = TensorGroup(rgb=torch.empty([B, T, 3], dtype=torch.float32, device=dev), depth=torch.empty([B, T, 1], dtype=torch.float32, device=dev),
-                                  normal=torch.empty([B, T, 3], dtype=torch.float32, device=dev), status=torch.empty([B, T], dtype=torch.int32, device=dev))
-            out.rgb[bs, rs], out.depth[bs, rs] = rgb.reshape(nb, n, 3), t_hit.reshape(nb, n, 1)
-            out.normal[bs, rs], out.status[bs, rs] = normal.reshape(nb, n, 3), status.reshape(nb, n)
-    return TensorGroup(rgb=out.rgb.reshape(BV, R, 3), depth=out.depth.reshape(BV, R, 1), normal=out.normal.reshape(BV, R, 3),
-                       status=out.status.reshape(BV, R))
+            out.put(bs, rs, rgb=rgb.reshape(nb, n, 3), depth=t_hit.reshape(nb, n, 1), normal=normal.reshape(nb, n, 3), status=status.reshape(nb, n))
+    rgb, depth, normal, status = out.result()
+    return TensorGroup(rgb=rgb.reshape(BV, R, 3), depth=depth.reshape(BV, R, 1), normal=normal.reshape(BV, R, 3), status=status.reshape(BV, R))
 
 
 def _shape_batches(G, ws, camera_params, plane_batch, **kw):
     """`tri_planes` on `plane_batch` samples at a time, `render_shape_views` on their cameras (the structure of inference._plane_batches)."""
     num_samples = len(ws)
-    if num_samples < 1 or len(camera_params) % num_samples != 0 or len(camera_params) < num_samples:
-        raise ValueError(f'{len(camera_params)} cameras are not a multiple of the {num_samples} samples')
+    V = _renderer.views_per_sample(len(camera_params), num_samples, f'{num_samples} samples')
     if int(plane_batch) < 1:
         raise ValueError(f'plane_batch must be positive, got {plane_batch!r}')
     S = int(G.cfg.num_ray_steps) if kw.get('num_steps') is None else kw['num_steps']
     _check_options(kw.get('mode', 'shaded'), S, kw.get('num_refine', 16))
     if G.synthesis.training:
         raise RuntimeError('render_shapes is the inference route: call .eval() first (training mode renders patches with density noise)')
-    V = len(camera_params) // num_samples
     camera_params = camera_params.to(dtype=torch.float32, device=ws.device)
     for n0 in range(0, num_samples, int(plane_batch)):
         n1 = min(n0 + int(plane_batch), num_samples)
@@ -252,17 +237,11 @@ def render_shapes(G, ws, camera_params, plane_batch=4, return_all=False, **kw):
     frames = _all_frames(G, ws, camera_params, plane_batch, **kw)
     h = w = G.synthesis.test_resolution
     BV = frames.rgb.shape[0]
-
-    def image(x):
-        img = torch.empty([BV, 3, h, w], dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.call('tdgp_rays_to_image', x.data_ptr(), img.data_ptr(), BV, h * w, _lib.stream_of(x))
-        return img
-
-    img = image(frames.rgb.contiguous())
+    img = _renderer.rays_to_image(frames.rgb, h, w)
     if not return_all:
         return img
-    return TensorGroup(img=img, depth=frames.depth.reshape(BV, 1, h, w), normal=image(frames.normal.contiguous()), status=frames.status.reshape(BV, h, w))
+    return TensorGroup(img=img, depth=frames.depth.reshape(BV, 1, h, w), normal=_renderer.rays_to_image(frames.normal, h, w),
+                       status=frames.status.reshape(BV, h, w))
 
 
 def _shown_frames(G, ws, camera_params, show, plane_batch, **kw):
