@@ -67,6 +67,9 @@ _PROTOTYPES = {
     'tdgp_render_fused': (c_int, [P] * 13 + [c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_int, c_float, P, c_int64, P]),
     'tdgp_rays_to_image': (c_int, [P, P, c_int, c_int, P]),
     'tdgp_frames_to_grid_u8': (c_int, [P, c_int64, c_int, c_int, c_int, P, c_int, c_int, c_int64, c_int64, c_int, c_int, c_int, c_float, c_float, P]),
+    'tdgp_ppl_frames': (c_int, [P, c_int64, c_int, c_int, c_int, c_int, c_int, P, P]),
+    'tdgp_pair_sqdist_workspace_bytes': (c_int64, [c_int64, c_int64]),
+    'tdgp_pair_sqdist': (c_int, [P, c_int64, c_int64, c_double, P, P, c_int64, P]),
     'tdgp_voxel_coords': (c_int, [P, c_int64, c_int64, c_int, c_float, c_float, c_float, c_float, P]),
     'tdgp_mcubes_workspace_bytes': (c_int64, [c_int, c_int, c_int]),
     'tdgp_mcubes_count': (c_int, [P, c_int, c_int, c_int, c_float, P, c_int64, P]),

@@ -6,6 +6,9 @@
 // One streaming kernel: 4 bytes read per channel value, 1 written; no workspace, no atomics, one writer per output dword, so the same bytes
 // come out on every run.  The fp32 chain is the CPU one, each operation rounded once (the library is built with -ffp-contract=off and `/` is
 // the correctly rounded division).
+//
+// Also here: ppl_frames_kernel (tdgp_ppl_frames), the fp32 image tail of the perceptual path length from the same ray-major frames
+//   src/metrics/perceptual_path_length.py:71-85   centre crop, box mean to 256^2, (x + 1) * 127.5, grey replicated
 #include "common.h"
 
 namespace {
@@ -100,7 +103,73 @@ __global__ __launch_bounds__(256) void frames_to_grid_u8_kernel(const float* __r
     }
 }
 
+// The image tail of the perceptual path length (src/metrics/perceptual_path_length.py:71-85 behind the reshape of networks_epigraf.py:242):
+// centre crop, factor x factor box mean, (x + 1) * 127.5, grey replicated -- one thread per output pixel, all three channels.  The box is
+// summed in fp64 in row-major order and divided by factor^2 there (one rounding to fp32); the two fp32 operations that follow are rounded
+// separately (the library is built with -ffp-contract=off): at factor 1 the bits of torch's CPU chain.
+struct TailGeom {
+    int h, w, C;              // source frame
+    int y0, x0;               // first row / column of the window
+    int oh, ow, factor;
+};
+
+__global__ __launch_bounds__(256) void ppl_frames_kernel(const float* __restrict__ frames, float* __restrict__ out, TailGeom g, int64_t pixels) {
+    const int64_t plane = (int64_t)g.oh * g.ow;
+    const double area = (double)g.factor * (double)g.factor;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < pixels; p += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t f = p / plane;
+        const int64_t r = p - f * plane;
+        const int oy = (int)(r / g.ow), ox = (int)(r - (int64_t)oy * g.ow);
+        const float* __restrict__ src = frames + (f * g.h * g.w + (int64_t)(g.y0 + oy * g.factor) * g.w + (g.x0 + ox * g.factor)) * g.C;
+        float y[3] = {0.f, 0.f, 0.f};
+        for (int c = 0; c < g.C; c++) {
+            float x;
+            if (g.factor == 1) {
+                x = src[c];
+            } else {
+                double s = 0.0;
+                for (int dy = 0; dy < g.factor; dy++)
+                    for (int dx = 0; dx < g.factor; dx++) s += (double)src[((int64_t)dy * g.w + dx) * g.C + c];
+                x = (float)(s / area);
+            }
+            y[c] = (x + 1.0f) * 127.5f;
+        }
+        float* __restrict__ dst = out + f * 3 * plane + r;
+        dst[0] = y[0];
+        dst[plane] = g.C == 1 ? y[0] : y[1];
+        dst[2 * plane] = g.C == 1 ? y[0] : y[2];
+    }
+}
+
 }  // namespace
+
+TDGP_API int tdgp_ppl_frames(const float* frames, int64_t num_frames, int h, int w, int C, int crop, int factor, float* out, tdgp_stream_t stream) {
+    TDGP_CHECK(num_frames >= 0 && h >= 1 && w >= 1, TDGP_EINVAL, "ppl_frames: bad shape (%lld frames of %d x %d)", (long long)num_frames, h, w);
+    TDGP_CHECK(C == 1 || C == 3, TDGP_EINVAL, "ppl_frames: C must be 1 or 3");
+    TDGP_CHECK(factor >= 1, TDGP_EINVAL, "ppl_frames: factor = %d, must be >= 1", factor);
+    TailGeom g;
+    g.h = h; g.w = w; g.C = C; g.factor = factor;
+    g.y0 = g.x0 = 0;
+    int wh = h, ww = w;
+    if (crop) {
+        TDGP_CHECK(h == w, TDGP_EINVAL, "ppl_frames: the centre crop needs a square frame, got %d x %d", h, w);
+        const int c = h / 8;
+        TDGP_CHECK(c >= 1, TDGP_EINVAL, "ppl_frames: the centre crop of a %d x %d frame is empty", h, w);
+        g.y0 = 3 * c; g.x0 = 2 * c;
+        wh = ww = 4 * c;
+    }
+    TDGP_CHECK(wh % factor == 0 && ww % factor == 0, TDGP_EINVAL, "ppl_frames: the %d x %d window does not divide by factor %d", wh, ww, factor);
+    g.oh = wh / factor; g.ow = ww / factor;
+    TDGP_CHECK((int64_t)h * w < ((int64_t)1 << 31) && (double)num_frames * h * w * 3 < 9.0e18, TDGP_EINVAL, "ppl_frames: tensor too large");
+    if (num_frames == 0) return TDGP_OK;
+    TDGP_CHECK(frames && out, TDGP_EINVAL, "ppl_frames: null pointer");
+    TDGP_CHECK(((uintptr_t)frames & 3) == 0 && ((uintptr_t)out & 3) == 0, TDGP_EINVAL, "ppl_frames: frames and out must be 4-byte aligned");
+    const int64_t pixels = num_frames * g.oh * g.ow;
+    const dim3 grid((unsigned)std::min<int64_t>(262144, cdiv64(pixels, 256)));
+    TDGP_LAUNCH("ppl_frames_kernel", ppl_frames_kernel, grid, dim3(256), 0, (hipStream_t)stream, frames, out, g, pixels);
+    TDGP_LAUNCH_CHECK();
+    return TDGP_OK;
+}
 
 TDGP_API int tdgp_frames_to_grid_u8(const float* frames, int64_t num_frames, int h, int w, int C, uint8_t* out, int images, int tiles,
                                     int64_t stride_image, int64_t stride_tile, int nrow, int padding, int normalise, float mid, float range,

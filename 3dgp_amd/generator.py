@@ -763,10 +763,12 @@ class SynthesisNetwork(torch.nn.Module):
 
     @torch.no_grad()
     def forward(self, ws, camera_params, patch_params=None, render_opts={}, u_coarse=None, u_fine=None, n_coarse=None, n_fine=None,
-                update_emas=False, **block_kwargs):
+                update_emas=False, ray_major=False, **block_kwargs):
         """ws [B,num_ws,w_dim]; camera_params {angles [B,3], fov [B], radius [B], look_at [B,3]} -> img [B,3,h,w]
         (or TensorGroup(img, depth) with render_opts['return_depth']).  u_* / n_*: explicit uniform / normal draws of the renderer
-        (stratification, inverse-CDF, density noise) for the parity tests; drawn on the device when absent."""
+        (stratification, inverse-CDF, density noise) for the parity tests; drawn on the device when absent.
+        ray_major=True: TensorGroup(rgb [B,R,C], depth [B,R,1]) as the renderer leaves them, as `render_views` returns them -- what
+        `tdgp_ppl_frames` reads; no CHW image is made and no adaptor is applied."""
         render_opts = {**self._default_render_options, **render_opts}
         if (render_opts['return_depth_adapted'] or render_opts['concat_depth']) and self.depth_adaptor is None:
             raise RuntimeError('return_depth_adapted / concat_depth need cfg.depth_adaptor')
@@ -810,6 +812,9 @@ class SynthesisNetwork(torch.nn.Module):
         # after `+ b1`... either way equal under ==).  The adaptor draws no random numbers in eval mode, so skipping it leaves every RNG
         # stream where the reference's is.  What IS lost: a NaN / Inf inside the adaptor (non-finite adaptor weights) no longer poisons the
         # image; `strict_nan_propagation = True` (or TDGP_STRICT_NAN=1) restores the literal forward.  Training-mode forwards are never elided.
+        if ray_major:
+            rgb, depth = out.result()
+            return TensorGroup(rgb=rgb, depth=depth)
         adapt = self.depth_adaptor is not None and bool(render_opts['concat_depth'] or render_opts['return_depth_adapted'] or self.strict_nan_propagation
                                                         or self.training)
         return self._image_tail(*out.result(), ws[:, 0], render_opts, h, w, adapt)

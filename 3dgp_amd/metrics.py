@@ -808,3 +808,249 @@ def compute_flatness_score(G, num_gen, min_depth, max_depth, num_bins=64, cut_qu
 def nfs256(G, **kw):
     """The registry entry 'nfs256' (metric_main.py:118-120): 256 samples, depth range = the generator's ray range."""
     return dict(nfs256=compute_flatness_score(G, num_gen=256, min_depth=G.cfg.ray_start, max_depth=G.cfg.ray_end, **kw))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# perceptual path length (src/metrics/perceptual_path_length.py; metric 'ppl2_wend', metric_main.py:105-108)
+# ----------------------------------------------------------------------------------------------------------------------
+def slerp(a, b, t):
+    """perceptual_path_length.py:22-31: spherical interpolation of a batch of vectors [B, D] at t [B, 1]; the result has unit length, and
+    slerp(a, b, 0) is a / |a|."""
+    a = a / a.norm(dim=-1, keepdim=True)
+    b = b / b.norm(dim=-1, keepdim=True)
+    d = (a * b).sum(dim=-1, keepdim=True)
+    p = t * torch.acos(d)
+    c = b - d * a
+    c = c / c.norm(dim=-1, keepdim=True)
+    d = a * torch.cos(p) + c * torch.sin(p)
+    return d / d.norm(dim=-1, keepdim=True)
+
+
+def ppl_ranks(n):
+    """(k_lo, k_hi): np.percentile(x, 1, interpolation='lower') is sorted(x)[k_lo] and np.percentile(x, 99, interpolation='higher') is
+    sorted(x)[k_hi] for n values -- numpy's float64 virtual index (n - 1) * (q / 100), floored / ceiled."""
+    n = int(n)
+    assert n >= 1
+    k_lo = int(np.floor((n - 1) * (np.float64(1) / 100)))
+    k_hi = int(np.ceil((n - 1) * (np.float64(99) / 100)))
+    return k_lo, min(k_hi, n - 1)
+
+
+def _order_statistic(x, k):
+    """sorted(x)[k] of a contiguous fp32 GPU vector as a 0-d tensor on the device, exact bits (tdgp_quantile_select with k_lo == k_hi); NaN if
+    any element is NaN.  Nothing is read back."""
+    from . import _lib, renderer as _renderer
+    n = x.numel()
+    with torch.cuda.device(x.device):
+        need = int(_lib.load().tdgp_quantile_select_workspace_bytes(n))
+        if need < 0:
+            raise RuntimeError(f'aggregate_ppl: {n} distances outside [1, 2^31 - 1]')
+        stream = _lib.stream_of(x)
+        ws = _renderer._qs_workspace(x.device, stream, need)
+        out = torch.empty(3, dtype=torch.float32, device=x.device)
+        _lib.call('tdgp_quantile_select', x.data_ptr(), n, int(k), int(k), 0.0, out.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+    return out[0]
+
+
+def aggregate_ppl(dist):
+    """perceptual_path_length.py:120-122: the mean of the distances between their 1st percentile (interpolation 'lower') and their 99th
+    ('higher'), both ends and every tie with them included.  lo = sorted[k_lo], hi = sorted[k_hi] with `ppl_ranks`; on a GPU tensor the two
+    order statistics come from tdgp_quantile_select (exact bits, no sort), the mean is an fp64 masked sum over its count in torch ops on
+    the device, and one scalar is read back.  A CPU tensor or array takes the same definition in numpy.
+    The reference averages the kept fp32 values in fp32 (`np.mean` of a float32 array); here the mean is taken in fp64.  A NaN distance
+    makes the result NaN (np.percentile's answer too)."""
+    if isinstance(dist, torch.Tensor) and dist.is_cuda:
+        from . import _lib
+        d = _lib.f32c(dist.reshape(-1))
+        k_lo, k_hi = ppl_ranks(d.numel())
+        lo, hi = _order_statistic(d, k_lo), _order_statistic(d, k_hi)
+        keep = (d >= lo) & (d <= hi)
+        total = torch.where(keep, d.double(), torch.zeros([], dtype=torch.float64, device=d.device)).sum()
+        return float((total / keep.sum()).item())
+    d = np.asarray(dist.detach().numpy() if isinstance(dist, torch.Tensor) else dist, dtype=np.float32).reshape(-1)
+    if np.isnan(d).any():
+        return float('nan')
+    k_lo, k_hi = ppl_ranks(d.size)
+    ordered = np.sort(d)
+    lo, hi = ordered[k_lo], ordered[k_hi]
+    return float(np.extract(np.logical_and(d >= lo, d <= hi), d).astype(np.float64).mean())
+
+
+def pair_sqdist(feats, inv_scale, out=None):
+    """feats [2n, W] (row i paired with row n + i, what `chunk(2)` splits) -> [n] fp32: sum((a - b)^2) * inv_scale with the difference in fp32
+    and its square and the sum in fp64, rounded once (tdgp_pair_sqdist, contract in include/tdgp.h: no full-width temporary, a summation tree
+    fixed by W, the same bytes on every run).  `out`: a contiguous fp32 [n] view to write into (any offset into a larger buffer).  A CPU
+    tensor takes the same arithmetic in torch ops, in torch's summation order."""
+    if not isinstance(feats, torch.Tensor) or feats.ndim != 2 or feats.shape[0] % 2 != 0 or feats.shape[1] < 1:
+        raise ValueError(f'pair_sqdist: expected [2n, W] feature rows, got {getattr(feats, "shape", type(feats))}')
+    n, width = feats.shape[0] // 2, int(feats.shape[1])
+    if out is None:
+        out = torch.empty([n], dtype=torch.float32, device=feats.device)
+    elif out.shape != (n,) or out.dtype != torch.float32 or out.device != feats.device or not out.is_contiguous():
+        raise ValueError(f'pair_sqdist: out must be a contiguous fp32 [{n}] tensor on {feats.device}')
+    if not feats.is_cuda:
+        a, b = feats.float().chunk(2)
+        out.copy_(((a - b).double().square().sum(dim=1) * float(inv_scale)).float())
+        return out
+    from . import _lib
+    feats = _lib.f32c(feats)
+    if n == 0:
+        return out
+    need = int(_lib.load().tdgp_pair_sqdist_workspace_bytes(n, width))
+    if need < 0:
+        raise _lib.Unsupported(f'tdgp_pair_sqdist refuses {n} pairs of {width} features')
+    ws = torch.empty([max(need, 16)], dtype=torch.uint8, device=feats.device)
+    with torch.cuda.device(feats.device):
+        _lib.call('tdgp_pair_sqdist', feats.data_ptr(), n, width, float(inv_scale), out.data_ptr(), ws.data_ptr(), need, _lib.stream_of(feats))
+    return out
+
+
+def ppl_image_tail(img, crop, factor):
+    """perceptual_path_length.py:71-85 on a CHW image batch in torch ops: centre crop, box mean, [-1, 1] -> [0, 255], grey replicated.  The
+    route of a synthesis network that returns images; the renderer's ray-major frames take `renderer.ppl_frames` (one launch)."""
+    if crop:
+        assert img.shape[2] == img.shape[3]
+        c = img.shape[2] // 8
+        img = img[:, :, c * 3: c * 7, c * 2: c * 6]
+    if factor > 1:
+        img = img.reshape([-1, img.shape[1], img.shape[2] // factor, factor, img.shape[3] // factor, factor]).mean([3, 5])
+    img = (img + 1) * (255 / 2)
+    if img.shape[1] == 1:
+        img = img.repeat([1, 3, 1, 1])
+    return img
+
+
+class PPLSampler(torch.nn.Module):
+    """perceptual_path_length.py:35-90 for a generator that renders through cameras and sampled rays: one call draws B pairs of latent codes
+    epsilon apart and returns their scaled squared detector distances [B] on the device.
+
+    `G`: any module with z_dim, c_dim, img_resolution, img_channels, mapping(z=, c=) and synthesis(ws=, camera_params=, noise_mode=,
+    u_coarse=, u_fine=, **G_kwargs); its synthesis exposes `cfg.num_ray_steps` and (optionally) `test_resolution`, which size the renderer
+    draws.  The sampler works on a deep copy, so the caller's `noise_const` buffers are never touched.  `detector(img)`: [2B,3,H,W] fp32 in
+    [0, 255] -> [2B, W_feat] fp32, built so that the squared L2 distance of two rows is LPIPS (the reference's TorchScript VGG16:
+    `lambda x: vgg16(x, resize_images=False, return_lpips=True)`); it stays the caller's.
+
+    Draw order of one call (the reference's, :48-66, then the two this project adds): t; z0, z1; [mapping]; every `.noise_const` buffer in
+    named_buffers() order; the camera (when none is passed: one per pair from the prior); u_coarse, u_fine (one set for the B pairs, in
+    `renderer.Draws.filled`'s shapes and order).  Both endpoints of a pair are rendered with the same camera and the same draws -- with
+    separate draws they would differ by sampling noise, which the division by epsilon^2 turns into the whole result.  The t endpoints and
+    the t + epsilon endpoints are rendered as two calls of B images (not one of 2B), so that the two images of a pair pass through the same
+    batch position of every kernel: endpoints with bit-identical codes give bit-identical images and a distance of exactly 0.
+    `epsilon == 0` (no differential quotient exists) returns the unscaled squared distances."""
+
+    def __init__(self, G, detector, epsilon, space, sampling, crop, camera_cfg=None, G_kwargs=None, target_resolution=256):
+        assert space in ['z', 'w']
+        assert sampling in ['full', 'end']
+        super().__init__()
+        import copy
+        self.G = copy.deepcopy(G)
+        self.detector = detector
+        self.epsilon = float(epsilon)
+        self.space, self.sampling, self.crop = space, sampling, bool(crop)
+        self.camera_cfg = camera_base() if camera_cfg is None else camera_cfg
+        self.G_kwargs = {} if G_kwargs is None else dict(G_kwargs)
+        self.factor = max(int(self.G.img_resolution) // int(target_resolution), 1)
+        opts = self.G_kwargs.get('render_opts', {})
+        if float(opts.get('cut_quantile', 0.0)) > 0.0 or any(opts.get(k) for k in ('return_depth', 'return_depth_adapted', 'concat_depth')):
+            raise ValueError('PPLSampler renders plain images: no cut_quantile, no depth outputs in G_kwargs["render_opts"]')
+
+    def draw_latents(self, batch, device):
+        """:51: z0, z1 = randn([2B, z_dim]).chunk(2)."""
+        return torch.randn([batch * 2, self.G.z_dim], device=device).chunk(2)
+
+    def draw(self, c, camera_params=None):
+        """Steps 1-6 of a call -> TensorGroup(t [B], z0, ws0, ws1 [B,num_ws,w_dim], camera_params, u_coarse [B,R,S], u_fine [B,R,N])."""
+        from . import renderer as _renderer
+        G, B, device = self.G, c.shape[0], c.device
+        t = torch.rand([B], device=device) * (1 if self.sampling == 'full' else 0)
+        z0, z1 = self.draw_latents(B, device)
+        if self.space == 'w':
+            w0, w1 = G.mapping(z=torch.cat([z0, z1]), c=torch.cat([c, c])).chunk(2)
+            ws0 = w0.lerp(w1, t.unsqueeze(1).unsqueeze(2))
+            ws1 = w0.lerp(w1, t.unsqueeze(1).unsqueeze(2) + self.epsilon)
+        else:
+            zt0 = slerp(z0, z1, t.unsqueeze(1))
+            zt1 = slerp(z0, z1, t.unsqueeze(1) + self.epsilon)
+            ws0, ws1 = G.mapping(z=torch.cat([zt0, zt1]), c=torch.cat([c, c])).chunk(2)
+        for name, buf in G.named_buffers():
+            if name.endswith('.noise_const'):
+                buf.copy_(torch.randn_like(buf))
+        if camera_params is None:
+            camera_params = sample_camera_params(self.camera_cfg, B, device)
+        if getattr(G.synthesis, 'camera_adaptor', None) is not None:
+            camera_params = G.synthesis.camera_adaptor(camera_params, z0, c)
+        res = int(getattr(G.synthesis, 'test_resolution', G.img_resolution))
+        steps = int(G.synthesis.cfg.num_ray_steps)
+        draws = _renderer.Draws(B, res * res).filled(steps, steps, 0.0, device)
+        return TensorGroup(t=t, z0=z0, ws0=ws0, ws1=ws1, camera_params=camera_params, u_coarse=draws.t['u_coarse'], u_fine=draws.t['u_fine'])
+
+    def endpoint_images(self, d):
+        """Step 7: the 2B detector inputs [2B,3,oh,ow] fp32 in [0, 255], the t endpoints first (`chunk(2)` splits them again)."""
+        from . import generator as _generator, renderer as _renderer
+        syn = self.G.synthesis
+        kw = dict(camera_params=d.camera_params, noise_mode='const', u_coarse=d.u_coarse, u_fine=d.u_fine, **self.G_kwargs)
+        if isinstance(syn, _generator.SynthesisNetwork) and d.ws0.is_cuda:
+            res = syn.train_resolution if syn.training else syn.test_resolution
+            frames = torch.cat([syn(ws=ws, ray_major=True, **kw).rgb for ws in (d.ws0, d.ws1)])
+            return _renderer.ppl_frames(frames, res, res, crop=self.crop, factor=self.factor)
+        return ppl_image_tail(torch.cat([syn(ws=ws, **kw) for ws in (d.ws0, d.ws1)]), self.crop, self.factor)
+
+    @torch.no_grad()
+    def forward(self, c, camera_params=None, out=None):
+        d = self.draw(c, camera_params)
+        feats = self.detector(self.endpoint_images(d))
+        inv_scale = 1.0 / (self.epsilon * self.epsilon) if self.epsilon != 0.0 else 1.0
+        return pair_sqdist(feats, inv_scale, out=out)
+
+
+def compute_ppl(G, detector, num_samples, epsilon, space, sampling, crop, batch_size, camera_cfg=None, c_sampler=None, dataset=None, num_gpus=1, rank=0,
+                gatherer=None, device='cuda', G_kwargs=None):
+    """perceptual_path_length.py:94-123: `num_samples` path-length samples in batches of `batch_size` pairs per rank -> `aggregate_ppl` of them.
+    Labels (and, with them, the cameras of the prior or the dataset's custom angles) come from `iterate_random_conditioning`; with
+    `c_sampler(batch) -> c` the sampler draws the cameras itself.  One sampler call per iteration; the [batch] block of every rank is
+    appended in rank order (:109-113; `gatherer`: a `distributed.FeatureGatherer`, created on demand when num_gpus > 1) into one preallocated
+    device buffer, which is cut to `num_samples` at the end.  Nothing crosses to the host inside the loop; `aggregate_ppl` reads one number
+    back.  Ranks other than 0 return NaN."""
+    assert 0 <= rank < num_gpus
+    num_samples, batch_size = int(num_samples), int(batch_size)
+    assert num_samples >= 1 and batch_size >= 1
+    device = torch.device(device)
+    sampler = PPLSampler(G, detector, epsilon, space, sampling, crop, camera_cfg=camera_cfg, G_kwargs=G_kwargs)
+    sampler.eval().requires_grad_(False).to(device)
+    if c_sampler is not None:
+        def cond():
+            while True:
+                yield c_sampler(batch_size).to(device), None
+        cond = cond()
+    else:
+        cond = iterate_random_conditioning(G, batch_size, device, camera_cfg, dataset)
+    if num_gpus > 1 and gatherer is None:
+        from .distributed import FeatureGatherer
+        gatherer = FeatureGatherer(side_stream=False)
+    step = batch_size * num_gpus
+    dist = torch.empty([-(-num_samples // step) * step], dtype=torch.float32, device=device)
+    for start in range(0, num_samples, step):
+        c, camera_params = next(cond)
+        if num_gpus == 1:
+            sampler(c, camera_params, out=dist[start:start + batch_size])
+            continue
+        x = gatherer.gather(sampler(c, camera_params).unsqueeze(1))          # [batch * world, 1], row i from rank i % world
+        dist[start:start + step] = x.reshape(batch_size, num_gpus).t().reshape(-1)      # -> the ranks' blocks one after the other
+    if rank != 0:
+        return float('nan')
+    return aggregate_ppl(dist[:num_samples])
+
+
+def ppl_for_generator(G, detector, num_samples=50000, epsilon=1e-4, space='w', sampling='end', crop=False, batch_size=2, **kw):
+    """A perceptual path length of a generator (`compute_ppl`, whose keywords `kw` are), drawn and kept where the generator lives; NaN on
+    ranks other than 0 as in the reference."""
+    kw.setdefault('device', _device_of(G))
+    value = compute_ppl(G, detector, num_samples, epsilon, space, sampling, crop, batch_size, **kw)
+    return value if kw.get('rank', 0) != 0 else _checked(G, value)
+
+
+def ppl2_wend(G, detector, **kw):
+    """The registry entry 'ppl2_wend' (metric_main.py:105-108): 50 000 samples, epsilon 1e-4, W space, end points, no crop, 2 pairs per batch."""
+    args = dict(num_samples=50000, epsilon=1e-4, space='w', sampling='end', crop=False, batch_size=2)
+    args.update(kw)
+    return dict(ppl2_wend=ppl_for_generator(G, detector, **args))

@@ -269,6 +269,24 @@ def rays_to_image(x, h, w):
     return img
 
 
+def ppl_frames(frames, h, w, crop=False, factor=1):
+    """Ray-major frames [B, h*w, C] (C = 1 or 3) -> [B, 3, oh, ow] fp32 in [0, 255]: the image tail of the perceptual path length
+    (perceptual_path_length.py:71-85 behind the reshape above) in one launch of tdgp_ppl_frames -- centre crop, `factor` x `factor` box mean,
+    `(x + 1) * 127.5`, grey replicated; the arithmetic is the contract in include/tdgp.h.  A shape the kernel refuses raises before a launch."""
+    _lib.require_cuda(frames, 'ppl_frames: frames')
+    frames = _lib.f32c(frames)
+    h, w, factor = int(h), int(w), int(factor)
+    if frames.ndim != 3 or frames.shape[1] != h * w:
+        raise ValueError(f'ppl_frames: expected ray-major frames [B, {h * w}, C], got {tuple(frames.shape)}')
+    side_h, side_w = (4 * (h // 8), 4 * (h // 8)) if crop else (h, w)
+    oh, ow = (side_h // factor, side_w // factor) if factor >= 1 else (0, 0)
+    B = frames.shape[0]
+    out = torch.empty([B, 3, oh, ow], dtype=torch.float32, device=frames.device)
+    with torch.cuda.device(frames.device):
+        _lib.call('tdgp_ppl_frames', frames.data_ptr(), B, h, w, int(frames.shape[2]), int(bool(crop)), factor, out.data_ptr(), _lib.stream_of(frames))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ explicit draws and results of a split call
 
 class Draws:

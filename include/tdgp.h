@@ -439,6 +439,37 @@ int tdgp_frames_to_grid_u8(const float* frames, int64_t num_frames, int h, int w
                            int64_t stride_image, int64_t stride_tile, int nrow, int padding, int normalise, float mid, float range,
                            tdgp_stream_t stream);
 
+/* The image tail of the perceptual path length in one launch (src/metrics/perceptual_path_length.py:71-85: centre crop, box mean down to
+ * 256^2, `(img + 1) * (255 / 2)`, grey replicated; with the reshape of networks_epigraf.py:242 in front of it).
+ * frames [num_frames, h*w, C] fp32 ray-major (the renderer's rgb; C = 1 or 3) -> out [num_frames, 3, oh, ow] fp32 in [0, 255].
+ * Window: the whole frame, or with `crop` rows [3c, 7c) and columns [2c, 6c) for c = h / 8 (needs h == w and c >= 1, else TDGP_EINVAL).
+ * Both window sides must divide by `factor` >= 1; oh, ow = the window sides / factor.
+ * Values: factor == 1: y = (x + 1.0f) * 127.5f, two fp32 roundings, no FMA contraction -- the bits of torch's CPU chain.
+ *   factor > 1: the factor x factor box is summed in fp64 in row-major order, divided by factor^2 in fp64 and rounded once to fp32 (the
+ *   correctly rounded mean; torch's fp32 `mean` is within factor^2 * 2^-24 * max|x| of it); then the same two operations.
+ * C == 1 is written to all three channels.  One writer per element, no atomics, no workspace: the same bytes on every run.  Arguments are
+ * checked before any launch; num_frames == 0 is a no-op.  frames and out 4-byte aligned; h * w < 2^31. */
+int tdgp_ppl_frames(const float* frames, int64_t num_frames, int h, int w, int C, int crop, int factor, float* out, tdgp_stream_t stream);
+
+/* The differential distance of the perceptual path length (perceptual_path_length.py:88-89: `(l0 - l1).square().sum(1) / epsilon ** 2` on
+ * the two halves of the detector's output, in torch two full-width temporaries and an fp32 sum next to cancellation).
+ * feats [2n, W] fp32 contiguous, row i paired with row n + i (the layout `chunk(2)` splits) -> out[i], i < n.
+ * Arithmetic: d = a - b in fp32 (one rounding); d * d and every addition in fp64; out[i] = (float)(sum * inv_scale), rounded once;
+ *   inv_scale = 1 / (epsilon * epsilon), computed by the caller in double.  NaN and Inf propagate (into their own row only).
+ * The summation tree is fixed by W alone: a row is cut into segments of 16384 elements, one block each; inside a segment an element's
+ *   place in the sum follows from its index, never from its address (rows are only 4-byte aligned when W % 4 != 0: a quad is read by one
+ *   16-byte load where its address allows and by four 4-byte loads otherwise, and enters the same sum either way); the segment partials of a
+ *   row are added in index order by a finishing pass.  Neither the number of segments nor their bounds depend on n, so a row's bits do not
+ *   depend on the call it is computed in.  No atomics, one writer per partial and output: the same bytes on every run.
+ * `out` may point anywhere (4-byte aligned) into a larger buffer; only out[0 .. n) is written.  n == 0 is a no-op.
+ * Limits: 1 <= W < 2^31 and 0 <= n <= 65535; W < 1 or n < 0: TDGP_EINVAL, above the upper ends: TDGP_EUNSUPPORTED.
+ * workspace: tdgp_pair_sqdist_workspace_bytes(n, W) bytes (0 when a row is one segment; -1 for a shape it refuses), 8-byte aligned,
+ * caller-owned; too small: TDGP_EWORKSPACE.  A streaming reduction: its point is the defined fp64 arithmetic, reproducible bytes and the
+ * absent temporaries, not speed -- the generator and the caller's detector are the expensive part of the metric. */
+int64_t tdgp_pair_sqdist_workspace_bytes(int64_t n, int64_t W);
+int     tdgp_pair_sqdist(const float* feats, int64_t n, int64_t W, double inv_scale, float* out, void* workspace, int64_t workspace_bytes,
+                         tdgp_stream_t stream);
+
 /* create_voxel_coords (scripts/extract_geometry.py:55-76; torch CPU ops over the whole grid there): the coordinates of grid indices
  * [i0, i0 + n) of a res^3 grid -> coords [n,3], bit for bit the reference's fp32 chain: the index converted to fp32 (inexact above 2^24),
  * y = (idx / res) % res and x = ((idx / res) / res) % res as UNFLOORED fp32 divisions, z from the integer remainder, then
