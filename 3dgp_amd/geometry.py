@@ -54,17 +54,27 @@ def density_grid(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=
     their sigma column is copied into the grid.  Temporaries are O(slab_points); the grid itself is the only O(res^3) tensor."""
     syn = G.synthesis
     _lib.require_cuda(ws, 'ws')
+    planes = _renderer.planes_to_hwc(syn.tri_plane_decoder(ws[:, :syn.tri_plane_decoder.num_ws], hwc=True, noise_mode=noise_mode))
+    return density_grid_from_planes(G, planes, volume_res, voxel_origin, cube_size, slab_points)
+
+
+@torch.no_grad()
+def density_grid_from_planes(G, planes, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=0.3, slab_points=2 ** 22):
+    """`density_grid` behind the backbone: the same grid from the HWCPlanes the backbone returned, for callers that use those planes again
+    (mesh.py renders field normals from them)."""
+    syn = G.synthesis
+    _lib.require_cuda(planes.t, 'planes')
+    dev = planes.t.device
     res = int(volume_res)
     total = res ** 3
     slab = int(min(max(int(slab_points), 1), total, FIELD_POINTS_MAX))
-    planes = _renderer.planes_to_hwc(syn.tri_plane_decoder(ws[:, :syn.tri_plane_decoder.num_ws], hwc=True, noise_mode=noise_mode))
     mlp, scale = syn.tri_plane_mlp, syn.cfg.cube_scale
     fused = _renderer.fused_form(mlp) or _renderer.deep_form(mlp)          # a field kernel evaluates it: two layers, or the deep form (3 / 4)
     params = (_renderer._mlp_params_deep(mlp) if _renderer.deep_form(mlp) else _renderer._mlp_params(mlp)) if fused else None
     consts = _grid_constants(res, voxel_origin, cube_size)
     B = planes.t.shape[0]
-    grid = torch.empty([B, total], dtype=torch.float32, device=ws.device)
-    coords = torch.empty([slab, 3], dtype=torch.float32, device=ws.device)
+    grid = torch.empty([B, total], dtype=torch.float32, device=dev)
+    coords = torch.empty([slab, 3], dtype=torch.float32, device=dev)
     for i0 in range(0, total, slab):
         n = min(slab, total - i0)
         c = _voxel_coords_into(coords[:n], i0, res, consts).unsqueeze(0)
@@ -73,7 +83,6 @@ def density_grid(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=
             rgbs = _renderer._field(pb, params, scale, coords=c) if fused else _renderer._field_eager(pb, mlp, scale, coords=c)
             grid[b, i0:i0 + n] = rgbs[0, :, -1]
     return grid.reshape(B, res, res, res)
-
 
 
 def crop_reference(res):
@@ -111,26 +120,68 @@ def marching_cubes(volume, thresh):
     return verts, tris
 
 
+def _crop_slices(crop, volume_res):
+    """'reference' | None | three slices -> three slices or None."""
+    if isinstance(crop, str):
+        if crop != 'reference':
+            raise ValueError("crop must be 'reference', None or three slices")
+        return crop_reference(volume_res)
+    if crop is None:
+        return None
+    crop = tuple(crop)
+    if len(crop) != 3 or not all(isinstance(s, slice) for s in crop):
+        raise ValueError("crop must be 'reference', None or three slices")
+    return crop
+
+
+@torch.no_grad()
+def grid_to_world(vertices, volume_res, voxel_origin=(0.0, 0.0, 0.0), cube_size=0.3, crop='reference', sheared=True):
+    """Mesh vertices in index units (d, h, w) of a CROPPED grid (`marching_cubes` of `sigma[crop]`) -> [V,3] fp32 world coordinates (x, y, z),
+    the space `create_voxel_coords` samples and the cameras live in.  The start of each crop slice is added (`slice.indices`: Python's floor
+    semantics for negative bounds), then the affine map whose values at integer grid indices are the points `create_voxel_coords` generates.
+    That grid is sheared (extract_geometry.py:64-65: `(idx.float() / res) % res` keeps its fraction):
+        x = (d + h / res + w / res^2) * voxel_size + origin_x,   y = (h + w / res) * voxel_size + origin_y,   z = w * voxel_size + origin_z
+    with voxel_size and the origins as `_grid_constants` returns them, each rounded to fp32 as tdgp_voxel_coords takes them.  sheared=False
+    drops the fractional terms: the plain lattice the reference's authors meant.  Computed in float64 on the vertices' device, rounded once."""
+    res = int(volume_res)
+    if res < 2:
+        raise ValueError(f'volume_res must be at least 2, got {volume_res!r}')
+    v = torch.as_tensor(vertices)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError(f'grid_to_world takes [V,3] vertices, got {tuple(v.shape)}')
+    crop = _crop_slices(crop, res)
+    starts = [0, 0, 0] if crop is None else [s.indices(res)[0] for s in crop]
+    vs, ox, oy, oz = (float(np.float32(c)) for c in _grid_constants(res, voxel_origin, cube_size))
+    v = v.to(torch.float64)
+    d, h, w = (v[:, i] + float(starts[i]) for i in range(3))
+    if sheared:
+        x, y = d + h / res + w / (res * res), h + w / res
+    else:
+        x, y = d, h
+    return torch.stack([x * vs + ox, y * vs + oy, w * vs + oz], dim=1).to(torch.float32)
+
+
 @torch.no_grad()
 def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=0.3, thresh_value=25.0, crop='reference', normalize=True,
-                     slab_points=2 ** 22, noise_mode='const'):
+                     slab_points=2 ** 22, noise_mode='const', units='index', sheared=True):
     """scripts/extract_geometry.py:26-42 per sample of `ws`: density grid -> crop -> marching cubes -> (optionally) scale.  Returns a list of
     Shape(vertices [V,3] fp32, triangles [T,3] int32, sigma [D,H,W] fp32 -- the cropped grid), all on the device.
     crop: 'reference' (extract_geometry.py:33), None, or three slices.  normalize: divide the vertices by the length of their bounding-box
-    diagonal (`mesh.apply_scale(1.0 / mesh.scale)`, extract_geometry.py:42 -- trimesh's `scale`; no translation)."""
-    if crop == 'reference':
-        crop = crop_reference(volume_res)
-    elif crop is not None:
-        crop = tuple(crop)
-        if len(crop) != 3 or not all(isinstance(s, slice) for s in crop):
-            raise ValueError("crop must be 'reference', None or three slices")
+    diagonal (`mesh.apply_scale(1.0 / mesh.scale)`, extract_geometry.py:42 -- trimesh's `scale`; no translation).
+    units='world': the vertices go through `grid_to_world` with this call's volume_res / voxel_origin / cube_size / crop (and `sheared`)
+    instead of `normalize` -- the mesh `mesh.render_mesh_views` takes."""
+    if units not in ('index', 'world'):
+        raise ValueError(f"units must be 'index' or 'world', got {units!r}")
+    crop = _crop_slices(crop, volume_res)
     out = []
     for b in range(ws.shape[0]):               # one sample's grid alive at a time, as the reference loops
         sigma = density_grid(G, ws[b:b + 1], volume_res, voxel_origin, cube_size, slab_points, noise_mode)[0]
         if crop is not None:
             sigma = sigma[crop]
         verts, tris = marching_cubes(sigma, thresh_value)
-        if normalize and verts.shape[0] > 0:
+        if units == 'world':
+            verts = grid_to_world(verts, volume_res, voxel_origin, cube_size, crop, sheared)
+        elif normalize and verts.shape[0] > 0:
             diag = (verts.max(dim=0).values - verts.min(dim=0).values).norm()
             if float(diag) > 0:
                 verts = verts / diag
@@ -155,11 +206,22 @@ def save_obj(path, vertices, triangles):
         fh.write(''.join(f'f {a + 1} {b + 1} {c + 1}\n' for a, b, c in f.tolist()))
 
 
-def save_ply(path, vertices, triangles):
-    """Binary little-endian .ply: float32 x y z per vertex, then per face a uchar count (3) and three int32 indices."""
+def save_ply(path, vertices, triangles, colours=None):
+    """Binary little-endian .ply: float32 x y z per vertex, then per face a uchar count (3) and three int32 indices.  colours [V,3] (uint8, or
+    floating point in [0, 1]: clamped, scaled by 255 and rounded): `uchar red green blue` follow each vertex's coordinates."""
     v, f = _host(vertices, '<f4').reshape(-1, 3), _host(triangles, '<i4').reshape(-1, 3)
+    rgb_props = ''
+    if colours is not None:
+        c = colours.detach().cpu().numpy() if isinstance(colours, torch.Tensor) else np.asarray(colours)
+        if c.shape != v.shape:
+            raise ValueError(f'colours must be [V,3] like the vertices {v.shape}, got {c.shape}')
+        if c.dtype != np.uint8:
+            c = np.rint(np.clip(np.nan_to_num(c.astype(np.float64)), 0.0, 1.0) * 255.0).astype(np.uint8)
+        rec = np.empty(len(v), dtype=[('p', '<f4', (3,)), ('c', 'u1', (3,))])
+        rec['p'], rec['c'] = v, c
+        v, rgb_props = rec, 'property uchar red\nproperty uchar green\nproperty uchar blue\n'
     header = ('ply\nformat binary_little_endian 1.0\n'
-              f'element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n'
+              f'element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n{rgb_props}'
               f'element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n')
     faces = np.empty(len(f), dtype=[('n', 'u1'), ('i', '<i4', (3,))])
     faces['n'], faces['i'] = 3, f

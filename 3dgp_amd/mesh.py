@@ -1,0 +1,316 @@
+"""Mesh frames: the indexed mesh `geometry.marching_cubes` leaves on the device, rasterised from the cameras.
+
+`shapes.render_shape_views` finds the surface of a density level on the rays, S + N + 7 field points per ray per frame.  The surface does not
+change between the frames of a turn-table, so here it is extracted once per sample (`density_grid` -> `marching_cubes` -> `grid_to_world`)
+and every frame is a visibility buffer of that mesh: tdgp_mesh_visibility (one triangle per lane, a 64-bit atomic minimum of (depth bits,
+triangle) per covered pixel) -> tdgp_mesh_resolve (depth, face normal, colour, the 7 stencil points) -> tdgp_mesh_shade, or -- for smooth
+normals -- the field at the 7 points and tdgp_iso_shade: 7 field points per pixel instead of 87.
+
+The arithmetic of the three kernels is fixed operation by operation (include/tdgp.h); the minimum does not depend on the order of its
+operands, so frames are the same bytes on every run, under every permutation of the triangles and every chunking of the cameras.  Limits:
+no clipping at the near plane (a triangle with a vertex nearer than `near` is dropped whole: the cameras sit outside the cube), flat normals
+in 'face' mode, one mesh per call, no anti-aliasing.  GPU only: the kernels have no CPU path.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from . import geometry as _geometry
+from . import inference as _inference
+from . import renderer as _renderer
+from . import shapes as _shapes
+from .generator import TensorGroup
+from .geometry import FIELD_POINTS_MAX
+
+MODES = _shapes.MODES
+CULL = {'none': 0, 'back': 1, 'front': 2}
+NORMALS = ('face', 'field')
+STENCIL = _shapes.STENCIL
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the three kernels on tensors
+# ----------------------------------------------------------------------------------------------------------------------
+def _check_mesh(vertices, triangles):
+    for t, what in ((vertices, 'vertices'), (triangles, 'triangles')):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f'{what} must be a tensor, got {type(t).__name__}')
+    if vertices.dtype != torch.float32 or vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError(f'vertices must be fp32 [V,3], got {vertices.dtype} {tuple(vertices.shape)}')
+    if triangles.dtype != torch.int32 or triangles.ndim != 2 or triangles.shape[1] != 3:
+        raise ValueError(f'triangles must be int32 [T,3], got {triangles.dtype} {tuple(triangles.shape)}')
+    _lib.require_cuda(vertices, 'vertices')
+    _lib.require_cuda(triangles, 'triangles')
+    return vertices.contiguous(), triangles.contiguous()
+
+
+def focal_lengths(fov, C, device):
+    """[C] fp32 1 / tan(fov / 2) of fields of view in degrees (a number, or a tensor of C): the angle as tdgp_sample_rays forms it in fp32, its
+    tangent in float64 rounded once, so that the pixel grid of the rasteriser is the one the rays were shot through."""
+    f = fov.to(device=device, dtype=torch.float32).reshape(-1) if isinstance(fov, torch.Tensor) else torch.full([1], float(fov), dtype=torch.float32, device=device)
+    if f.numel() == 1:
+        f = f.expand(C)
+    if f.numel() != C:
+        raise ValueError(f'fov must be a number or have {C} elements, got {f.numel()}')
+    half = (f / 360.0 * 2.0 * float(np.float32(np.pi))) * 0.5
+    return (1.0 / torch.tan(half.double()).float()).contiguous()
+
+
+def mesh_visibility(vertices, triangles, c2w, focal, ray_d, resolution, near=1e-3, cull='none'):
+    """tdgp_mesh_visibility: vertices [V,3] fp32 (world), triangles [T,3] int32, c2w [C,4,4], focal [C], ray_d [C,h*w,3] -> vis int64 [C,h*w]
+    (the kernel's uint64 keys: -1 is an empty pixel, otherwise (bits(t) << 32) | triangle).  resolution: (w, h) as `sample_rays` takes it."""
+    if cull not in CULL:
+        raise ValueError(f'cull must be one of {sorted(CULL)}, got {cull!r}')
+    vertices, triangles = _check_mesh(vertices, triangles)
+    w, h = (int(resolution), int(resolution)) if np.isscalar(resolution) else (int(r) for r in resolution)
+    _lib.require_cuda(ray_d, 'ray_d')
+    c2w, focal, ray_d = _lib.f32c(c2w), _lib.f32c(focal), _lib.f32c(ray_d)
+    C = int(c2w.shape[0]) if c2w.ndim == 3 else -1
+    if tuple(c2w.shape) != (C, 4, 4) or focal.numel() != C or ray_d.numel() != C * h * w * 3:
+        raise ValueError(f'mesh_visibility: c2w [C,4,4], focal [C], ray_d [C,{h * w},3] expected, got {tuple(c2w.shape)}, {tuple(focal.shape)}, {tuple(ray_d.shape)}')
+    if not float(near) > 0.0:
+        raise ValueError(f'near must be positive, got {near!r}')
+    vis = torch.empty([C, h * w], dtype=torch.int64, device=vertices.device)
+    with torch.cuda.device(vertices.device):
+        _lib.call('tdgp_mesh_visibility', vertices.data_ptr(), vertices.shape[0], triangles.data_ptr(), triangles.shape[0], c2w.data_ptr(), focal.data_ptr(),
+                  ray_d.data_ptr(), C, h, w, float(near), CULL[cull], vis.data_ptr(), _lib.stream_of(vertices))
+    return vis
+
+
+def mesh_resolve(vis, vertices, triangles, ray_o, ray_d, step, t_miss, vertex_rgb=None):
+    """tdgp_mesh_resolve -> (t_hit [rays], status int32 [rays], tri int32 [rays], normal [rays,3], colour [rays,3] or None, points [rays,7,3])."""
+    vertices, triangles = _check_mesh(vertices, triangles)
+    _lib.require_cuda(vis, 'vis')
+    if vis.dtype != torch.int64:
+        raise ValueError(f'vis must be the int64 tensor mesh_visibility returns, got {vis.dtype}')
+    vis, ray_o, ray_d = vis.contiguous(), _lib.f32c(ray_o), _lib.f32c(ray_d)
+    rays = vis.numel()
+    if ray_o.numel() != rays * 3 or ray_d.numel() != rays * 3:
+        raise ValueError(f'mesh_resolve: ray_o / ray_d [{rays}, 3] expected')
+    if vertex_rgb is not None:
+        if vertex_rgb.dtype != torch.float32 or tuple(vertex_rgb.shape) != tuple(vertices.shape):
+            raise ValueError(f'vertex_rgb must be fp32 {tuple(vertices.shape)}, got {vertex_rgb.dtype} {tuple(vertex_rgb.shape)}')
+        _lib.require_cuda(vertex_rgb, 'vertex_rgb')
+        vertex_rgb = vertex_rgb.contiguous()
+    dev = vertices.device
+    t_hit = torch.empty([rays], dtype=torch.float32, device=dev)
+    status = torch.empty([rays], dtype=torch.int32, device=dev)
+    tri = torch.empty([rays], dtype=torch.int32, device=dev)
+    normal = torch.empty([rays, 3], dtype=torch.float32, device=dev)
+    colour = None if vertex_rgb is None else torch.empty([rays, 3], dtype=torch.float32, device=dev)
+    points = torch.empty([rays, STENCIL, 3], dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call('tdgp_mesh_resolve', vis.data_ptr(), vertices.data_ptr(), vertices.shape[0], triangles.data_ptr(), triangles.shape[0], ray_o.data_ptr(),
+                  ray_d.data_ptr(), rays, float(step), float(t_miss), _lib.ptr(vertex_rgb), t_hit.data_ptr(), status.data_ptr(), tri.data_ptr(),
+                  normal.data_ptr(), _lib.ptr(colour), points.data_ptr(), _lib.stream_of(vertices))
+    return t_hit, status, tri, normal, colour, points
+
+
+def mesh_shade(normal, status, ray_d, colour=None, mode='shaded', light=None, ambient=0.2, albedo=(0.8, 0.8, 0.8), background=(1.0, 1.0, 1.0)):
+    """tdgp_mesh_shade: normal [rays,3], status int32 [rays], ray_d [rays,3], colour [rays,3] in [0, 1] (mode 'colour') -> rgb [rays,3]."""
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
+    if mode == 'colour' and colour is None:
+        raise ValueError("mode 'colour' needs the colour mesh_resolve interpolated (give it vertex_rgb)")
+    _lib.require_cuda(normal, 'normal')
+    normal, ray_d = _lib.f32c(normal), _lib.f32c(ray_d)
+    rays = status.numel()
+    if normal.numel() != rays * 3 or ray_d.numel() != rays * 3 or status.dtype != torch.int32 or (colour is not None and (colour.dtype != torch.float32 or colour.numel() != rays * 3)):
+        raise ValueError(f'mesh_shade: normal [{rays}, 3], status int32 [{rays}], ray_d [{rays}, 3], colour fp32 [{rays}, 3] expected')
+    status = status.contiguous()
+    colour = None if colour is None else colour.contiguous()
+    rgb = torch.empty([rays, 3], dtype=torch.float32, device=normal.device)
+    with torch.cuda.device(normal.device):
+        _lib.call('tdgp_mesh_shade', normal.data_ptr(), status.data_ptr(), ray_d.data_ptr(), _lib.ptr(colour), rays, MODES[mode],
+                  None if light is None else _shapes._vec3(light, 'light'), float(ambient), _shapes._vec3(albedo, 'albedo'), _shapes._vec3(background, 'background'),
+                  rgb.data_ptr(), _lib.stream_of(normal))
+    return rgb
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# frames
+# ----------------------------------------------------------------------------------------------------------------------
+def _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_call):
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
+    if normals not in NORMALS:
+        raise ValueError(f'normals must be one of {NORMALS}, got {normals!r}')
+    if cull not in CULL:
+        raise ValueError(f'cull must be one of {sorted(CULL)}, got {cull!r}')
+    if normals == 'field' and (planes is None or G is None):
+        raise ValueError("normals='field' evaluates the field at the hits: it needs the generator G and the sample's planes (G.synthesis.tri_planes)")
+    if normals == 'face' and mode == 'colour' and vertex_colours is None:
+        raise ValueError("mode='colour' with normals='face' needs vertex_colours [V,3] (mesh.vertex_colours)")
+    if max_rays_per_call is not None and int(max_rays_per_call) < 1:
+        raise ValueError(f'max_rays_per_call must be positive, got {max_rays_per_call!r}')
+
+
+@torch.no_grad()
+def vertex_colours(G, planes, vertices, points_per_call=2 ** 22):
+    """The field's colour at the vertices of one sample's mesh (coords mode), `* 0.5 + 0.5`, clamped to [0, 1] -> [V,3] fp32."""
+    _lib.require_cuda(vertices, 'vertices')
+    point_field = _shapes.field_functions(G.synthesis)[1]
+    out = torch.empty([vertices.shape[0], 3], dtype=torch.float32, device=vertices.device)
+    step = int(min(max(int(points_per_call), 1), FIELD_POINTS_MAX))
+    for i0 in range(0, vertices.shape[0], step):
+        v = _lib.f32c(vertices[i0:i0 + step]).unsqueeze(0)
+        out[i0:i0 + step] = (point_field(planes, v)[0, :, :3] * 0.5 + 0.5).clamp_(0.0, 1.0)
+    return out
+
+
+@torch.no_grad()
+def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shaded', normals='face', cull='none', near=None, planes=None, G=None,
+                      vertex_colours=None, light=None, ambient=0.2, albedo=(0.8, 0.8, 0.8), background=(1.0, 1.0, 1.0), max_rays_per_call=None,
+                      t_miss=None, step=None):
+    """C frames of ONE mesh (vertices [V,3] fp32 in world units, triangles [T,3] int32, on the device) under C cameras (`camera_params`: angles,
+    radius, look_at, fov as the renderer takes them) at `resolution` (a side, or (w, h)).
+
+    -> TensorGroup(rgb [C,R,3], depth [C,R,1], normal [C,R,3], status int32 [C,R], tri int32 [C,R]), ray-major, on the device: the layout and
+    meanings of `shapes.render_shape_views`.  status 1: a hit, 0: a miss (rgb = background, normal = 0, tri = -1, depth = t_miss: default
+    cfg.ray_end with a generator, 0 without).  depth is the ray parameter of the hit.
+    normals='face': the flat normal of the hit triangle (its stored winding; marching cubes: toward lower density) -- no generator is needed, any
+    mesh renders.  normals='field': `planes` (this sample's, batch 1) and `G`: the field at the 7 stencil points of every pixel and
+    tdgp_iso_shade -- smooth normals, and mode='colour' takes the field's colour at the hit; `step` is the stencil step (default one
+    tri-plane texel).  mode='colour' with face normals interpolates `vertex_colours` [V,3] in [0, 1].
+    cull: 'none' | 'back' | 'front'.  near (default cfg.ray_start with a generator, else 1e-3): a triangle with a vertex nearer is dropped whole.
+    Cameras are taken in chunks of whole frames, max_rays_per_call rays at most (default 16 frames; never less than one frame): they are
+    independent, so the chunking does not change a byte."""
+    _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_call)
+    vertices, triangles = _check_mesh(vertices, triangles)
+    w, h = (int(resolution), int(resolution)) if np.isscalar(resolution) else (int(r) for r in resolution)
+    if h < 2 or w < 2:
+        raise ValueError(f'resolution must be at least 2 x 2, got {resolution!r}')
+    cfg = None if G is None else G.cfg
+    near = (float(cfg.ray_start) if cfg is not None else 1e-3) if near is None else float(near)
+    t_miss = (float(cfg.ray_end) if cfg is not None else 0.0) if t_miss is None else float(t_miss)
+    if step is None:
+        step = 2.0 * float(cfg.cube_scale) / int(cfg.tri_plane_res) if cfg is not None else 0.0
+    dev = vertices.device
+    R = h * w
+    get = _renderer.cam_get(camera_params)
+    c2w = _renderer.compute_cam2world_matrix(camera_params)
+    C = int(c2w.shape[0])
+    focal = focal_lengths(get('fov'), C, dev)
+    ray_o, ray_d = _renderer.sample_rays(c2w, fov=get('fov'), resolution=(w, h))
+    field = normals == 'field'
+    if field:
+        if G.synthesis.training:
+            raise RuntimeError('render_mesh_views is the inference route: call .eval() first')
+        if not isinstance(planes, _renderer.HWCPlanes) or int(planes.t.shape[0]) != 1:
+            raise TypeError("normals='field' takes the HWCPlanes of ONE sample (tri_planes of a batch of one, or HWCPlanes(planes.t[b:b + 1]))")
+        point_field = _shapes.field_functions(G.synthesis)[1]
+    vrgb = None
+    if not field and mode == 'colour':
+        vrgb = vertex_colours if vertex_colours.dtype == torch.float32 else vertex_colours.float() / (255.0 if vertex_colours.dtype == torch.uint8 else 1.0)
+    max_rays = 16 * R if max_rays_per_call is None else int(max_rays_per_call)
+    cstep = max(1, min(max_rays, FIELD_POINTS_MAX // STENCIL) // R)
+    out = _renderer.Gather(C, R)
+    for c0 in range(0, C, cstep):
+        cs = slice(c0, min(c0 + cstep, C))
+        n = (cs.stop - cs.start) * R
+        o, d = ray_o[cs].reshape(n, 3), ray_d[cs].reshape(n, 3)
+        vis = mesh_visibility(vertices, triangles, c2w[cs], focal[cs], d, (w, h), near=near, cull=cull)
+        t_hit, status, tri, normal, colour, points = mesh_resolve(vis.reshape(n), vertices, triangles, o, d, step, t_miss, vertex_rgb=vrgb)
+        if field:
+            stencil = point_field(planes, points.reshape(1, n * STENCIL, 3))
+            rgb, normal = _shapes.iso_shade(stencil, status, d, mode=mode, light=light, ambient=ambient, albedo=albedo, background=background)
+        else:
+            rgb = mesh_shade(normal, status, d, colour=colour, mode=mode, light=light, ambient=ambient, albedo=albedo, background=background)
+        k = cs.stop - cs.start
+        out.put(cs, slice(0, R), rgb=rgb.reshape(k, R, 3), depth=t_hit.reshape(k, R, 1), normal=normal.reshape(k, R, 3), status=status.reshape(k, R),
+                tri=tri.reshape(k, R))
+    if C == 0:
+        e = lambda *s, dt=torch.float32: torch.empty([0, R, *s], dtype=dt, device=dev)      # noqa: E731
+        return TensorGroup(rgb=e(3), depth=e(1), normal=e(3), status=e(dt=torch.int32), tri=e(dt=torch.int32))
+    rgb, depth, normal, status, tri = out.result()
+    return TensorGroup(rgb=rgb, depth=depth, normal=normal, status=status, tri=tri)
+
+
+def _camera_slice(camera_params, device, c0, c1):
+    """Cameras c0 .. c1 of an attribute bag or dict, fp32 on `device`."""
+    get = _renderer.cam_get(camera_params)
+    cam = {k: get(k).to(dtype=torch.float32, device=device)[c0:c1] for k in ('angles', 'radius', 'look_at')}
+    fov = get('fov')
+    cam['fov'] = fov.to(dtype=torch.float32, device=device).reshape(-1)[c0:c1] if isinstance(fov, torch.Tensor) and fov.numel() > 1 else fov
+    return cam
+
+
+@torch.no_grad()
+def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=None, crop=None, sheared=True,
+                       mode='shaded', normals='face', plane_batch=4, return_counts=False, **kw):
+    """Mesh frames of every `ws` under its cameras (sample-major: camera n * V + v is view v of sample n).  Per sample: `density_grid` at
+    volume_res^3 over a cube of `cube_size` (default the whole field, 2 * cfg.cube_scale) -> `marching_cubes` at `level` -> `grid_to_world`,
+    then its V cameras through `render_mesh_views`.  The backbone runs once per plane batch; its planes feed the density grid and, with
+    normals='field' (or face normals in mode 'colour'), the field lookups of the frames.
+    -> TensorGroup(rgb [B*V,R,3], depth, normal, status, tri) as `render_mesh_views`; return_counts=True: also [(vertices, triangles)] per sample.
+    kw: cull, near, light, ambient, albedo, background, max_rays_per_call, t_miss, step of `render_mesh_views`."""
+    syn, cfg = G.synthesis, G.cfg
+    num_samples = len(ws)
+    get = _renderer.cam_get(camera_params)
+    V = _renderer.views_per_sample(int(get('angles').shape[0]), num_samples, f'{num_samples} samples')
+    if int(plane_batch) < 1:
+        raise ValueError(f'plane_batch must be positive, got {plane_batch!r}')
+    _check_options(mode, normals, kw.get('cull', 'none'), True, G, True, kw.get('max_rays_per_call'))
+    if syn.training:
+        raise RuntimeError('render_mesh_frames is the inference route: call .eval() first (training mode renders patches with density noise)')
+    _lib.require_cuda(ws, 'ws')
+    cube_size = 2.0 * float(cfg.cube_scale) if cube_size is None else float(cube_size)
+    slices = _geometry._crop_slices(crop, volume_res)
+    res = syn.test_resolution
+    parts, counts = [], []
+    for n0 in range(0, num_samples, int(plane_batch)):
+        n1 = min(n0 + int(plane_batch), num_samples)
+        planes = syn.tri_planes(ws[n0:n1], noise_mode='const')
+        for b in range(n1 - n0):
+            pb = _renderer.HWCPlanes(planes.t[b:b + 1])
+            sigma = _geometry.density_grid_from_planes(G, pb, volume_res, voxel_origin, cube_size)[0]
+            if slices is not None:
+                sigma = sigma[slices]
+            verts, tris = _geometry.marching_cubes(sigma, level)
+            del sigma
+            verts = _geometry.grid_to_world(verts, volume_res, voxel_origin, cube_size, slices, sheared)
+            counts.append((int(verts.shape[0]), int(tris.shape[0])))
+            vc = vertex_colours(G, pb, verts) if (mode == 'colour' and normals == 'face') else None
+            cams = _camera_slice(camera_params, ws.device, (n0 + b) * V, (n0 + b + 1) * V)
+            parts.append(render_mesh_views(verts, tris, cams, res, mode=mode, normals=normals, planes=pb if normals == 'field' else None,
+                                           G=G, vertex_colours=vc, **kw))
+    frames = parts[0] if len(parts) == 1 else TensorGroup.cat(parts, dim=0)
+    return (frames, counts) if return_counts else frames
+
+
+def _shown(frames, show):
+    if show not in ('rgb', 'depth'):
+        raise ValueError(f"show must be 'rgb' or 'depth', got {show!r}")
+    return frames.depth if show == 'depth' else frames.rgb
+
+
+def render_mesh_video_grid(G, ws, camera_params, nrow='auto', show='rgb', num_videos=None, padding=2, as_numpy=False, return_counts=False, **kw):
+    """`shapes.render_shape_video_grid` of mesh frames: frame t of the video is the make_grid of every sample's mesh view t -> uint8
+    [T, GH, GW, 3] on the device (as_numpy=True: one copy to the host).  kw: the options of `render_mesh_frames`."""
+    if show not in ('rgb', 'depth'):
+        raise ValueError(f"show must be 'rgb' or 'depth', got {show!r}")
+    num_samples = len(ws)
+    V = int(_renderer.cam_get(camera_params)('angles').shape[0]) // max(num_samples, 1)
+    if nrow == 'auto':
+        nrow = int(np.ceil(min(num_samples if num_videos is None else num_videos, num_samples) ** 0.5))
+    res = G.synthesis.test_resolution
+    _inference.grid_shape(res, res, num_samples, nrow, padding)
+    frames, counts = render_mesh_frames(G, ws, camera_params, return_counts=True, **kw)
+    out = _inference.frames_to_grid(_shown(frames, show), res, res, tiles=num_samples, images=V, stride_image=1, stride_tile=V, nrow=nrow, padding=padding,
+                                    normalise=_inference._depth_normalisation(G) if show == 'depth' else None)
+    out = _inference._to_host(out) if as_numpy else out
+    return (out, counts) if return_counts else out
+
+
+def render_mesh_strips(G, ws, camera_params, show='rgb', as_numpy=False, return_counts=False, **kw):
+    """`shapes.render_shape_strips` of mesh frames: per sample, its mesh views side by side -> uint8 [num_samples, h, V * w, 3] on the device."""
+    if show not in ('rgb', 'depth'):
+        raise ValueError(f"show must be 'rgb' or 'depth', got {show!r}")
+    num_samples = len(ws)
+    V = int(_renderer.cam_get(camera_params)('angles').shape[0]) // max(num_samples, 1)
+    res = G.synthesis.test_resolution
+    frames, counts = render_mesh_frames(G, ws, camera_params, return_counts=True, **kw)
+    out = _inference.frames_to_grid(_shown(frames, show), res, res, tiles=V, images=num_samples, stride_image=V, stride_tile=1, nrow=V, padding=0,
+                                    normalise=_inference._depth_normalisation(G) if show == 'depth' else None)
+    out = _inference._to_host(out) if as_numpy else out
+    return (out, counts) if return_counts else out

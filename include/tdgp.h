@@ -538,6 +538,68 @@ int tdgp_iso_locate(const float* sigma, int64_t sigma_stride, const float* t, co
 int tdgp_iso_shade(const float* stencil, const int32_t* status, const float* ray_d, int64_t rays, int mode, const float* light, float ambient,
                    const float* albedo, const float* background, float* rgb, float* normal, tdgp_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mesh frames (csrc/mesh_raster.hip; nothing in the reference): the indexed mesh tdgp_mcubes_emit leaves on the device, in world units
+ * (geometry.grid_to_world), seen from the cameras of tdgp_sample_rays -- a visibility-buffer rasteriser for triangles smaller than a pixel:
+ *   tdgp_mesh_visibility -> tdgp_mesh_resolve -> tdgp_mesh_shade        (or, for normals from the field: -> field (coords mode, the 7
+ *   points per ray tdgp_mesh_resolve wrote) -> tdgp_iso_shade).
+ * Arithmetic contract of all three: every floating-point operation is rounded once, in the order written below (no contraction into FMA);
+ * `(double)` of a float is exact, `(double)` of an int64 and `(float)` of a double round to nearest even (the former is exact below 2^53);
+ * `/` and sqrt are correctly rounded in either width; comparisons are ordered (a NaN compares false).  Coverage is decided in exact int64
+ * arithmetic.  Arguments are checked before any launch; empty inputs are no-ops (C == 0 or rays == 0: nothing is written; T == 0: vis is
+ * only cleared); a vertex index outside [0, V) skips its triangle and is never dereferenced.
+ * The atomic: tdgp_mesh_visibility merges candidates with ONE unsigned 64-bit atomic minimum per covered pixel (global_atomic_umin_x2 on
+ * gfx950, a single native instruction, no compare-and-swap loop).  It is the library's first atomic whose result is not a floating-point
+ * sum: a minimum of integers does not depend on the order of its operands, so vis is the same bytes on every run and under every
+ * permutation of the triangles or of the launch order; ties in t go to the lower triangle index.
+ *
+ * tdgp_mesh_visibility: vertices [V,3] fp32 (world), triangles [T,3] int32, c2w [C,4,4] (m below, row-major, as tdgp_cam2world writes it:
+ *   columns right / up / -forward / position), focal [C] fp32 = 1 / tan(fov / 2) (computed by the caller in float64 and rounded once),
+ *   ray_d [C,h*w,3] of tdgp_sample_rays -> vis uint64 [C,h*w].  2 <= h, w <= 16384, C*h*w <= 2^30, C*T <= 2^38, near > 0, cull 0 (none),
+ *   1 (back faces dropped), 2 (front faces dropped).  vis is first set to all ones (empty).  Then per (camera, triangle k), in double:
+ *     per vertex i:  p_j = (double)v_j - (double)m[j][3];   xc = (p0*m[0][0] + p1*m[1][0]) + p2*m[2][0];   yc likewise with column 1;
+ *       zc = (p0*f0 + p1*f1) + p2*f2 with f_j = -m[j][2] (the depth along the camera axis).  not (zc >= near): the triangle is dropped whole
+ *       (there is no clipper).   fx = ((((xc*focal)/zc) + 1) * ((w-1)*0.5)) * 256;   fy = ((1 - ((yc*focal)/zc)) * ((h-1)*0.5)) * 256;
+ *       not (|fx| < 2^30 and |fy| < 2^30): dropped.   X_i = rint(fx), Y_i = rint(fy) (round half to even), iz_i = 1 / zc.
+ *       Pixel (row, col) has its centre at (X, Y) = (256 col, 256 row): the ray through x = -1 + 2 col/(w-1), y = 1 - 2 row/(h-1), z = -focal.
+ *     area2 = (X1-X0)*(Y2-Y0) - (Y1-Y0)*(X2-X0) in int64.  area2 == 0: skipped.  The screen's y points down, so a triangle whose stored winding
+ *       is counter-clockwise as the camera sees it (its normal faces the camera; marching cubes: toward lower density) has area2 < 0 and is a
+ *       front face: cull 1 drops area2 > 0, cull 2 drops area2 < 0.  s = sign(area2).
+ *     For every pixel of the bounding box [ceil(min X / 256), floor(max X / 256)] x [likewise in Y] clamped to the frame, with P its centre:
+ *       edge i runs from vertex a = i+1 to b = i+2 (mod 3):  dx = s*(X_b - X_a), dy = s*(Y_b - Y_a),  e_i = dx*(P_y - Y_a) - dy*(P_x - X_a);
+ *       the pixel is covered iff for all three edges e_i > 0, or e_i == 0 and the edge is a top or a left one (dy < 0, or dy == 0 and dx > 0):
+ *       a pixel centre on an edge shared by two triangles belongs to exactly one of them.  e_0 + e_1 + e_2 == |area2|.
+ *       depth = (double)|area2| / (((double)e_0*iz_0 + (double)e_1*iz_1) + (double)e_2*iz_2)     (perspective-correct: 1/z is linear on the screen)
+ *       t = (float)(depth / (((double)d0*f0 + (double)d1*f1) + (double)d2*f2)) for that pixel's own ray_d, so that o + t d is the hit whatever the
+ *       length of d.   not (t > 0 and t < inf): skipped.   key = ((uint64)bits(t) << 32) | (uint32)k;   vis[pixel] = min(vis[pixel], key).
+ *   Work shape: one lane per (camera, triangle); a lane whose clamped bounding box is wider or taller than 8 pixels hands its triangle to its
+ *   wave (64 lanes stride the box), so a frame-filling triangle costs h*w/64 steps of one wave.
+ *
+ * tdgp_mesh_resolve: vis [rays], the mesh, ray_o / ray_d [rays,3], vertex_rgb [V,3] or NULL -> t_hit [rays], status int32 [rays], tri int32
+ *   [rays], normal [rays,3], colour [rays,3] (NULL exactly when vertex_rgb is), points [rays,7,3].  One writer per element, no atomics.
+ *   vis all ones, or naming a triangle outside [0, T) or with a vertex outside [0, V): a miss -- status 0, t_hit = t_miss, tri = -1, normal =
+ *   colour = 0.  Otherwise status 1, tri = low word, t_hit = the float in the high word, and with a = v1 - v0, b = v2 - v0 in double:
+ *   g = (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0);  q = (g0*g0 + g1*g1) + g2*g2;  if q > 0 and q < inf: n_c = (float)(g_c / sqrt(q)), else
+ *   (fp32) n_c = (-d_c) / sqrtf((d0*d0 + d1*d1) + d2*d2), tdgp_iso_shade's own fallback.
+ *   For every ray, misses included (fp32): x_c = o_c + d_c * t_hit and the seven points of tdgp_iso_locate around it with h = step.
+ *   colour (double): e = x - v0;  d11 = (a.a), d12 = (a.b), d22 = (b.b), e1 = (e.a), e2 = (e.b), each (u0*w0 + u1*w1) + u2*w2;
+ *   den = d11*d22 - d12*d12;  b1 = (d22*e1 - d12*e2) / den;  b2 = (d11*e2 - d12*e1) / den;  if not (b1 >= 0) then b1 = 0, the same for b2;
+ *   sum = b1 + b2;  if sum > 1: b1 = b1 / sum, b2 = b2 / sum;  b0 = (1 - b1) - b2;  colour_c = (float)((b0*c0 + b1*c1) + b2*c2) with c_i vertex i's.
+ *
+ * tdgp_mesh_shade: normal, status, ray_d, colour (may be NULL unless mode is 2) -> rgb [rays,3].  tdgp_iso_shade's arithmetic from n on, in
+ *   fp32: l = light, or (-d_c) / sqrtf((d0*d0 + d1*d1) + d2*d2);  c = (n0*l0 + n1*l1) + n2*l2;  if not (c > 0) then c = 0;
+ *   v = ambient + (1 - ambient) * c.  mode 0: out_c = (albedo_c * v) * 2 - 1.  mode 1: out = n.  mode 2: k_c = colour_c (already in [0, 1]: the
+ *   * 0.5 + 0.5 of tdgp_iso_shade is applied once per vertex, mesh.vertex_colours); if not (k_c > 0) then k_c = 0; if k_c > 1 then k_c = 1;
+ *   out_c = (k_c * v) * 2 - 1.  status 0: out = background.  light / albedo / background: HOST pointers to 3 floats.
+ * --------------------------------------------------------------------------------------------- */
+int tdgp_mesh_visibility(const float* vertices, int64_t V, const int32_t* triangles, int64_t T, const float* c2w, const float* focal,
+                         const float* ray_d, int C, int h, int w, float near_, int cull, uint64_t* vis, tdgp_stream_t stream);
+int tdgp_mesh_resolve(const uint64_t* vis, const float* vertices, int64_t V, const int32_t* triangles, int64_t T, const float* ray_o,
+                      const float* ray_d, int64_t rays, float step, float t_miss, const float* vertex_rgb, float* t_hit, int32_t* status,
+                      int32_t* tri, float* normal, float* colour, float* points, tdgp_stream_t stream);
+int tdgp_mesh_shade(const float* normal, const int32_t* status, const float* ray_d, const float* colour, int64_t rays, int mode,
+                    const float* light, float ambient, const float* albedo, const float* background, float* rgb, tdgp_stream_t stream);
+
 /* Exact order statistics without a sort: the quantile behind the marchers' `cut_quantile` option (tri_plane_renderer.py:324-326, 366-368:
  * torch.quantile of the activated densities; the non-flatness score renders with 0.5, non_flatness_score.py:9-11).
  * out3[0] = sorted(x)[k_lo] and out3[1] = sorted(x)[k_hi], exact bits; out3[2] = torch.lerp(out3[0], out3[1], weight), i.e.

@@ -10,6 +10,8 @@ one strip per sample, its views side by side; .png (the strips stacked into one 
 (`--plane-batch` samples at a time), every frame is rendered from its sample's planes, and the frames become the uint8 grid on the device.
 `--vis shape_grid` / `--vis shape_strips`: the same two layouts of SHAPE frames -- the surface where the raw density reaches `--level`, found on
 the rays and shaded (`--shape-mode shaded | normals | colour`, `--num-refine`, `--ambient`, `--background`; `--depth` shows the hit depths).
+`--vis mesh_grid` / `--vis mesh_strips`: the same layouts of MESH frames -- the surface extracted once per sample (`--volume-res`, `--cube-size`,
+marching cubes at `--level`) and rasterised for every frame; `--mesh-normals face` shades the flat facets, `field` takes the normals from the field.
 """
 import argparse
 import importlib
@@ -72,7 +74,7 @@ def build_parser():
     p.add_argument('--pitch-start', type=float, default=np.pi / 2)
     p.add_argument('--pitch-end', type=float, default=np.pi / 2)
     p.add_argument('--posterior-camera', action='store_true', help='a posterior camera sample per seed instead of the mean camera')
-    p.add_argument('--vis', choices=['video_grid', 'image_grid', 'shape_grid', 'shape_strips'], default='video_grid')
+    p.add_argument('--vis', choices=['video_grid', 'image_grid', 'shape_grid', 'shape_strips', 'mesh_grid', 'mesh_strips'], default='video_grid')
     p.add_argument('--nrow', default='auto', help="'auto' or an integer (video_grid)")
     p.add_argument('--fps', type=float, default=25)
     p.add_argument('--depth', action='store_true', help='show the depth maps (normalised by the ray range) instead of the colours')
@@ -81,6 +83,9 @@ def build_parser():
     p.add_argument('--num-refine', type=int, default=16, help='shape frames: refinement depths inside the bracket of the first crossing (1..64)')
     p.add_argument('--ambient', type=float, default=0.2, help='shape frames: ambient share of the shade')
     p.add_argument('--background', type=float, default=1.0, help='shape frames: grey level of the rays that miss, in [-1, 1]')
+    p.add_argument('--volume-res', type=int, default=256, help='mesh frames: points per side of the density grid the mesh is extracted from')
+    p.add_argument('--cube-size', type=float, default=None, help='mesh frames: side of the cube the grid spans (default: the whole field, 2 * cube_scale)')
+    p.add_argument('--mesh-normals', choices=['face', 'field'], default='face', help='mesh frames: flat facet normals, or normals from the field at the hits')
     p.add_argument('--img-resolution', type=int, default=None, help='default: the checkpoint\'s')
     p.add_argument('--ray-step-multiplier', type=int, default=1)
     p.add_argument('--force-whiteback', action='store_true')
@@ -94,6 +99,12 @@ def build_parser():
 def shape_options(args):
     """The options of shapes.render_shape_views, from the command line."""
     return dict(level=args.level, mode=args.shape_mode, num_refine=args.num_refine, ambient=args.ambient, background=(args.background,) * 3)
+
+
+def mesh_options(args):
+    """The options of mesh.render_mesh_frames, from the command line."""
+    return dict(level=args.level, volume_res=args.volume_res, cube_size=args.cube_size, mode=args.shape_mode, normals=args.mesh_normals,
+                ambient=args.ambient, background=(args.background,) * 3, plane_batch=args.plane_batch)
 
 
 def main(argv=None):
@@ -121,8 +132,12 @@ def main(argv=None):
             block = I.render_video_grid(G, ws, cams, nrow=nrow, depth=args.depth, plane_batch=args.plane_batch, as_numpy=True)
         elif args.vis == 'shape_grid':
             block = tdgp.shapes.render_shape_video_grid(G, ws, cams, nrow=nrow, show=show, plane_batch=args.plane_batch, as_numpy=True, **shape_options(args))
+        elif args.vis == 'mesh_grid':
+            block, counts = tdgp.mesh.render_mesh_video_grid(G, ws, cams, nrow=nrow, show=show, as_numpy=True, return_counts=True, **mesh_options(args))
         else:
-            if args.vis == 'shape_strips':
+            if args.vis == 'mesh_strips':
+                block, counts = tdgp.mesh.render_mesh_strips(G, ws, cams, show=show, as_numpy=True, return_counts=True, **mesh_options(args))
+            elif args.vis == 'shape_strips':
                 block = tdgp.shapes.render_shape_strips(G, ws, cams, show=show, plane_batch=args.plane_batch, as_numpy=True, **shape_options(args))
             else:
                 block = I.render_image_strips(G, ws, cams, depth=args.depth, plane_batch=args.plane_batch, as_numpy=True)
@@ -134,6 +149,9 @@ def main(argv=None):
                 img_resolution=G.synthesis.test_resolution, ray_steps=G.cfg.num_ray_steps, depth=args.depth, seconds=seconds, ckpt=args.ckpt)
     if args.vis.startswith('shape_'):
         line.update(level=args.level, shape_mode=args.shape_mode, num_refine=args.num_refine)
+    if args.vis.startswith('mesh_'):
+        line.update(level=args.level, shape_mode=args.shape_mode, volume_res=args.volume_res, cube_size=args.cube_size, mesh_normals=args.mesh_normals,
+                    vertices=[v for v, _ in counts], triangles=[t for _, t in counts])
     print(json.dumps(line))
 
 
