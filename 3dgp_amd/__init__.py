@@ -22,6 +22,8 @@ The directory name starts with a digit, so import it with ``importlib.import_mod
   dataset              ImageFolderDataset, InfiniteSampler, threaded batch iterator (host code: numpy + PIL)
   training_loop        the training driver: ticks, snapshots, metrics, resume (tools/train.py is its command line)
   instance_selection   the dataset filter of the ImageNet recipe: Gaussian log-likelihood scores on the fp64 matrix pipe, top-k, folder copy
+  images               Pillow-exact anti-aliased resampling of uint8 images and 16-bit depth maps (device kernels + host path), detector input
+  data_tools           resize_dataset / merge_depth_data / extract_features: the offline data scripts of the ImageNet recipe
 """
 from . import config, weights  # noqa: F401  (numpy only)
 from .config import GeneratorConfig  # noqa: F401
@@ -29,7 +31,7 @@ from .config import GeneratorConfig  # noqa: F401
 
 def __getattr__(name):
     # torch-dependent submodules are imported on first use
-    if name in ('_lib', 'ops', 'renderer', 'generator', 'adaptors', 'metrics', 'inference', 'discriminator', 'training', 'compat', 'distributed', 'build', 'graphs', 'geometry', 'shapes', 'mesh', 'augment', 'step_tail', 'dataset', 'training_loop', 'instance_selection'):
+    if name in ('_lib', 'ops', 'renderer', 'generator', 'adaptors', 'metrics', 'inference', 'discriminator', 'training', 'compat', 'distributed', 'build', 'graphs', 'geometry', 'shapes', 'mesh', 'augment', 'step_tail', 'dataset', 'training_loop', 'instance_selection', 'images', 'data_tools'):
         import importlib
         return importlib.import_module(f'{__name__}.{name}')
     raise AttributeError(name)

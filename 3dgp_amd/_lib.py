@@ -102,6 +102,12 @@ _PROTOTYPES = {
     'tdgp_grads_sanitise_norm': (c_int, [P, c_int64, c_int, c_int, P, c_int64, P, P]),
     'tdgp_adam_step': (c_int, [P, P, c_int, c_int64, c_int, P, c_int64, P, c_double, c_double, c_double, c_double, P]),
     'tdgp_ema_update': (c_int, [P, c_int, c_int64, c_int, c_double, P]),
+    'tdgp_resample_workspace_bytes': (c_int64, [c_int64, c_int, c_int, c_int, c_int, c_int, c_int]),
+    'tdgp_resample_u8': (c_int, [P, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P, c_int, P, c_int, c_int, P, c_int64, P]),
+    'tdgp_resample_u16': (c_int, [P, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P, c_int, P, c_int, c_int, c_int, P, c_int64, P]),
+    'tdgp_resample_u8_to_f32_workspace_bytes': (c_int64, [c_int64, c_int, c_int, c_int, c_int, c_int, c_int]),
+    'tdgp_resample_u8_to_f32': (c_int, [P, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P, c_int, c_int, c_int, c_int,
+                                        c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), P, P, c_int64, P]),
 }
 EXPORTS = tuple(_PROTOTYPES)
 

@@ -758,6 +758,41 @@ int     tdgp_adam_step(const int64_t* table, const int64_t* step_table, int num_
                        int64_t total, const double* norm, double max_norm, double beta1, double beta2, double eps, tdgp_stream_t stream);
 int     tdgp_ema_update(const int64_t* table, int num_tensors, int64_t num_blocks, int chunk, double beta, tdgp_stream_t stream);
 
+/* Anti-aliased resampling with Pillow's arithmetic, csrc/resample.hip: the operation behind the reference's dataset scripts
+ * (scripts/utils.py:116-120 center_resize_crop; the bicubic eval transform of scripts/data_scripts/extract_features.py), which reach it
+ * through torchvision -> PIL.Image.resize.  All images of a call have one size and share one set of tables.
+ *   src [B, H, W, C] (C in {1, 3}; the 16-bit entry: [B, H, W]), channel-last, contiguous.  The crop window (x0, y0, w, h) on the source is
+ *   resampled to oh x ow, exactly as if it had been cropped first.
+ *   Tables (device), one pair per axis, built by the caller in float64 for (w -> ow) and (h -> oh): bounds int32 [out, 2] = (first source
+ *   index, number of taps), coeffs [out, ksize].  The pair of an axis whose size does not change must be NULL and that pass is not run;
+ *   with both NULL the call copies the window.  Entries are clamped to the source extent before use.
+ *   8 bit : int32 coefficients, round(w * 2^22) half away from zero; one output = clip((2^21 + sum pixel * k) >> 22, 0, 255) in int32.
+ *           The caller asserts 255 * sum|k| + 2^21 < 2^31 when it builds a table.
+ *   16 bit: float64 coefficients; ss = 0.0; ss += double(pixel) * k in tap order, every product and every sum rounded (nothing fused);
+ *           v = int(ss + 0.5) for ss >= 0, int(ss - 0.5) otherwise.  saturate = 0 stores Pillow's byte pair hi = clip(v >> 8, 0, 255),
+ *           lo = clip(v % 256, 0, 255) (C's %): 0 for v < 0 and 0xFF00 | (v & 255) for v > 65535; saturate = 1 stores 65535 for v > 65535.
+ *           The rows between the passes always hold Pillow's bytes, so the two modes differ only where the LAST pass overflows.
+ *   The horizontal pass runs first and rounds to the sample type; its rows [B, h, ow, C] are the only intermediate and live in `workspace`
+ *   (tdgp_resample_workspace_bytes: 0 unless both passes run; -1 for a refused shape; aligned to a sample).
+ * tdgp_resample_u8_to_f32: the same two passes, then the window (cx0, cy0, cw, ch) of the resized image, then
+ *   ((float(v) / 255.0f) - mean[c]) / std[c], each fp32 operation rounded on its own, both divisions true divisions; stored channel-first,
+ *   dst [B, C, ch, cw] fp32.  mean / std: C floats each on the HOST.  Only the kept columns pass through the workspace ([B, h, cw, C] bytes,
+ *   tdgp_resample_u8_to_f32_workspace_bytes); the resized image itself is never stored.
+ * Limits: every size <= 32768 per axis, B <= 65535 per call; any ksize (a tap loop).  Offsets are 64-bit.  Launches on `stream`; no
+ * atomics; only the output rows (and the workspace) are written; nothing is read back. */
+int64_t tdgp_resample_workspace_bytes(int64_t B, int h, int w, int oh, int ow, int C, int sample_bytes);
+int     tdgp_resample_u8(const uint8_t* src, int64_t B, int H, int W, int C, int x0, int y0, int w, int h, const int32_t* hbounds,
+                         const int32_t* hcoeffs, int hksize, const int32_t* vbounds, const int32_t* vcoeffs, int vksize, uint8_t* dst, int oh, int ow,
+                         void* workspace, int64_t workspace_bytes, tdgp_stream_t stream);
+int     tdgp_resample_u16(const uint16_t* src, int64_t B, int H, int W, int x0, int y0, int w, int h, const int32_t* hbounds, const double* hcoeffs,
+                          int hksize, const int32_t* vbounds, const double* vcoeffs, int vksize, uint16_t* dst, int oh, int ow, int saturate,
+                          void* workspace, int64_t workspace_bytes, tdgp_stream_t stream);
+int64_t tdgp_resample_u8_to_f32_workspace_bytes(int64_t B, int h, int w, int oh, int ow, int C, int cw);
+int     tdgp_resample_u8_to_f32(const uint8_t* src, int64_t B, int H, int W, int C, int x0, int y0, int w, int h, const int32_t* hbounds,
+                                const int32_t* hcoeffs, int hksize, const int32_t* vbounds, const int32_t* vcoeffs, int vksize, int oh, int ow, int cx0,
+                                int cy0, int cw, int ch, const float* mean, const float* std, float* dst, void* workspace, int64_t workspace_bytes,
+                                tdgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
