@@ -80,6 +80,16 @@ _PROTOTYPES = {
     'tdgp_mesh_visibility': (c_int, [P, c_int64, P, c_int64, P, P, P, c_int, c_int, c_int, c_float, c_int, P, P]),
     'tdgp_mesh_resolve': (c_int, [P, P, c_int64, P, c_int64, P, P, c_int64, c_float, c_float, P, P, P, P, P, P, P, P]),
     'tdgp_mesh_shade': (c_int, [P, P, P, P, c_int64, c_int, POINTER(c_float), c_float, POINTER(c_float), POINTER(c_float), P, P]),
+    'tdgp_mesh_labels_workspace_bytes': (c_int64, [c_int64, c_int64]),
+    'tdgp_mesh_labels': (c_int, [P, c_int64, c_int64, P, P, c_int64, P]),
+    'tdgp_mesh_component_ids_workspace_bytes': (c_int64, [c_int64]),
+    'tdgp_mesh_component_ids': (c_int, [P, c_int64, P, P, c_int64, P]),
+    'tdgp_mesh_component_stats': (c_int, [P, P, c_int64, c_int64, P, c_int64, P, P, P, P, P, P, P, P]),
+    'tdgp_mesh_component_sums': (c_int, [P, P, P, c_int64, c_int64, P, P, P, P, P]),
+    'tdgp_mesh_compact_workspace_bytes': (c_int64, [c_int64, c_int64]),
+    'tdgp_mesh_compact_count': (c_int, [P, c_int64, c_int64, P, P, c_int64, P, c_int64, P]),
+    'tdgp_mesh_compact_emit': (c_int, [P, P, c_int64, c_int64, P, P, c_int64, P, c_int64, P, c_int64, P, c_int64, P, POINTER(c_void_p), POINTER(c_void_p),
+                                       POINTER(c_int32), c_int, P]),
     'tdgp_quantile_select_workspace_bytes': (c_int64, [c_int64]),
     'tdgp_quantile_select': (c_int, [P, c_int64, c_int64, c_int64, c_float, P, P, c_int64, P]),
     'tdgp_depth_histc': (c_int, [P, c_int64, c_int64, c_float, c_float, c_int, P, P]),

@@ -163,13 +163,15 @@ def grid_to_world(vertices, volume_res, voxel_origin=(0.0, 0.0, 0.0), cube_size=
 
 @torch.no_grad()
 def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=0.3, thresh_value=25.0, crop='reference', normalize=True,
-                     slab_points=2 ** 22, noise_mode='const', units='index', sheared=True):
+                     slab_points=2 ** 22, noise_mode='const', units='index', sheared=True, components=None):
     """scripts/extract_geometry.py:26-42 per sample of `ws`: density grid -> crop -> marching cubes -> (optionally) scale.  Returns a list of
     Shape(vertices [V,3] fp32, triangles [T,3] int32, sigma [D,H,W] fp32 -- the cropped grid), all on the device.
     crop: 'reference' (extract_geometry.py:33), None, or three slices.  normalize: divide the vertices by the length of their bounding-box
     diagonal (`mesh.apply_scale(1.0 / mesh.scale)`, extract_geometry.py:42 -- trimesh's `scale`; no translation).
     units='world': the vertices go through `grid_to_world` with this call's volume_res / voxel_origin / cube_size / crop (and `sheared`)
-    instead of `normalize` -- the mesh `mesh.render_mesh_views` takes."""
+    instead of `normalize` -- the mesh `mesh.render_mesh_views` takes.
+    components: None (the raw level set), or a dict of `mesh_components.select` keyword arguments (e.g. dict(keep=1)): the marching-cubes
+    output goes through `mesh_components.clean_mesh` BEFORE it is scaled, so `normalize` divides by the diagonal of the cleaned mesh."""
     if units not in ('index', 'world'):
         raise ValueError(f"units must be 'index' or 'world', got {units!r}")
     crop = _crop_slices(crop, volume_res)
@@ -179,6 +181,9 @@ def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_s
         if crop is not None:
             sigma = sigma[crop]
         verts, tris = marching_cubes(sigma, thresh_value)
+        if components is not None:
+            from . import mesh_components as _mesh_components
+            verts, tris = _mesh_components.clean_mesh(verts, tris, **dict(components))[:2]
         if units == 'world':
             verts = grid_to_world(verts, volume_res, voxel_origin, cube_size, crop, sheared)
         elif normalize and verts.shape[0] > 0:

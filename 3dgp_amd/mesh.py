@@ -17,6 +17,7 @@ import torch
 from . import _lib
 from . import geometry as _geometry
 from . import inference as _inference
+from . import mesh_components as _mesh_components
 from . import renderer as _renderer
 from . import shapes as _shapes
 from .generator import TensorGroup
@@ -237,12 +238,14 @@ def _camera_slice(camera_params, device, c0, c1):
 
 @torch.no_grad()
 def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=None, crop=None, sheared=True,
-                       mode='shaded', normals='face', plane_batch=4, return_counts=False, **kw):
+                       mode='shaded', normals='face', plane_batch=4, return_counts=False, components=None, **kw):
     """Mesh frames of every `ws` under its cameras (sample-major: camera n * V + v is view v of sample n).  Per sample: `density_grid` at
     volume_res^3 over a cube of `cube_size` (default the whole field, 2 * cfg.cube_scale) -> `marching_cubes` at `level` -> `grid_to_world`,
     then its V cameras through `render_mesh_views`.  The backbone runs once per plane batch; its planes feed the density grid and, with
     normals='field' (or face normals in mode 'colour'), the field lookups of the frames.
     -> TensorGroup(rgb [B*V,R,3], depth, normal, status, tri) as `render_mesh_views`; return_counts=True: also [(vertices, triangles)] per sample.
+    components: None (the raw level set), or a dict of `mesh_components.select` keyword arguments (e.g. dict(keep=1)): every sample's mesh goes
+    through `mesh_components.clean_mesh` before it is drawn (floaters dropped on the device); the counts are those of the cleaned mesh.
     kw: cull, near, light, ambient, albedo, background, max_rays_per_call, t_miss, step of `render_mesh_views`."""
     syn, cfg = G.synthesis, G.cfg
     num_samples = len(ws)
@@ -268,6 +271,8 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
                 sigma = sigma[slices]
             verts, tris = _geometry.marching_cubes(sigma, level)
             del sigma
+            if components is not None:
+                verts, tris = _mesh_components.clean_mesh(verts, tris, **dict(components))[:2]
             verts = _geometry.grid_to_world(verts, volume_res, voxel_origin, cube_size, slices, sheared)
             counts.append((int(verts.shape[0]), int(tris.shape[0])))
             vc = vertex_colours(G, pb, verts) if (mode == 'colour' and normals == 'face') else None

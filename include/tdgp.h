@@ -600,6 +600,59 @@ int tdgp_mesh_resolve(const uint64_t* vis, const float* vertices, int64_t V, con
 int tdgp_mesh_shade(const float* normal, const int32_t* status, const float* ray_d, const float* colour, int64_t rays, int mode,
                     const float* light, float ambient, const float* albedo, const float* background, float* rgb, tdgp_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mesh components (csrc/mesh_components.hip; the reference's users split the mesh on the host with trimesh): connected components of the
+ * indexed mesh tdgp_mcubes_emit leaves on the device, per-component measurements, and an order-preserving filter.
+ *   tdgp_mesh_labels -> tdgp_mesh_component_ids -> tdgp_mesh_component_stats (+ a stable sort by the caller) -> tdgp_mesh_component_sums
+ *   -> (the caller chooses keep[K]) -> tdgp_mesh_compact_count -> tdgp_mesh_compact_emit
+ * Common: triangles [T,3] int32, 0 <= T, V <= 2^31 - 1; a triangle with an index outside [0, V) is skipped by every kernel and the index is
+ * never dereferenced.  Two vertices are connected when a triangle names both (triangles sharing ONE vertex are in one component); a vertex no
+ * triangle names is a component of its own; degenerate and duplicate triangles connect what they name.  Workspaces are caller-owned, 16-byte
+ * aligned, sized by the *_workspace_bytes queries (-1 for sizes they refuse); no kernel waits for another workgroup; integer outputs are
+ * pure functions of the inputs and every floating-point output is the same bytes on every run.
+ *
+ * tdgp_mesh_labels: label[v] = the smallest vertex index of v's component (int32 [V]).  A lock-free union-find over a parent array in the
+ *   workspace with parent[v] <= v at all times (the larger root is linked under the smaller by a compare-and-swap; a failed one is retried from
+ *   the value it returned, and the larger of the pair strictly decreases, so the retry is bounded); every access to the array in that pass is an
+ *   agent-scope relaxed atomic.  The first int64 of the workspace receives the number of failed compare-and-swaps of the call (a diagnostic).
+ * tdgp_mesh_component_ids: component[v] int32 = the dense id of v's component, 0 .. K-1 in the order of the components' smallest vertices;
+ *   K is left as one int64 at the START of the workspace, the one number the caller reads back.
+ * tdgp_mesh_component_stats: component [V], K -> tri_count int64 [K] (a triangle belongs to the component of its FIRST vertex), vert_count
+ *   int64 [K], bbox_min / bbox_max fp32 [K,3] (exact minima / maxima; -0 orders below +0), and per triangle t: tri_key int32 [T] (its component;
+ *   K for a skipped triangle) and the two terms, in double from the fp32 vertices a, b, c widened exactly, every operation rounded once:
+ *     u = b - a, w = c - a, n = (u1*w2 - u2*w1, u2*w0 - u0*w2, u0*w1 - u1*w0);  area_term = 0.5 * sqrt((n0*n0 + n1*n1) + n2*n2);
+ *     x = (b1*c2 - b2*c1, b2*c0 - b0*c2, b0*c1 - b1*c0);  vol_term = (a0*x0 + a1*x1) + a2*x2      (six times the signed volume of the tetrahedron
+ *     (0, a, b, c): the division by 6 is applied ONCE to the sum, so integer coordinates give exact volumes).
+ *   Counts and boxes use integer atomics (exact, order-independent); nothing is summed in floating point here.
+ * tdgp_mesh_component_sums: order int64 [T] = the triangle indices sorted by tri_key with the triangle order kept inside a key (a stable
+ *   sort), start int64 [K] = the exclusive prefix sum of tri_count -> area [K], volume [K] in double.  THE SUMMATION ORDER, per component with
+ *   its n triangles t_0 < t_1 < ... < t_{n-1}: lane l of 256 adds the terms of t_l, t_{l+256}, t_{l+512}, ... in that order onto 0.0; then for
+ *   d = 128, 64, ..., 1 lane l < d adds lane l + d's partial onto its own; area = lane 0's, volume = lane 0's / 6.
+ * tdgp_mesh_compact_count: keep uint8 [K] -> V' = vertices whose component is kept, T' = triangles all three of whose corners are kept, as two
+ *   int64 at the START of the workspace (the one pair read back).  tdgp_mesh_compact_emit (same inputs and workspace): the kept vertices
+ *   in their original order [V',3], the kept triangles in their original order re-indexed [T',3], vertex_map int32 [V] (new index or -1), and
+ *   for each of num_attr fp32 arrays [V, attr_channels[i]] its kept rows [V', attr_channels[i]].  attr_in / attr_out / attr_channels are HOST
+ *   arrays (of device pointers / of ints).  Positions come from scans alone; writes never pass the V' / T' given.
+ * --------------------------------------------------------------------------------------------- */
+int64_t tdgp_mesh_labels_workspace_bytes(int64_t T, int64_t V);
+int     tdgp_mesh_labels(const int32_t* triangles, int64_t T, int64_t V, int32_t* label, void* workspace, int64_t workspace_bytes,
+                         tdgp_stream_t stream);
+int64_t tdgp_mesh_component_ids_workspace_bytes(int64_t V);
+int     tdgp_mesh_component_ids(const int32_t* label, int64_t V, int32_t* component, void* workspace, int64_t workspace_bytes,
+                                tdgp_stream_t stream);
+int     tdgp_mesh_component_stats(const float* vertices, const int32_t* triangles, int64_t T, int64_t V, const int32_t* component, int64_t K,
+                                  int64_t* tri_count, int64_t* vert_count, float* bbox_min, float* bbox_max, int32_t* tri_key,
+                                  double* area_term, double* vol_term, tdgp_stream_t stream);
+int     tdgp_mesh_component_sums(const int64_t* order, const int64_t* start, const int64_t* tri_count, int64_t K, int64_t T,
+                                 const double* area_term, const double* vol_term, double* area, double* volume, tdgp_stream_t stream);
+int64_t tdgp_mesh_compact_workspace_bytes(int64_t T, int64_t V);
+int     tdgp_mesh_compact_count(const int32_t* triangles, int64_t T, int64_t V, const int32_t* component, const uint8_t* keep, int64_t K,
+                                void* workspace, int64_t workspace_bytes, tdgp_stream_t stream);
+int     tdgp_mesh_compact_emit(const float* vertices, const int32_t* triangles, int64_t T, int64_t V, const int32_t* component,
+                               const uint8_t* keep, int64_t K, void* workspace, int64_t workspace_bytes, float* out_vertices, int64_t V_out,
+                               int32_t* out_triangles, int64_t T_out, int32_t* vertex_map, const void* const* attr_in, void* const* attr_out,
+                               const int32_t* attr_channels, int num_attr, tdgp_stream_t stream);
+
 /* Exact order statistics without a sort: the quantile behind the marchers' `cut_quantile` option (tri_plane_renderer.py:324-326, 366-368:
  * torch.quantile of the activated densities; the non-flatness score renders with 0.5, non_flatness_score.py:9-11).
  * out3[0] = sorted(x)[k_lo] and out3[1] = sorted(x)[k_hi], exact bits; out3[2] = torch.lerp(out3[0], out3[1], weight), i.e.

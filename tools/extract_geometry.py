@@ -48,7 +48,30 @@ def build_parser():
     _flag(p, 'save-obj', False, 'write the mesh as Wavefront .obj')
     _flag(p, 'save-ply', False, 'write the mesh as binary .ply')
     p.add_argument('--ckpt', default=None, metavar='DIR', help='directory written by tools/export_reference_checkpoint.py')
+    # the component filter is this project's own: its flags are absent from the namespace unless given (argparse.SUPPRESS), so the parsed
+    # defaults stay exactly the keys of the reference's extract_geometry.yaml; component_options() reads them
+    p.add_argument('--keep-components', type=parse_keep, default=argparse.SUPPRESS, metavar='K',
+                   help="keep only the K largest connected components of the mesh ('all': no limit; default: the raw level set, floaters included)")
+    p.add_argument('--component-by', choices=['triangles', 'area'], default=argparse.SUPPRESS, help='what "largest" measures (default: triangles)')
+    p.add_argument('--min-component-triangles', type=int, default=argparse.SUPPRESS, metavar='N', help='drop components with fewer than N triangles')
     return p
+
+
+def parse_keep(s):
+    if s == 'all':
+        return s
+    k = int(s)
+    if k < 1:
+        raise argparse.ArgumentTypeError(f'--keep-components takes a positive integer or "all", got {s!r}')
+    return k
+
+
+def component_options(args):
+    """The `components` argument of geometry.extract_geometry / mesh.render_mesh_frames from the command line: None unless a flag asks for the filter."""
+    keep, least = getattr(args, 'keep_components', None), getattr(args, 'min_component_triangles', None)
+    if keep is None and least is None:
+        return None
+    return dict(keep='all' if keep is None else keep, by=getattr(args, 'component_by', 'triangles'), min_triangles=least or 0)
 
 
 def parse_args(argv=None):
@@ -84,10 +107,11 @@ def main(argv=None):
     names = sample_names(seeds, args.classes)
     os.makedirs(args.output_dir, exist_ok=True)
     need_mesh = args.save_obj or args.save_ply
+    comp = component_options(args)
     for name, w in zip(names, ws.split(1, dim=0)):
         if need_mesh:
             shape = geometry.extract_geometry(G, w, volume_res=args.volume_res, voxel_origin=args.voxel_origin, cube_size=args.cube_size,
-                                              thresh_value=args.thresh_value, crop='reference', normalize=True)[0]
+                                              thresh_value=args.thresh_value, crop='reference', normalize=True, components=comp)[0]
             sigma = shape.sigma
             if args.save_obj:
                 geometry.save_obj(os.path.join(args.output_dir, f'{name}.obj'), shape.vertices, shape.triangles)
@@ -95,6 +119,14 @@ def main(argv=None):
                 geometry.save_ply(os.path.join(args.output_dir, f'{name}.ply'), shape.vertices, shape.triangles)
             if args.verbose:
                 print(f'{name}: {shape.vertices.shape[0]} vertices, {shape.triangles.shape[0]} triangles')
+                if comp is not None:
+                    # the report measures the raw level set of the grid the shape was cut from (one more marching-cubes pass, verbose runs only)
+                    raw_v, raw_t = geometry.marching_cubes(sigma, args.thresh_value)
+                    if raw_v.shape[0]:
+                        found = tdgp.mesh_components.components(raw_v, raw_t)
+                        kept = int(tdgp.mesh_components.select(found, **comp).sum())
+                        print(f'{name}: {found.triangles.shape[0]} components found, {kept} kept, '
+                              f'{raw_t.shape[0] - shape.triangles.shape[0]} triangles dropped')
         else:
             sigma = geometry.density_grid(G, w, args.volume_res, args.voxel_origin, args.cube_size)[0][geometry.crop_reference(args.volume_res)]
             if args.verbose:

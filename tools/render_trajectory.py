@@ -86,6 +86,10 @@ def build_parser():
     p.add_argument('--volume-res', type=int, default=256, help='mesh frames: points per side of the density grid the mesh is extracted from')
     p.add_argument('--cube-size', type=float, default=None, help='mesh frames: side of the cube the grid spans (default: the whole field, 2 * cube_scale)')
     p.add_argument('--mesh-normals', choices=['face', 'field'], default='face', help='mesh frames: flat facet normals, or normals from the field at the hits')
+    p.add_argument('--keep-components', type=parse_keep, default=None, metavar='K',
+                   help="mesh frames: draw only the K largest connected components of each mesh ('all': no limit; default: the raw level set)")
+    p.add_argument('--component-by', choices=['triangles', 'area'], default='triangles', help='mesh frames: what "largest" measures')
+    p.add_argument('--min-component-triangles', type=int, default=None, metavar='N', help='mesh frames: drop components with fewer than N triangles')
     p.add_argument('--img-resolution', type=int, default=None, help='default: the checkpoint\'s')
     p.add_argument('--ray-step-multiplier', type=int, default=1)
     p.add_argument('--force-whiteback', action='store_true')
@@ -96,6 +100,23 @@ def build_parser():
     return p
 
 
+def parse_keep(s):
+    if s == 'all':
+        return s
+    k = int(s)
+    if k < 1:
+        raise argparse.ArgumentTypeError(f'--keep-components takes a positive integer or "all", got {s!r}')
+    return k
+
+
+def component_options(args):
+    """The `components` argument of mesh.render_mesh_frames from the command line: None unless a flag asks for the filter."""
+    if args.keep_components is None and args.min_component_triangles is None:
+        return None
+    return dict(keep='all' if args.keep_components is None else args.keep_components, by=args.component_by,
+                min_triangles=args.min_component_triangles or 0)
+
+
 def shape_options(args):
     """The options of shapes.render_shape_views, from the command line."""
     return dict(level=args.level, mode=args.shape_mode, num_refine=args.num_refine, ambient=args.ambient, background=(args.background,) * 3)
@@ -104,7 +125,7 @@ def shape_options(args):
 def mesh_options(args):
     """The options of mesh.render_mesh_frames, from the command line."""
     return dict(level=args.level, volume_res=args.volume_res, cube_size=args.cube_size, mode=args.shape_mode, normals=args.mesh_normals,
-                ambient=args.ambient, background=(args.background,) * 3, plane_batch=args.plane_batch)
+                ambient=args.ambient, background=(args.background,) * 3, plane_batch=args.plane_batch, components=component_options(args))
 
 
 def main(argv=None):
@@ -151,7 +172,7 @@ def main(argv=None):
         line.update(level=args.level, shape_mode=args.shape_mode, num_refine=args.num_refine)
     if args.vis.startswith('mesh_'):
         line.update(level=args.level, shape_mode=args.shape_mode, volume_res=args.volume_res, cube_size=args.cube_size, mesh_normals=args.mesh_normals,
-                    vertices=[v for v, _ in counts], triangles=[t for _, t in counts])
+                    vertices=[v for v, _ in counts], triangles=[t for _, t in counts], components=component_options(args))
     print(json.dumps(line))
 
 
