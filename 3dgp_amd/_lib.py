@@ -179,6 +179,16 @@ def call(name, *args):
         raise (Unsupported if rc == -2 else RuntimeError)(f'{name} failed ({rc}): {msg.decode() if msg else "?"}')
 
 
+def byte_workspace(query_name, dims, device, refusal, at_least=0):
+    """Ask `query_name(*dims)` how many workspace bytes a call needs -> (uint8 tensor of max(need, at_least) bytes on `device`, need).
+    A negative answer is the library refusing the sizes: `refusal` (the caller's exception, so every entry point keeps its own type and
+    words) is raised before anything is allocated."""
+    need = int(getattr(load(), query_name)(*dims))
+    if need < 0:
+        raise refusal
+    return torch.empty([max(need, at_least)], dtype=torch.uint8, device=device), need
+
+
 def require_cuda(t, what):
     if not (isinstance(t, torch.Tensor) and t.is_cuda):
         raise RuntimeError(f'{what} must reside on the GPU (got {getattr(t, "device", type(t))}); the HIP ops have no CPU path')

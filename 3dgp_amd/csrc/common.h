@@ -141,6 +141,17 @@ __device__ __forceinline__ double wave_last_f64(double v) {
 __device__ __forceinline__ double wave_shr1_f64(double v, double first) { return dpp_f64<0x138, 0xf>(first, v); }
 __device__ __forceinline__ double wave_sum_f64(double v) { return wave_last_f64(wave_scan_f64<false>(v)); }
 
+// fp64 MFMA (v_mfma_f64_16x16x4_f64): a wave's 32 x 32 output as 2 x 2 tiles of 16 x 16, 32 accumulator registers.  Per K step of 4 a lane
+// (lc = lane & 15, lk = lane >> 4) gives fa[a] = A[row a*16 + lc][k lk] and fb[b] = B[k lk][column b*16 + lc].  Accumulator element e of
+// tile (a, b) is row a*16 + lk + 4 e, column b*16 + lc of the wave's output.
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void mfma_f64_2x2(const double (&fa)[2], const double (&fb)[2], f64x4 (&acc)[2][2]) {
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int b = 0; b < 2; b++) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a], fb[b], acc[a][b], 0, 0, 0);
+}
+
 // torch's thresholded softplus (beta 1, threshold 20), evaluated in fp64 and rounded once.
 __device__ __forceinline__ float softplus20(float x) { return x > 20.f ? x : (float)log1p(exp((double)x)); }
 

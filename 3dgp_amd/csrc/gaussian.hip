@@ -34,8 +34,6 @@ constexpr int GM_DIRECT_TILES = 512;                 // this many row tiles fill
 constexpr int GM_MAX_F = 16384;
 constexpr int64_t GM_MAX_N = (int64_t)1 << 31;
 
-typedef double gm_f64x4 __attribute__((ext_vector_type(4)));
-
 struct GmPlan { int t1; int64_t row_tiles; bool split; };
 
 inline bool gm_shape_ok(int64_t n, int F) { return n >= 0 && n < GM_MAX_N && F >= 1 && F <= GM_MAX_F; }
@@ -92,7 +90,7 @@ __device__ __forceinline__ double gm_tile(GmShared& sh, const float* __restrict_
         if (t < GM_C) sh.mu[buf][t] = rm;
     };
 
-    gm_f64x4 acc[2][2];
+    f64x4 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; a++)
 #pragma unroll
@@ -120,16 +118,13 @@ __device__ __forceinline__ double gm_tile(GmShared& sh, const float* __restrict_
                 fa[s] = (double)A[(wi * 32 + s * 16 + lc) * GM_LDA + kq] - m;
                 fb[s] = B[kq * GM_LDB + wj * 32 + s * 16 + lc];
             }
-#pragma unroll
-            for (int a = 0; a < 2; a++)
-#pragma unroll
-                for (int b = 0; b < 2; b++) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a], fb[b], acc[a][b], 0, 0, 0);
+            mfma_f64_2x2(fa, fb, acc);
         }
         if (more) put(cur ^ 1);
         __syncthreads();
     }
 
-    // accumulator element e of MFMA tile (a, b): row i0 + wi*32 + a*16 + lk + 4 e, column j0 + wj*32 + b*16 + lc
+    // the wave's output starts at row i0 + wi*32, column j0 + wj*32 (element map: common.h)
 #pragma unroll
     for (int a = 0; a < 2; a++)
 #pragma unroll

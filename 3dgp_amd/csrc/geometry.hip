@@ -15,6 +15,7 @@
 // Positions in the outputs are decided by the scans alone (no atomics): vertices ordered by owning grid point then axis (d, h, w),
 // triangles by cell then table order, bit-identical from run to run.  Winding: normals point toward lower values (mc_table.inc).
 #include "common.h"
+#include "device_scan.h"
 #define MC_TABLE_QUAL __device__ const __attribute__((aligned(16)))
 #include "mc_table.inc"
 
@@ -40,29 +41,6 @@ __global__ __launch_bounds__(256) void voxel_coords_kernel(float* __restrict__ o
         out[k * 3 + 1] = y * vs + oy;
         out[k * 3 + 2] = z * vs + oz;
     }
-}
-
-__device__ __forceinline__ int wave_incl_scan_i32(int v) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(v, d, 64);
-        if (lane_id() >= d) v += o;
-    }
-    return v;
-}
-
-// exclusive prefix of `v` over the block's 256 threads (thread order); `total` = the block's sum.  `sm` holds 4 ints.
-__device__ __forceinline__ int block_excl_scan(int v, int* sm, int& total) {
-    const int incl = wave_incl_scan_i32(v);
-    const int wv = threadIdx.x >> 6;
-    __syncthreads();                               // `sm` may still be read from an earlier scan
-    if (lane_id() == 63) sm[wv] = incl;
-    __syncthreads();
-    int base = 0;
-#pragma unroll
-    for (int i = 0; i < MC_BLOCK / 64; i++) base += (i < wv) ? sm[i] : 0;
-    total = sm[0] + sm[1] + sm[2] + sm[3];
-    return base + incl - v;
 }
 
 // code of a grid point: bits 0-7 the case of its cell (0 where it has none), bits 8-10 its owned sign-changing edges along d / h / w
@@ -96,38 +74,17 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_count_kernel(const float* __restr
         nt = ntri_s[cs];
     }
     int tv, tt;
-    block_excl_scan(nv, sm, tv);
-    block_excl_scan(nt, sm, tt);
+    block_excl_scan<MC_BLOCK>(nv, sm, tv);
+    block_excl_scan<MC_BLOCK>(nt, sm, tt);
     if (threadIdx.x == 0) {
         block_sums[2 * (int64_t)blockIdx.x + 0] = (uint32_t)tv;
         block_sums[2 * (int64_t)blockIdx.x + 1] = (uint32_t)tt;
     }
 }
 
-// one block of 1024 threads: thread t takes the contiguous run [t * per, (t + 1) * per) of block sums
+// one block of 1024 threads over the (vertex, triangle) sums of every block: totals[0] = V, totals[1] = T
 __global__ __launch_bounds__(1024) void mc_scan_kernel(uint32_t* __restrict__ block_sums, int64_t nb, int64_t* __restrict__ totals) {
-    __shared__ unsigned long long part[2][1024];
-    const int t = threadIdx.x;
-    const int64_t per = (nb + 1023) / 1024;
-    const int64_t b0 = min((int64_t)t * per, nb), b1 = min(b0 + per, nb);
-    unsigned long long sv = 0, st = 0;
-    for (int64_t b = b0; b < b1; b++) { sv += block_sums[2 * b]; st += block_sums[2 * b + 1]; }
-    part[0][t] = sv; part[1][t] = st;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {           // Hillis-Steele over the 1024 partial sums
-        unsigned long long av = 0, at = 0;
-        if (t >= d) { av = part[0][t - d]; at = part[1][t - d]; }
-        __syncthreads();
-        part[0][t] += av; part[1][t] += at;
-        __syncthreads();
-    }
-    unsigned long long ev = part[0][t] - sv, et = part[1][t] - st;
-    for (int64_t b = b0; b < b1; b++) {
-        const uint32_t cv = block_sums[2 * b], ct = block_sums[2 * b + 1];
-        block_sums[2 * b] = (uint32_t)ev; block_sums[2 * b + 1] = (uint32_t)et;      // exact whenever the totals pass tdgp_mcubes_emit's bounds
-        ev += cv; et += ct;
-    }
-    if (t == 1023) { totals[0] = (int64_t)part[0][1023]; totals[1] = (int64_t)part[1][1023]; }
+    scan_block_sums<2>(block_sums, nb, totals);
 }
 
 __global__ __launch_bounds__(MC_BLOCK) void mc_emit_verts_kernel(const float* __restrict__ vol, int D, int H, int W, float thresh,
@@ -137,7 +94,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_emit_verts_kernel(const float* __
     const int64_t i = blockIdx.x * (int64_t)MC_BLOCK + threadIdx.x;
     const int flags = i < N ? (code[i] >> 8) & 7 : 0;
     int total;
-    const int64_t first = (int64_t)block_offs[2 * (int64_t)blockIdx.x] + block_excl_scan(popc3(flags), sm, total);
+    const int64_t first = (int64_t)block_offs[2 * (int64_t)blockIdx.x] + block_excl_scan<MC_BLOCK>(popc3(flags), sm, total);
     if (i >= N) return;
     // rank of the h edge = (d edge present), rank of the w edge = (d edge) + (h edge)
     vid[i] = ((uint32_t)first << 3) | (uint32_t)(flags & 1) | ((uint32_t)((flags & 1) + ((flags >> 1) & 1)) << 1);
@@ -175,7 +132,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_emit_tris_kernel(int H, int W, co
     const int cs = i < N ? code[i] & 255 : 0;
     const int nt = tab_s[cs][0];
     int total;
-    int64_t tid = (int64_t)block_offs[2 * (int64_t)blockIdx.x + 1] + block_excl_scan(nt, sm, total);
+    int64_t tid = (int64_t)block_offs[2 * (int64_t)blockIdx.x + 1] + block_excl_scan<MC_BLOCK>(nt, sm, total);
     if (!nt) return;                                // a non-zero case only exists where the whole cell does
     const int64_t HW = (int64_t)H * W;
     for (int k = 0; k < nt; k++, tid++) {
@@ -201,7 +158,6 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_emit_tris_kernel(int H, int W, co
 struct McLayout {
     int64_t N, nb, off_sums, off_code, off_vid, bytes;
 };
-inline int64_t align64(int64_t x) { return (x + 63) & ~(int64_t)63; }
 inline McLayout mc_layout(int D, int H, int W) {
     McLayout L;
     L.N = (int64_t)D * H * W;

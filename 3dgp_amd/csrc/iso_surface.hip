@@ -7,6 +7,7 @@
 // atomics, no workspace: the same bytes on every run, and a numpy float32 restatement reproduces them bit for bit (tests/shapes_reference.py).
 // Memory-light kernels kept plain: no LDS, the first crossing comes from a ballot over the ray's lane group.
 #include "common.h"
+#include "shade.h"
 
 namespace {
 
@@ -95,11 +96,6 @@ __global__ __launch_bounds__(256) void iso_locate_kernel(const float* __restrict
     }
 }
 
-struct ShadeParams {
-    int mode, has_light;
-    float light[3], ambient, albedo[3], background[3];
-};
-
 __global__ __launch_bounds__(256) void iso_shade_kernel(const float* __restrict__ stencil, const int32_t* __restrict__ status, const float* __restrict__ ray_d,
                                                         int64_t rays, ShadeParams q, float* __restrict__ rgb, float* __restrict__ normal) {
     const int64_t ray = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -117,8 +113,7 @@ __global__ __launch_bounds__(256) void iso_shade_kernel(const float* __restrict_
     } else {
         const float g[3] = {sg[1] - sg[2], sg[3] - sg[4], sg[5] - sg[6]};
         const float gq = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
-        const float dn = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-        float l[3];
+        const float dn = ray_norm(d);
         if (gq > 0.0f && gq < __builtin_inff()) {
             const float r = sqrtf(gq);
 #pragma unroll
@@ -127,25 +122,8 @@ __global__ __launch_bounds__(256) void iso_shade_kernel(const float* __restrict_
 #pragma unroll
             for (int c = 0; c < 3; c++) n[c] = (-d[c]) / dn;
         }
-#pragma unroll
-        for (int c = 0; c < 3; c++) l[c] = q.has_light ? q.light[c] : (-d[c]) / dn;
-        float cs = (n[0] * l[0] + n[1] * l[1]) + n[2] * l[2];
-        if (!(cs > 0.0f)) cs = 0.0f;
-        const float v = q.ambient + (1.0f - q.ambient) * cs;
         const float col[3] = {row[0], row[1], row[2]};
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            if (q.mode == 0) {
-                out[c] = (q.albedo[c] * v) * 2.0f - 1.0f;
-            } else if (q.mode == 1) {
-                out[c] = n[c];
-            } else {
-                float k = col[c] * 0.5f + 0.5f;
-                k = !(k > 0.0f) ? 0.0f : k;                             // min(max(k, 0), 1) with a NaN taken to 0
-                k = k > 1.0f ? 1.0f : k;
-                out[c] = (k * v) * 2.0f - 1.0f;
-            }
-        }
+        shade_hit(q, n, d, [&](int c) { return col[c] * 0.5f + 0.5f; }, out);
     }
 #pragma unroll
     for (int c = 0; c < 3; c++) rgb[ray * 3 + c] = out[c];
@@ -201,9 +179,7 @@ TDGP_API int tdgp_iso_shade(const float* stencil, const int32_t* status, const f
     TDGP_CHECK(rays >= 0 && rays <= ISO_RAYS_MAX, TDGP_EINVAL, "iso_shade: bad shape");
     TDGP_CHECK(mode >= 0 && mode <= 2, TDGP_EINVAL, "iso_shade: mode must be 0 (shaded), 1 (normals) or 2 (colour), got %d", mode);
     if (rays == 0) return TDGP_OK;
-    ShadeParams q;
-    q.mode = mode; q.has_light = light ? 1 : 0; q.ambient = ambient;
-    for (int c = 0; c < 3; c++) { q.light[c] = light ? light[c] : 0.0f; q.albedo[c] = albedo[c]; q.background[c] = background[c]; }
+    const ShadeParams q = shade_params(mode, light, ambient, albedo, background);
     TDGP_LAUNCH("iso_shade_kernel", iso_shade_kernel, dim3((unsigned)cdiv64(rays, 256)), dim3(256), 0, (hipStream_t)stream, stencil, status, ray_d,
                 rays, q, rgb, normal);
     TDGP_LAUNCH_CHECK();

@@ -11,10 +11,11 @@
 //                       retry is the CAS retry (a failure means another lane's link succeeded); no lane waits for another workgroup
 //   cc_flatten_kernel   (after the kernel boundary: plain loads) label[v] = root of v
 // Dense ids and the filter: positions decided by scans alone -- a block-local scan of 256 flags, ONE block scanning the block sums, block-local
-// scan + block offset -- exactly the pattern of marching cubes (geometry.hip), so every output is the same bytes on every run.
+// scan + block offset (device_scan.h, shared with marching cubes), so every output is the same bytes on every run.
 // Stats: counts and boxes by integer / ordered-bit atomics (exact, order-independent); the fp64 sums in the store-then-sum form: per-triangle
 // terms stored once, summed per component in the fixed order tdgp.h states.  No float atomics anywhere.
 #include "common.h"
+#include "device_scan.h"
 
 namespace {
 
@@ -23,61 +24,15 @@ constexpr int64_t CC_WS_HEAD = 64;            // bytes in front of the block sum
 constexpr int STATS_ITEMS = 8;               // consecutive 256-element rows a block of the stats kernels takes
 constexpr int SUM_BLOCK = 256;                // lanes of the per-component summation (its order is part of the contract)
 
-inline int64_t align64(int64_t x) { return (x + 63) & ~(int64_t)63; }
-
-__device__ __forceinline__ int wave_incl_scan_i32(int v) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(v, d, 64);
-        if (lane_id() >= d) v += o;
-    }
-    return v;
-}
-
 __device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += (unsigned)__shfl_xor((int)v, d, 64);
     return v;
 }
 
-// exclusive prefix of `v` over the block's 256 threads (thread order); `total` = the block's sum.  `sm` holds 4 ints.
-__device__ __forceinline__ int block_excl_scan(int v, int* sm, int& total) {
-    const int incl = wave_incl_scan_i32(v);
-    const int wv = threadIdx.x >> 6;
-    __syncthreads();                               // `sm` may still be read from an earlier scan
-    if (lane_id() == 63) sm[wv] = incl;
-    __syncthreads();
-    int base = 0;
-#pragma unroll
-    for (int i = 0; i < CC_BLOCK / 64; i++) base += (i < wv) ? sm[i] : 0;
-    total = sm[0] + sm[1] + sm[2] + sm[3];
-    return base + incl - v;
-}
-
-// one block of 1024 threads: exclusive scan of nb block sums in place, the grand total to *total (the pattern of mc_scan_kernel)
+// one block of 1024 threads: exclusive scan of nb block sums in place, the grand total to *total (every total here is at most V or T < 2^31)
 __global__ __launch_bounds__(1024) void cc_scan_kernel(uint32_t* __restrict__ block_sums, int64_t nb, int64_t* __restrict__ total) {
-    __shared__ unsigned long long part[1024];
-    const int t = threadIdx.x;
-    const int64_t per = (nb + 1023) / 1024;
-    const int64_t b0 = min((int64_t)t * per, nb), b1 = min(b0 + per, nb);
-    unsigned long long s = 0;
-    for (int64_t b = b0; b < b1; b++) s += block_sums[b];
-    part[t] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {           // Hillis-Steele over the 1024 partial sums
-        unsigned long long a = 0;
-        if (t >= d) a = part[t - d];
-        __syncthreads();
-        part[t] += a;
-        __syncthreads();
-    }
-    unsigned long long e = part[t] - s;
-    for (int64_t b = b0; b < b1; b++) {
-        const uint32_t c = block_sums[b];
-        block_sums[b] = (uint32_t)e;               // exact: every total here is at most V or T < 2^31
-        e += c;
-    }
-    if (t == 1023) *total = (int64_t)part[1023];
+    scan_block_sums<1>(block_sums, nb, total);
 }
 
 // ---- labels ------------------------------------------------------------------------------------------------------------------------------
@@ -157,7 +112,7 @@ __global__ __launch_bounds__(CC_BLOCK) void ids_count_kernel(const int32_t* __re
     __shared__ int sm[4];
     const int64_t v = blockIdx.x * (int64_t)CC_BLOCK + threadIdx.x;
     int total;
-    block_excl_scan(v < V && label[v] == (int)v ? 1 : 0, sm, total);
+    block_excl_scan<CC_BLOCK>(v < V && label[v] == (int)v ? 1 : 0, sm, total);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = (uint32_t)total;
 }
 
@@ -167,7 +122,7 @@ __global__ __launch_bounds__(CC_BLOCK) void ids_roots_kernel(const int32_t* __re
     const int64_t v = blockIdx.x * (int64_t)CC_BLOCK + threadIdx.x;
     const bool root = v < V && label[v] == (int)v;
     int total;
-    const int rank = (int)block_offs[blockIdx.x] + block_excl_scan(root ? 1 : 0, sm, total);
+    const int rank = (int)block_offs[blockIdx.x] + block_excl_scan<CC_BLOCK>(root ? 1 : 0, sm, total);
     if (root) component[v] = rank;
 }
 
@@ -180,13 +135,6 @@ __global__ __launch_bounds__(CC_BLOCK) void ids_spread_kernel(const int32_t* __r
 }
 
 // ---- stats -------------------------------------------------------------------------------------------------------------------------------
-// floats as unsigned keys whose integer order is the floats' order (-0 below +0)
-__device__ __forceinline__ uint32_t f32_key(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_f32(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
 __global__ __launch_bounds__(CC_BLOCK) void stats_init_kernel(int64_t K, unsigned long long* __restrict__ tri_count, unsigned long long* __restrict__ vert_count,
                                                               uint32_t* __restrict__ box_min, uint32_t* __restrict__ box_max) {
     const int64_t k = blockIdx.x * (int64_t)CC_BLOCK + threadIdx.x;
@@ -378,7 +326,7 @@ __global__ __launch_bounds__(CC_BLOCK) void compact_count_verts_kernel(const int
     __shared__ int sm[4];
     const int64_t v = blockIdx.x * (int64_t)CC_BLOCK + threadIdx.x;
     int total;
-    block_excl_scan(v < V && vert_kept(component, keep, v, K) ? 1 : 0, sm, total);
+    block_excl_scan<CC_BLOCK>(v < V && vert_kept(component, keep, v, K) ? 1 : 0, sm, total);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = (uint32_t)total;
 }
 
@@ -387,7 +335,7 @@ __global__ __launch_bounds__(CC_BLOCK) void compact_count_tris_kernel(const int3
     __shared__ int sm[4];
     const int64_t t = blockIdx.x * (int64_t)CC_BLOCK + threadIdx.x;
     int total;
-    block_excl_scan(t < T && tri_kept(tris, component, keep, t, V, K) ? 1 : 0, sm, total);
+    block_excl_scan<CC_BLOCK>(t < T && tri_kept(tris, component, keep, t, V, K) ? 1 : 0, sm, total);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = (uint32_t)total;
 }
 
@@ -398,7 +346,7 @@ __global__ __launch_bounds__(CC_BLOCK) void compact_emit_verts_kernel(const floa
     const int64_t v = blockIdx.x * (int64_t)CC_BLOCK + threadIdx.x;
     const bool kept = v < V && vert_kept(component, keep, v, K);
     int total;
-    const int64_t pos = (int64_t)block_offs[blockIdx.x] + block_excl_scan(kept ? 1 : 0, sm, total);
+    const int64_t pos = (int64_t)block_offs[blockIdx.x] + block_excl_scan<CC_BLOCK>(kept ? 1 : 0, sm, total);
     if (v >= V) return;
     const bool fits = kept && pos < Vout;          // Vout is the caller's: never write past the buffer it sized
     vertex_map[v] = fits ? (int32_t)pos : -1;
@@ -417,7 +365,7 @@ __global__ __launch_bounds__(CC_BLOCK) void compact_emit_tris_kernel(const int32
     const int64_t t = blockIdx.x * (int64_t)CC_BLOCK + threadIdx.x;
     const bool kept = t < T && tri_kept(tris, component, keep, t, V, K);
     int total;
-    const int64_t pos = (int64_t)block_offs[blockIdx.x] + block_excl_scan(kept ? 1 : 0, sm, total);
+    const int64_t pos = (int64_t)block_offs[blockIdx.x] + block_excl_scan<CC_BLOCK>(kept ? 1 : 0, sm, total);
     if (!kept || pos >= Tout) return;
 #pragma unroll
     for (int c = 0; c < 3; c++) out_tris[pos * 3 + c] = vertex_map[tris[t * 3 + c]];

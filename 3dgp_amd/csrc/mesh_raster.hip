@@ -8,6 +8,7 @@
 // only atomic is an unsigned 64-bit minimum, whose result does not depend on the order of its operands: the same bytes on every run and under
 // every permutation of the triangles.  A numpy restatement reproduces all three bit for bit (tests/mesh_raster_reference.py).
 #include "common.h"
+#include "shade.h"
 
 namespace {
 
@@ -217,12 +218,9 @@ __global__ __launch_bounds__(256) void mesh_resolve_kernel(const unsigned long l
     }
 }
 
-struct MeshShadeParams {
-    int mode, has_light;
-    float light[3], ambient, albedo[3], background[3];
-};
+// ShadeParams under the name the kernel's symbol has carried since the first mesh frames
+struct MeshShadeParams : ShadeParams {};
 
-// tdgp_iso_shade's arithmetic from the normal on (csrc/iso_surface.hip), restated: the normal and the colour are inputs here.
 __global__ __launch_bounds__(256) void mesh_shade_kernel(const float* __restrict__ normal, const int32_t* __restrict__ status, const float* __restrict__ ray_d,
                                                          const float* __restrict__ colour, int64_t rays, MeshShadeParams q, float* __restrict__ rgb) {
     const int64_t ray = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -234,26 +232,8 @@ __global__ __launch_bounds__(256) void mesh_shade_kernel(const float* __restrict
     } else {
         const float d[3] = {ray_d[ray * 3 + 0], ray_d[ray * 3 + 1], ray_d[ray * 3 + 2]};
         const float n[3] = {normal[ray * 3 + 0], normal[ray * 3 + 1], normal[ray * 3 + 2]};
-        const float dn = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-        float l[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) l[c] = q.has_light ? q.light[c] : (-d[c]) / dn;
-        float cs = (n[0] * l[0] + n[1] * l[1]) + n[2] * l[2];
-        if (!(cs > 0.0f)) cs = 0.0f;
-        const float v = q.ambient + (1.0f - q.ambient) * cs;
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            if (q.mode == 0) {
-                out[c] = (q.albedo[c] * v) * 2.0f - 1.0f;
-            } else if (q.mode == 1) {
-                out[c] = n[c];
-            } else {
-                float k = colour[ray * 3 + c];                          // already in [0, 1] (mesh.vertex_colours); the clamp takes a NaN to 0
-                k = !(k > 0.0f) ? 0.0f : k;
-                k = k > 1.0f ? 1.0f : k;
-                out[c] = (k * v) * 2.0f - 1.0f;
-            }
-        }
+        // the colour is already in [0, 1] (mesh.vertex_colours); it may be null outside mode 2
+        shade_hit(q, n, d, [&](int c) { return colour[ray * 3 + c]; }, out);
     }
 #pragma unroll
     for (int c = 0; c < 3; c++) rgb[ray * 3 + c] = out[c];
@@ -308,9 +288,7 @@ TDGP_API int tdgp_mesh_shade(const float* normal, const int32_t* status, const f
     TDGP_CHECK(mode >= 0 && mode <= 2, TDGP_EINVAL, "mesh_shade: mode must be 0 (shaded), 1 (normals) or 2 (colour), got %d", mode);
     TDGP_CHECK(mode != 2 || colour, TDGP_EINVAL, "mesh_shade: mode 2 (colour) needs the colour tdgp_mesh_resolve wrote");
     if (rays == 0) return TDGP_OK;
-    MeshShadeParams q;
-    q.mode = mode; q.has_light = light ? 1 : 0; q.ambient = ambient;
-    for (int c = 0; c < 3; c++) { q.light[c] = light ? light[c] : 0.0f; q.albedo[c] = albedo[c]; q.background[c] = background[c]; }
+    const MeshShadeParams q{shade_params(mode, light, ambient, albedo, background)};
     TDGP_LAUNCH("mesh_shade_kernel", mesh_shade_kernel, dim3((unsigned)cdiv64(rays, 256)), dim3(256), 0, (hipStream_t)stream, normal, status, ray_d, colour, rays, q, rgb);
     TDGP_LAUNCH_CHECK();
     return TDGP_OK;

@@ -18,6 +18,7 @@
 // hist_add() therefore peels up to two groups of equal bins off a wave with ballots (one add of the group's size by its first lane) before
 // the remaining lanes add individually -- the dominant bin is hit by the first peel with the probability of its own share.
 #include "common.h"
+#include "device_scan.h"
 #include <math.h>
 
 namespace {
@@ -33,14 +34,13 @@ constexpr uint32_t QS_NAN_KEY = 0xffffffffu;        // the key of a NaN bit patt
 __host__ __device__ constexpr int qs_shift(int P) { return P == 0 ? 21 : (P == 1 ? 10 : 0); }
 __host__ __device__ constexpr int qs_bits(int P) { return P == 2 ? 10 : 11; }
 
-// order-preserving key: negatives bit-flipped, non-negatives with the sign bit set; -0.0 keyed as +0.0, every NaN as QS_NAN_KEY
+// the order-preserving f32_key (device_scan.h) with -0.0 keyed as +0.0 and every NaN as QS_NAN_KEY; key_f32 is its inverse
 __device__ __forceinline__ uint32_t qs_key(float v) {
     uint32_t u = __float_as_uint(v);
     if (u == 0x80000000u) u = 0u;
-    const uint32_t k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    const uint32_t k = f32_bits_key(u);
     return v != v ? QS_NAN_KEY : k;
 }
-__device__ __forceinline__ float qs_value(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 // h[bin] += 1 for every lane with `valid`; to be reached by the whole wave (the ballots are taken over it)
 __device__ __forceinline__ void hist_add(uint32_t* h, bool valid, uint32_t bin) {
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(QS_BLOCK) void qs_pick_kernel(uint32_t* __restrict_
     if (P == QS_PASSES - 1) {
         __syncthreads();                                            // the two writers' stores, block scope
         if (t == 0) {
-            const float a = qs_value(ws[0]), b = qs_value(ws[1]);
+            const float a = key_f32(ws[0]), b = key_f32(ws[1]);
             const bool nan = ws[4] != 0u;
             const float qn = __uint_as_float(0x7fc00000u);
             out3[0] = nan ? qn : a;
@@ -655,8 +655,6 @@ constexpr int MOM_TLD = MOM_T + 1;                   // doubles per row of the e
 constexpr int MOM_LDS_BYTES = 2 * 2 * MOM_C * MOM_LD * 4;
 static_assert(MOM_LDS_BYTES >= MOM_T * MOM_TLD * 8, "the epilogue tile reuses the staging buffers");
 
-typedef double mom_f64x4 __attribute__((ext_vector_type(4)));
-
 struct MomPlan { int t1; int64_t tiles; int64_t run_rows; int64_t runs; };
 
 inline MomPlan mom_plan(int64_t n, int F) {
@@ -733,7 +731,7 @@ __global__ __launch_bounds__(MOM_THREADS) void mom_tile_kernel(const float* __re
         }
     };
 
-    mom_f64x4 acc[2][2];
+    f64x4 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; a++)
 #pragma unroll
@@ -761,10 +759,7 @@ __global__ __launch_bounds__(MOM_THREADS) void mom_tile_kernel(const float* __re
                     fa[s] = (double)A[kr + wi * 32 + s * 16 + lc];
                     fb[s] = (double)B[kr + wj * 32 + s * 16 + lc];
                 }
-#pragma unroll
-                for (int a = 0; a < 2; a++)
-#pragma unroll
-                    for (int b = 0; b < 2; b++) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a], fb[b], acc[a][b], 0, 0, 0);
+                mfma_f64_2x2(fa, fb, acc);
             }
         }
         if (diag) {
@@ -786,7 +781,7 @@ __global__ __launch_bounds__(MOM_THREADS) void mom_tile_kernel(const float* __re
         }
     }
 
-    // accumulator element e of MFMA tile (a, b): row (feature f) f0 + wi*32 + a*16 + lk + 4 e, column (feature g) g0 + wj*32 + b*16 + lc
+    // the wave's output starts at row (feature f) f0 + wi*32, column (feature g) g0 + wj*32 (element map: common.h)
     if (DIRECT) {
         double* const tile = reinterpret_cast<double*>(lds_raw);                // the K loop's last barrier is behind every read of `stage`
         if (work) {

@@ -104,10 +104,8 @@ def marching_cubes(volume, thresh):
     empty = lambda: (torch.empty([0, 3], dtype=torch.float32, device=dev), torch.empty([0, 3], dtype=torch.int32, device=dev))   # noqa: E731
     if min(D, H, W) < 2:
         return empty()
-    need = int(_lib.load().tdgp_mcubes_workspace_bytes(D, H, W))
-    if need < 0:
-        raise _lib.Unsupported(f'marching_cubes: a volume of {D}x{H}x{W} points exceeds the 2^31 - 1 this build indexes; extract it in parts')
-    ws = torch.empty([need], dtype=torch.uint8, device=dev)
+    ws, need = _lib.byte_workspace('tdgp_mcubes_workspace_bytes', (D, H, W), dev, _lib.Unsupported(
+        f'marching_cubes: a volume of {D}x{H}x{W} points exceeds the 2^31 - 1 this build indexes; extract it in parts'))
     with torch.cuda.device(dev):
         stream = _lib.stream_of(vol)
         _lib.call('tdgp_mcubes_count', vol.data_ptr(), D, H, W, float(thresh), ws.data_ptr(), need, stream)

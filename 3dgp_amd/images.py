@@ -218,10 +218,9 @@ def _resize_device(x, bits, box, oh, ow, filter, saturate, out):
     C = int(x.shape[3]) if bits == 8 else 1
     hb, hk, hks = _axis_tables(w, ow, filter, bits, x.device)
     vb, vk, vks = _axis_tables(h, oh, filter, bits, x.device)
-    need = int(_lib.load().tdgp_resample_workspace_bytes(B, h, w, oh, ow, C, bits // 8))
-    if need < 0:
-        raise RuntimeError(f'tdgp_resample refuses {B} x {h} x {w} -> {oh} x {ow}')
-    ws = torch.empty([need], dtype=torch.uint8, device=x.device) if need else None                  # bytes; torch's allocations are aligned far beyond a sample
+    ws, need = _lib.byte_workspace('tdgp_resample_workspace_bytes', (B, h, w, oh, ow, C, bits // 8), x.device,
+                                   RuntimeError(f'tdgp_resample refuses {B} x {h} x {w} -> {oh} x {ow}'))
+    ws = ws if need else None                                          # bytes; torch's allocations are aligned far beyond a sample
     with torch.cuda.device(x.device):
         if bits == 8:
             _lib.call('tdgp_resample_u8', x.data_ptr(), B, H, W, C, x0, y0, w, h, _lib.ptr(hb), _lib.ptr(hk), hks, _lib.ptr(vb), _lib.ptr(vk), vks,
@@ -366,10 +365,9 @@ def detector_input(x_u8, resize=256, crop=224, filter='bicubic', mean=DETECTOR_M
         x = x_u8.contiguous()
         hb, hk, hks = _axis_tables(W, ow, filter, 8, x.device)
         vb, vk, vks = _axis_tables(H, oh, filter, 8, x.device)
-        need = int(_lib.load().tdgp_resample_u8_to_f32_workspace_bytes(B, H, W, oh, ow, C, crop))
-        if need < 0:
-            raise RuntimeError(f'tdgp_resample_u8_to_f32 refuses {B} x {H} x {W} -> {oh} x {ow}')
-        ws = torch.empty([need], dtype=torch.uint8, device=x.device) if need else None
+        ws, need = _lib.byte_workspace('tdgp_resample_u8_to_f32_workspace_bytes', (B, H, W, oh, ow, C, crop), x.device,
+                                       RuntimeError(f'tdgp_resample_u8_to_f32 refuses {B} x {H} x {W} -> {oh} x {ow}'))
+        ws = ws if need else None
         res = torch.empty([B, C, crop, crop], dtype=torch.float32, device=x.device)
         fl = ctypes.c_float * C
         with torch.cuda.device(x.device):

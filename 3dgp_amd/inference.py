@@ -261,33 +261,51 @@ def _depth_normalisation(G):
     return ((G.cfg.ray_start + G.cfg.ray_end) * 0.5, G.cfg.ray_end - G.cfg.ray_start)
 
 
+def shown(show, make_all):
+    """The buffer `show` names ('rgb' | 'depth') of the frames make_all() renders (a TensorGroup with both); `show` is checked first."""
+    if show not in ('rgb', 'depth'):
+        raise ValueError(f"show must be 'rgb' or 'depth', got {show!r}")
+    frames = make_all()
+    return frames.depth if show == 'depth' else frames.rgb
+
+
+def video_grid_of(G, num_samples, V, make_frames, nrow, num_videos, padding, depth, as_numpy):
+    """The tail of every video grid (pixels, shape frames, mesh frames): frame t is the make_grid of every sample's view t.  make_frames()
+    renders the ray-major frames [num_samples * V, R, C], sample-major; it is called only after `grid_shape` has accepted the layout, so a bad
+    nrow / padding is refused before anything is rendered.  depth: the frames are depths, shown normalised by the ray range."""
+    if nrow == 'auto':
+        nrow = int(np.ceil(min(num_samples if num_videos is None else num_videos, num_samples) ** 0.5))
+    res = G.synthesis.test_resolution
+    grid_shape(res, res, num_samples, nrow, padding)
+    out = frames_to_grid(make_frames(), res, res, tiles=num_samples, images=V, stride_image=1, stride_tile=V, nrow=nrow, padding=padding,
+                         normalise=_depth_normalisation(G) if depth else None)
+    return _to_host(out) if as_numpy else out
+
+
+def strips_of(G, num_samples, V, make_frames, depth, as_numpy):
+    """The tail of every set of image strips: per sample, its V views side by side (make_frames, depth: as `video_grid_of`)."""
+    res = G.synthesis.test_resolution
+    out = frames_to_grid(make_frames(), res, res, tiles=V, images=num_samples, stride_image=V, stride_tile=1, nrow=V, padding=0,
+                         normalise=_depth_normalisation(G) if depth else None)
+    return _to_host(out) if as_numpy else out
+
+
 def render_video_grid(G, ws, camera_params, nrow='auto', depth=False, plane_batch=4, num_videos=None, padding=2, as_numpy=False, **kwargs):
     """scripts/inference.py:68-75 (`video_grid`) on the device: frame t of the video is the make_grid of every sample's view t ->
     uint8 [T, GH, GW, 3] (a device tensor; as_numpy=True: one copy to the host).  Shared planes, ray-major buffers, `frames_to_grid`.
     nrow='auto' = ceil(sqrt(min(num_videos, num_samples))) as the reference script sets it (num_videos: its num_videos_per_grid, default all
     samples).  depth=True shows the depth maps, normalised by the ray range.  kwargs: render_opts, u_coarse, u_fine, max_rays_per_call, block kwargs."""
     num_samples = len(ws)
-    V = len(camera_params) // max(num_samples, 1)
-    if nrow == 'auto':
-        nrow = int(np.ceil(min(num_samples if num_videos is None else num_videos, num_samples) ** 0.5))
-    res = G.synthesis.test_resolution
-    grid_shape(res, res, num_samples, nrow, padding)
-    frames = _ray_major_frames(G, ws, camera_params, depth, plane_batch, **kwargs)
-    out = frames_to_grid(frames, res, res, tiles=num_samples, images=V, stride_image=1, stride_tile=V, nrow=nrow, padding=padding,
-                         normalise=_depth_normalisation(G) if depth else None)
-    return _to_host(out) if as_numpy else out
+    return video_grid_of(G, num_samples, len(camera_params) // max(num_samples, 1),
+                         lambda: _ray_major_frames(G, ws, camera_params, depth, plane_batch, **kwargs), nrow, num_videos, padding, depth, as_numpy)
 
 
 def render_image_strips(G, ws, camera_params, depth=False, plane_batch=4, as_numpy=False, **kwargs):
     """scripts/inference.py:63-66 (`image_grid`): per sample, its views side by side (`torch.cat(list(images), dim=3)`) ->
     uint8 [num_samples, h, V * w, 3] on the device."""
     num_samples = len(ws)
-    V = len(camera_params) // max(num_samples, 1)
-    res = G.synthesis.test_resolution
-    frames = _ray_major_frames(G, ws, camera_params, depth, plane_batch, **kwargs)
-    out = frames_to_grid(frames, res, res, tiles=V, images=num_samples, stride_image=V, stride_tile=1, nrow=V, padding=0,
-                         normalise=_depth_normalisation(G) if depth else None)
-    return _to_host(out) if as_numpy else out
+    return strips_of(G, num_samples, len(camera_params) // max(num_samples, 1),
+                     lambda: _ray_major_frames(G, ws, camera_params, depth, plane_batch, **kwargs), depth, as_numpy)
 
 
 def _to_host(out):

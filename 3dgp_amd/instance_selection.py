@@ -43,10 +43,8 @@ def _maha_device(rows, mu, P):
     out = torch.empty([n], dtype=torch.float64, device=rows.device)
     if n == 0:
         return out
-    need = int(_lib.load().tdgp_gaussian_maha_workspace_bytes(n, width))
-    if need < 0:
-        raise RuntimeError(f'tdgp_gaussian_maha refuses {n} rows of {width} features')
-    ws = torch.empty([need], dtype=torch.uint8, device=rows.device)
+    ws, need = _lib.byte_workspace('tdgp_gaussian_maha_workspace_bytes', (n, width), rows.device,
+                                   RuntimeError(f'tdgp_gaussian_maha refuses {n} rows of {width} features'))
     with torch.cuda.device(rows.device):
         _lib.call('tdgp_gaussian_maha', rows.data_ptr(), n, width, mu.data_ptr(), P.data_ptr(), out.data_ptr(), ws.data_ptr(), need, _lib.stream_of(rows))
     return out

@@ -283,39 +283,27 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
     return (frames, counts) if return_counts else frames
 
 
-def _shown(frames, show):
-    if show not in ('rgb', 'depth'):
-        raise ValueError(f"show must be 'rgb' or 'depth', got {show!r}")
-    return frames.depth if show == 'depth' else frames.rgb
+def _shown_mesh_frames(G, ws, camera_params, show, counts, **kw):
+    """-> a callable for the grid tails: the `show` buffer of `render_mesh_frames`; the per-sample counts are left in the list `counts`."""
+    def all_frames():
+        frames, counts[:] = render_mesh_frames(G, ws, camera_params, return_counts=True, **kw)
+        return frames
+    return lambda: _inference.shown(show, all_frames)
 
 
 def render_mesh_video_grid(G, ws, camera_params, nrow='auto', show='rgb', num_videos=None, padding=2, as_numpy=False, return_counts=False, **kw):
     """`shapes.render_shape_video_grid` of mesh frames: frame t of the video is the make_grid of every sample's mesh view t -> uint8
     [T, GH, GW, 3] on the device (as_numpy=True: one copy to the host).  kw: the options of `render_mesh_frames`."""
-    if show not in ('rgb', 'depth'):
-        raise ValueError(f"show must be 'rgb' or 'depth', got {show!r}")
-    num_samples = len(ws)
+    num_samples, counts = len(ws), []
     V = int(_renderer.cam_get(camera_params)('angles').shape[0]) // max(num_samples, 1)
-    if nrow == 'auto':
-        nrow = int(np.ceil(min(num_samples if num_videos is None else num_videos, num_samples) ** 0.5))
-    res = G.synthesis.test_resolution
-    _inference.grid_shape(res, res, num_samples, nrow, padding)
-    frames, counts = render_mesh_frames(G, ws, camera_params, return_counts=True, **kw)
-    out = _inference.frames_to_grid(_shown(frames, show), res, res, tiles=num_samples, images=V, stride_image=1, stride_tile=V, nrow=nrow, padding=padding,
-                                    normalise=_inference._depth_normalisation(G) if show == 'depth' else None)
-    out = _inference._to_host(out) if as_numpy else out
+    out = _inference.video_grid_of(G, num_samples, V, _shown_mesh_frames(G, ws, camera_params, show, counts, **kw), nrow, num_videos, padding,
+                                   show == 'depth', as_numpy)
     return (out, counts) if return_counts else out
 
 
 def render_mesh_strips(G, ws, camera_params, show='rgb', as_numpy=False, return_counts=False, **kw):
     """`shapes.render_shape_strips` of mesh frames: per sample, its mesh views side by side -> uint8 [num_samples, h, V * w, 3] on the device."""
-    if show not in ('rgb', 'depth'):
-        raise ValueError(f"show must be 'rgb' or 'depth', got {show!r}")
-    num_samples = len(ws)
+    num_samples, counts = len(ws), []
     V = int(_renderer.cam_get(camera_params)('angles').shape[0]) // max(num_samples, 1)
-    res = G.synthesis.test_resolution
-    frames, counts = render_mesh_frames(G, ws, camera_params, return_counts=True, **kw)
-    out = _inference.frames_to_grid(_shown(frames, show), res, res, tiles=V, images=num_samples, stride_image=V, stride_tile=1, nrow=V, padding=0,
-                                    normalise=_inference._depth_normalisation(G) if show == 'depth' else None)
-    out = _inference._to_host(out) if as_numpy else out
+    out = _inference.strips_of(G, num_samples, V, _shown_mesh_frames(G, ws, camera_params, show, counts, **kw), show == 'depth', as_numpy)
     return (out, counts) if return_counts else out

@@ -61,10 +61,7 @@ def _check_mesh(vertices, triangles):
 
 
 def _workspace(query, *sizes, device):
-    need = int(getattr(_lib.load(), query)(*sizes))
-    if need < 0:
-        raise ValueError(f'{query}{sizes}: sizes outside [0, 2^31 - 1]')
-    return torch.empty([need], dtype=torch.uint8, device=device), need
+    return _lib.byte_workspace(query, sizes, device, ValueError(f'{query}{sizes}: sizes outside [0, 2^31 - 1]'))
 
 
 def _labels(triangles, V, return_retries=False):

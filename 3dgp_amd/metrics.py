@@ -131,10 +131,8 @@ def _moments_add(rows, s1, s2):
     n, width = int(rows.shape[0]), int(rows.shape[1])
     if n == 0:
         return
-    need = int(_lib.load().tdgp_moments_workspace_bytes(n, width))
-    if need < 0:
-        raise RuntimeError(f'tdgp_moments_add refuses {n} rows of {width} features')
-    ws = torch.empty([need], dtype=torch.uint8, device=rows.device)
+    ws, need = _lib.byte_workspace('tdgp_moments_workspace_bytes', (n, width), rows.device,
+                                   RuntimeError(f'tdgp_moments_add refuses {n} rows of {width} features'))
     with torch.cuda.device(rows.device):
         _lib.call('tdgp_moments_add', rows.data_ptr(), n, width, s1.data_ptr(), s2.data_ptr(), ws.data_ptr(), need, _lib.stream_of(rows))
 
@@ -545,10 +543,8 @@ def _pr_kth(manifold, k1):
     from . import _lib
     h = manifold.half
     kth = torch.empty([manifold.n], dtype=torch.float16, device=h.device)
-    need = int(_lib.load().tdgp_pr_kth_workspace_bytes(manifold.n, manifold.n, k1))
-    if need < 0:
-        raise RuntimeError(f'tdgp_pr_kth refuses {manifold.n} rows with k + 1 = {k1}')
-    ws = torch.empty([need], dtype=torch.uint8, device=h.device)
+    ws, need = _lib.byte_workspace('tdgp_pr_kth_workspace_bytes', (manifold.n, manifold.n, k1), h.device,
+                                   RuntimeError(f'tdgp_pr_kth refuses {manifold.n} rows with k + 1 = {k1}'))
     with torch.cuda.device(h.device):
         _lib.call('tdgp_pr_kth', h.data_ptr(), manifold.norms.data_ptr(), manifold.n, h.data_ptr(), manifold.norms.data_ptr(), manifold.n, h.shape[1], k1,
                   kth.data_ptr(), ws.data_ptr(), need, _lib.stream_of(h))
@@ -559,10 +555,8 @@ def _pr_member(probes, manifold, kth):
     from . import _lib
     h = probes.half
     member = torch.empty([probes.n], dtype=torch.uint8, device=h.device)
-    need = int(_lib.load().tdgp_pr_member_workspace_bytes(probes.n, manifold.n))
-    if need < 0:
-        raise RuntimeError(f'tdgp_pr_member refuses {probes.n} probes x {manifold.n} manifold rows')
-    ws = torch.empty([need], dtype=torch.uint8, device=h.device)
+    ws, need = _lib.byte_workspace('tdgp_pr_member_workspace_bytes', (probes.n, manifold.n), h.device,
+                                   RuntimeError(f'tdgp_pr_member refuses {probes.n} probes x {manifold.n} manifold rows'))
     with torch.cuda.device(h.device):
         _lib.call('tdgp_pr_member', h.data_ptr(), probes.norms.data_ptr(), probes.n, manifold.half.data_ptr(), manifold.norms.data_ptr(), kth.data_ptr(),
                   manifold.n, h.shape[1], member.data_ptr(), ws.data_ptr(), need, _lib.stream_of(h))
@@ -896,10 +890,8 @@ def pair_sqdist(feats, inv_scale, out=None):
     feats = _lib.f32c(feats)
     if n == 0:
         return out
-    need = int(_lib.load().tdgp_pair_sqdist_workspace_bytes(n, width))
-    if need < 0:
-        raise _lib.Unsupported(f'tdgp_pair_sqdist refuses {n} pairs of {width} features')
-    ws = torch.empty([max(need, 16)], dtype=torch.uint8, device=feats.device)
+    ws, need = _lib.byte_workspace('tdgp_pair_sqdist_workspace_bytes', (n, width), feats.device,
+                                   _lib.Unsupported(f'tdgp_pair_sqdist refuses {n} pairs of {width} features'), at_least=16)
     with torch.cuda.device(feats.device):
         _lib.call('tdgp_pair_sqdist', feats.data_ptr(), n, width, float(inv_scale), out.data_ptr(), ws.data_ptr(), need, _lib.stream_of(feats))
     return out

@@ -12,7 +12,6 @@ under every chunking of the rays.  GPU only: the kernels have no CPU path.
 """
 import ctypes
 
-import numpy as np
 import torch
 
 from . import _lib
@@ -244,34 +243,17 @@ def render_shapes(G, ws, camera_params, plane_batch=4, return_all=False, **kw):
                        status=frames.status.reshape(BV, h, w))
 
 
-def _shown_frames(G, ws, camera_params, show, plane_batch, **kw):
-    if show not in ('rgb', 'depth'):
-        raise ValueError(f"show must be 'rgb' or 'depth', got {show!r}")
-    frames = _all_frames(G, ws, camera_params, plane_batch, **kw)
-    return frames.depth if show == 'depth' else frames.rgb
-
-
 def render_shape_video_grid(G, ws, camera_params, nrow='auto', show='rgb', plane_batch=4, num_videos=None, padding=2, as_numpy=False, **kw):
     """`inference.render_video_grid` of shape frames: frame t of the video is the make_grid of every sample's shape view t -> uint8
     [T, GH, GW, 3] on the device (as_numpy=True: one copy to the host).  show='depth': the hit depths, normalised by the ray range."""
     num_samples = len(ws)
-    V = len(camera_params) // max(num_samples, 1)
-    if nrow == 'auto':
-        nrow = int(np.ceil(min(num_samples if num_videos is None else num_videos, num_samples) ** 0.5))
-    res = G.synthesis.test_resolution
-    _inference.grid_shape(res, res, num_samples, nrow, padding)
-    frames = _shown_frames(G, ws, camera_params, show, plane_batch, **kw)
-    out = _inference.frames_to_grid(frames, res, res, tiles=num_samples, images=V, stride_image=1, stride_tile=V, nrow=nrow, padding=padding,
-                                    normalise=_inference._depth_normalisation(G) if show == 'depth' else None)
-    return _inference._to_host(out) if as_numpy else out
+    return _inference.video_grid_of(G, num_samples, len(camera_params) // max(num_samples, 1),
+                                    lambda: _inference.shown(show, lambda: _all_frames(G, ws, camera_params, plane_batch, **kw)),
+                                    nrow, num_videos, padding, show == 'depth', as_numpy)
 
 
 def render_shape_strips(G, ws, camera_params, show='rgb', plane_batch=4, as_numpy=False, **kw):
     """`inference.render_image_strips` of shape frames: per sample, its shape views side by side -> uint8 [num_samples, h, V * w, 3] on the device."""
     num_samples = len(ws)
-    V = len(camera_params) // max(num_samples, 1)
-    res = G.synthesis.test_resolution
-    frames = _shown_frames(G, ws, camera_params, show, plane_batch, **kw)
-    out = _inference.frames_to_grid(frames, res, res, tiles=V, images=num_samples, stride_image=V, stride_tile=1, nrow=V, padding=0,
-                                    normalise=_inference._depth_normalisation(G) if show == 'depth' else None)
-    return _inference._to_host(out) if as_numpy else out
+    return _inference.strips_of(G, num_samples, len(camera_params) // max(num_samples, 1),
+                                lambda: _inference.shown(show, lambda: _all_frames(G, ws, camera_params, plane_batch, **kw)), show == 'depth', as_numpy)

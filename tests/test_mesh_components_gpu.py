@@ -273,6 +273,37 @@ def test_compaction_at_block_edges(tdgp):
             check_compaction(tdgp, verts, tris, rs.rand(K) < 0.6, [rs.rand(V, 2).astype(F)], f'V={V} T={nt}')
 
 
+def test_more_than_1024_blocks_of_vertices(tdgp):
+    """The one-block scan of the block sums takes runs of 2 sums per thread from 1025 blocks on: a strip of 257 triangles on 1024 * 256 + 257
+    vertices is 1026 blocks of vertices, nearly all of them singletons.  Every expectation is written down directly."""
+    M = tdgp.mesh_components
+    nt, V = 257, 1024 * 256 + 257
+    assert -(-V // 256) == 1026
+    tris, _ = CR.strip(nt, V=V)
+    v = np.arange(V, dtype=np.int32)
+    same_bytes(device_labels(tdgp, tris, V), np.where(v < nt + 2, 0, v).astype(np.int32), 'labels')
+    verts = np.random.RandomState(11).randn(V, 3).astype(F)
+    attr = np.random.RandomState(12).rand(V, 2).astype(F)
+    tv, tt = T(verts), T(tris)
+    comps = M.components(tv, tt)
+    K = V - (nt + 1)
+    want_ids = np.where(v < nt + 2, 0, v - (nt + 1)).astype(np.int32)
+    same_bytes(H(comps.component), want_ids, 'dense ids')
+    assert tuple(comps.triangles.shape) == (K,) and int(comps.triangles[0]) == nt and int(comps.vertices[0]) == nt + 2
+    for first in (0, 1):                                        # the strip's component kept with every other singleton, then dropped
+        mask = (np.arange(K) % 2 == first)
+        kept = mask[want_ids]
+        vmap = np.where(kept, np.cumsum(kept) - 1, -1).astype(np.int32)
+        want_t = vmap[tris] if mask[0] else np.zeros((0, 3), np.int32)
+        got_v, got_t, (got_a,), got_map = M.keep_components(tv, tt, comps, T(mask), attributes=(T(attr),))
+        what = f'mask {first}::2'
+        assert (got_v.shape[0], got_t.shape[0]) == (int(kept.sum()), len(want_t)), what
+        same_bytes(H(got_map), vmap, 'vertex_map ' + what)
+        same_bytes(H(got_v).view(np.uint32), verts[kept].view(np.uint32), 'vertices ' + what)
+        same_bytes(H(got_a).view(np.uint32), attr[kept].view(np.uint32), 'attribute ' + what)
+        same_bytes(H(got_t), want_t, 'triangles ' + what)
+
+
 def test_clean_mesh_keeps_the_larger_sphere_and_passes_empty_meshes(tdgp, mc_mesh):
     M = tdgp.mesh_components
     verts, tris = mc_mesh
