@@ -90,6 +90,12 @@ _PROTOTYPES = {
     'tdgp_mesh_compact_count': (c_int, [P, c_int64, c_int64, P, P, c_int64, P, c_int64, P]),
     'tdgp_mesh_compact_emit': (c_int, [P, P, c_int64, c_int64, P, P, c_int64, P, c_int64, P, c_int64, P, c_int64, P, POINTER(c_void_p), POINTER(c_void_p),
                                        POINTER(c_int32), c_int, P]),
+    'tdgp_mesh_corner_table_workspace_bytes': (c_int64, [c_int64, c_int64]),
+    'tdgp_mesh_corner_table': (c_int, [P, c_int64, c_int64, P, P, P, P, c_int64, P]),
+    'tdgp_mesh_vertex_normals': (c_int, [P, P, c_int64, c_int64, P, P, c_int, P, P]),
+    'tdgp_mesh_boundary_vertices': (c_int, [P, c_int64, c_int64, P, P, P, P]),
+    'tdgp_mesh_smooth_step': (c_int, [P, P, c_int64, c_int64, P, P, c_double, P, P, P]),
+    'tdgp_mesh_interp_normals': (c_int, [P, P, P, P, P, c_int64, P, c_int64, P, c_int64, P, P, P]),
     'tdgp_quantile_select_workspace_bytes': (c_int64, [c_int64]),
     'tdgp_quantile_select': (c_int, [P, c_int64, c_int64, c_int64, c_float, P, P, c_int64, P]),
     'tdgp_depth_histc': (c_int, [P, c_int64, c_int64, c_float, c_float, c_int, P, P]),

@@ -9,6 +9,7 @@
 // every permutation of the triangles.  A numpy restatement reproduces all three bit for bit (tests/mesh_raster_reference.py).
 #include "common.h"
 #include "shade.h"
+#include "mesh_bary.h"
 
 namespace {
 
@@ -182,22 +183,13 @@ __global__ __launch_bounds__(256) void mesh_resolve_kernel(const unsigned long l
             for (int c = 0; c < 3; c++) n[c] = (-d[c]) / dn;
         }
         if (colour) {
-            const double e[3] = {(double)x[0] - v0[0], (double)x[1] - v0[1], (double)x[2] - v0[2]};
-            const double d11 = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2], d12 = (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
-            const double d22 = (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2];
-            const double e1 = (e[0] * a[0] + e[1] * a[1]) + e[2] * a[2], e2 = (e[0] * b[0] + e[1] * b[1]) + e[2] * b[2];
-            const double den = d11 * d22 - d12 * d12;
-            double b1 = (d22 * e1 - d12 * e2) / den, b2 = (d11 * e2 - d12 * e1) / den;
-            if (!(b1 >= 0.0)) b1 = 0.0;                                 // a NaN (a needle: den == 0) is taken to vertex 0
-            if (!(b2 >= 0.0)) b2 = 0.0;
-            const double sum = b1 + b2;
-            if (sum > 1.0) { b1 = b1 / sum; b2 = b2 / sum; }
-            const double b0 = (1.0 - b1) - b2;
+            double bw[3];
+            mesh_bary_weights(a, b, v0, x, bw);                         // shared with tdgp_mesh_interp_normals (mesh_bary.h)
 #pragma unroll
             for (int c = 0; c < 3; c++) {
                 const double c0 = (double)vertex_rgb[(int64_t)idx[0] * 3 + c], c1 = (double)vertex_rgb[(int64_t)idx[1] * 3 + c];
                 const double c2 = (double)vertex_rgb[(int64_t)idx[2] * 3 + c];
-                col[c] = (float)((b0 * c0 + b1 * c1) + b2 * c2);
+                col[c] = (float)((bw[0] * c0 + bw[1] * c1) + bw[2] * c2);
             }
         }
     }

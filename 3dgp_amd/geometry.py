@@ -161,7 +161,7 @@ def grid_to_world(vertices, volume_res, voxel_origin=(0.0, 0.0, 0.0), cube_size=
 
 @torch.no_grad()
 def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=0.3, thresh_value=25.0, crop='reference', normalize=True,
-                     slab_points=2 ** 22, noise_mode='const', units='index', sheared=True, components=None):
+                     slab_points=2 ** 22, noise_mode='const', units='index', sheared=True, components=None, smooth=None):
     """scripts/extract_geometry.py:26-42 per sample of `ws`: density grid -> crop -> marching cubes -> (optionally) scale.  Returns a list of
     Shape(vertices [V,3] fp32, triangles [T,3] int32, sigma [D,H,W] fp32 -- the cropped grid), all on the device.
     crop: 'reference' (extract_geometry.py:33), None, or three slices.  normalize: divide the vertices by the length of their bounding-box
@@ -169,7 +169,9 @@ def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_s
     units='world': the vertices go through `grid_to_world` with this call's volume_res / voxel_origin / cube_size / crop (and `sheared`)
     instead of `normalize` -- the mesh `mesh.render_mesh_views` takes.
     components: None (the raw level set), or a dict of `mesh_components.select` keyword arguments (e.g. dict(keep=1)): the marching-cubes
-    output goes through `mesh_components.clean_mesh` BEFORE it is scaled, so `normalize` divides by the diagonal of the cleaned mesh."""
+    output goes through `mesh_components.clean_mesh` BEFORE it is scaled, so `normalize` divides by the diagonal of the cleaned mesh.
+    smooth: None, or a dict of `mesh_surface.smooth` keyword arguments (e.g. dict(iterations=10)): applied after the cleaning and before the
+    scaling, in index units.  Vertex normals are the caller's: `mesh_surface.vertex_normals` of the final vertices."""
     if units not in ('index', 'world'):
         raise ValueError(f"units must be 'index' or 'world', got {units!r}")
     crop = _crop_slices(crop, volume_res)
@@ -182,6 +184,9 @@ def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_s
         if components is not None:
             from . import mesh_components as _mesh_components
             verts, tris = _mesh_components.clean_mesh(verts, tris, **dict(components))[:2]
+        if smooth is not None:
+            from . import mesh_surface as _mesh_surface
+            verts = _mesh_surface.smooth(verts, tris, **dict(smooth))
         if units == 'world':
             verts = grid_to_world(verts, volume_res, voxel_origin, cube_size, crop, sheared)
         elif normalize and verts.shape[0] > 0:
@@ -200,31 +205,47 @@ def _host(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
-def save_obj(path, vertices, triangles):
-    """Wavefront .obj: `v x y z` lines (shortest text that reads back as the same fp32) and 1-based `f a b c` lines."""
+def _check_normals(normals, v):
+    n = _host(normals, '<f4')
+    if n.shape != v.shape:
+        raise ValueError(f'normals must be [V,3] like the vertices {v.shape}, got {n.shape}')
+    return n
+
+
+def save_obj(path, vertices, triangles, normals=None):
+    """Wavefront .obj: `v x y z` lines (shortest text that reads back as the same fp32) and 1-based `f a b c` lines.  normals [V,3]: `vn x y z`
+    lines after the vertices (the same shortest text) and faces as `f a//a b//b c//c`."""
     v, f = _host(vertices, np.float32).reshape(-1, 3), _host(triangles, np.int32).reshape(-1, 3)
+    text = lambda x: np.format_float_positional(x, unique=True, trim='-')              # noqa: E731
     with open(path, 'w') as fh:
-        fh.write(''.join(f'v {np.format_float_positional(x, unique=True, trim="-")} {np.format_float_positional(y, unique=True, trim="-")} '
-                         f'{np.format_float_positional(z, unique=True, trim="-")}\n' for x, y, z in v))
-        fh.write(''.join(f'f {a + 1} {b + 1} {c + 1}\n' for a, b, c in f.tolist()))
+        fh.write(''.join(f'v {text(x)} {text(y)} {text(z)}\n' for x, y, z in v))
+        if normals is None:
+            fh.write(''.join(f'f {a + 1} {b + 1} {c + 1}\n' for a, b, c in f.tolist()))
+        else:
+            fh.write(''.join(f'vn {text(x)} {text(y)} {text(z)}\n' for x, y, z in _check_normals(normals, v)))
+            fh.write(''.join(f'f {a + 1}//{a + 1} {b + 1}//{b + 1} {c + 1}//{c + 1}\n' for a, b, c in f.tolist()))
 
 
-def save_ply(path, vertices, triangles, colours=None):
+def save_ply(path, vertices, triangles, colours=None, normals=None):
     """Binary little-endian .ply: float32 x y z per vertex, then per face a uchar count (3) and three int32 indices.  colours [V,3] (uint8, or
-    floating point in [0, 1]: clamped, scaled by 255 and rounded): `uchar red green blue` follow each vertex's coordinates."""
+    floating point in [0, 1]: clamped, scaled by 255 and rounded): `uchar red green blue` follow each vertex's coordinates.  normals [V,3]:
+    `float nx ny nz` after x y z and before the colours."""
     v, f = _host(vertices, '<f4').reshape(-1, 3), _host(triangles, '<i4').reshape(-1, 3)
     rgb_props = ''
+    nrm, n_props = (None, '') if normals is None else (_check_normals(normals, v), 'property float nx\nproperty float ny\nproperty float nz\n')
     if colours is not None:
         c = colours.detach().cpu().numpy() if isinstance(colours, torch.Tensor) else np.asarray(colours)
         if c.shape != v.shape:
             raise ValueError(f'colours must be [V,3] like the vertices {v.shape}, got {c.shape}')
         if c.dtype != np.uint8:
             c = np.rint(np.clip(np.nan_to_num(c.astype(np.float64)), 0.0, 1.0) * 255.0).astype(np.uint8)
-        rec = np.empty(len(v), dtype=[('p', '<f4', (3,)), ('c', 'u1', (3,))])
-        rec['p'], rec['c'] = v, c
+        rec = np.empty(len(v), dtype=[('p', '<f4', (3 if nrm is None else 6,)), ('c', 'u1', (3,))])
+        rec['p'], rec['c'] = (v if nrm is None else np.concatenate([v, nrm], axis=1)), c
         v, rgb_props = rec, 'property uchar red\nproperty uchar green\nproperty uchar blue\n'
+    elif nrm is not None:
+        v = np.ascontiguousarray(np.concatenate([v, nrm], axis=1))
     header = ('ply\nformat binary_little_endian 1.0\n'
-              f'element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n{rgb_props}'
+              f'element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n{n_props}{rgb_props}'
               f'element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n')
     faces = np.empty(len(f), dtype=[('n', 'u1'), ('i', '<i4', (3,))])
     faces['n'], faces['i'] = 3, f

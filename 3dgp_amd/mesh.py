@@ -3,13 +3,15 @@
 `shapes.render_shape_views` finds the surface of a density level on the rays, S + N + 7 field points per ray per frame.  The surface does not
 change between the frames of a turn-table, so here it is extracted once per sample (`density_grid` -> `marching_cubes` -> `grid_to_world`)
 and every frame is a visibility buffer of that mesh: tdgp_mesh_visibility (one triangle per lane, a 64-bit atomic minimum of (depth bits,
-triangle) per covered pixel) -> tdgp_mesh_resolve (depth, face normal, colour, the 7 stencil points) -> tdgp_mesh_shade, or -- for smooth
-normals -- the field at the 7 points and tdgp_iso_shade: 7 field points per pixel instead of 87.
+triangle) per covered pixel) -> tdgp_mesh_resolve (depth, face normal, colour, the 7 stencil points) -> tdgp_mesh_shade.  Smooth normals come either
+from the mesh itself (normals='vertex': tdgp_mesh_interp_normals between the two, the vertex normals of mesh_surface.py interpolated at the
+hit -- any mesh, no generator) or from the field (normals='field': the field at the 7 points and tdgp_iso_shade: 7 field points per pixel
+instead of 87).
 
 The arithmetic of the three kernels is fixed operation by operation (include/tdgp.h); the minimum does not depend on the order of its
 operands, so frames are the same bytes on every run, under every permutation of the triangles and every chunking of the cameras.  Limits:
-no clipping at the near plane (a triangle with a vertex nearer than `near` is dropped whole: the cameras sit outside the cube), flat normals
-in 'face' mode, one mesh per call, no anti-aliasing.  GPU only: the kernels have no CPU path.
+no clipping at the near plane (a triangle with a vertex nearer than `near` is dropped whole: the cameras sit outside the cube), one mesh per
+call, no anti-aliasing.  GPU only: the kernels have no CPU path.
 """
 import numpy as np
 import torch
@@ -18,6 +20,7 @@ from . import _lib
 from . import geometry as _geometry
 from . import inference as _inference
 from . import mesh_components as _mesh_components
+from . import mesh_surface as _mesh_surface
 from . import renderer as _renderer
 from . import shapes as _shapes
 from .generator import TensorGroup
@@ -25,7 +28,7 @@ from .geometry import FIELD_POINTS_MAX
 
 MODES = _shapes.MODES
 CULL = {'none': 0, 'back': 1, 'front': 2}
-NORMALS = ('face', 'field')
+NORMALS = ('face', 'field', 'vertex')
 STENCIL = _shapes.STENCIL
 
 
@@ -131,7 +134,7 @@ def mesh_shade(normal, status, ray_d, colour=None, mode='shaded', light=None, am
 # ----------------------------------------------------------------------------------------------------------------------
 # frames
 # ----------------------------------------------------------------------------------------------------------------------
-def _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_call):
+def _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_call, vertex_normals=None):
     if mode not in MODES:
         raise ValueError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
     if normals not in NORMALS:
@@ -140,8 +143,14 @@ def _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_
         raise ValueError(f'cull must be one of {sorted(CULL)}, got {cull!r}')
     if normals == 'field' and (planes is None or G is None):
         raise ValueError("normals='field' evaluates the field at the hits: it needs the generator G and the sample's planes (G.synthesis.tri_planes)")
-    if normals == 'face' and mode == 'colour' and vertex_colours is None:
-        raise ValueError("mode='colour' with normals='face' needs vertex_colours [V,3] (mesh.vertex_colours)")
+    if normals != 'field' and mode == 'colour' and vertex_colours is None:
+        raise ValueError(f"mode='colour' with normals={normals!r} needs vertex_colours [V,3] (mesh.vertex_colours)")
+    if vertex_normals is not None:
+        if normals != 'vertex':
+            raise ValueError(f"vertex_normals are read by normals='vertex' only, got normals={normals!r}")
+        if not isinstance(vertex_normals, torch.Tensor) or vertex_normals.dtype != torch.float32 or vertex_normals.ndim != 2 or vertex_normals.shape[1] != 3:
+            raise ValueError(f'vertex_normals must be an fp32 [V,3] tensor (mesh_surface.vertex_normals), got {getattr(vertex_normals, "dtype", type(vertex_normals).__name__)} '
+                             f'{tuple(getattr(vertex_normals, "shape", ()))}')
     if max_rays_per_call is not None and int(max_rays_per_call) < 1:
         raise ValueError(f'max_rays_per_call must be positive, got {max_rays_per_call!r}')
 
@@ -162,7 +171,7 @@ def vertex_colours(G, planes, vertices, points_per_call=2 ** 22):
 @torch.no_grad()
 def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shaded', normals='face', cull='none', near=None, planes=None, G=None,
                       vertex_colours=None, light=None, ambient=0.2, albedo=(0.8, 0.8, 0.8), background=(1.0, 1.0, 1.0), max_rays_per_call=None,
-                      t_miss=None, step=None):
+                      t_miss=None, step=None, vertex_normals=None):
     """C frames of ONE mesh (vertices [V,3] fp32 in world units, triangles [T,3] int32, on the device) under C cameras (`camera_params`: angles,
     radius, look_at, fov as the renderer takes them) at `resolution` (a side, or (w, h)).
 
@@ -172,11 +181,16 @@ def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shad
     normals='face': the flat normal of the hit triangle (its stored winding; marching cubes: toward lower density) -- no generator is needed, any
     mesh renders.  normals='field': `planes` (this sample's, batch 1) and `G`: the field at the 7 stencil points of every pixel and
     tdgp_iso_shade -- smooth normals, and mode='colour' takes the field's colour at the hit; `step` is the stencil step (default one
-    tri-plane texel).  mode='colour' with face normals interpolates `vertex_colours` [V,3] in [0, 1].
+    tri-plane texel).  normals='vertex': smooth normals from the mesh alone -- `vertex_normals` [V,3] fp32 (default: `mesh_surface.vertex_normals`
+    of this mesh, area weight, computed once per call) interpolated at every hit with the weights of the colour interpolation and normalised
+    (tdgp_mesh_interp_normals); no generator is needed.  A mesh on the CPU is refused as a bad option (ValueError): the mode exists on the device only.  mode='colour' with face or vertex normals interpolates `vertex_colours` [V,3] in [0, 1].
     cull: 'none' | 'back' | 'front'.  near (default cfg.ray_start with a generator, else 1e-3): a triangle with a vertex nearer is dropped whole.
     Cameras are taken in chunks of whole frames, max_rays_per_call rays at most (default 16 frames; never less than one frame): they are
     independent, so the chunking does not change a byte."""
-    _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_call)
+    _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_call, vertex_normals)
+    if normals == 'vertex' and isinstance(vertices, torch.Tensor) and isinstance(triangles, torch.Tensor) and not (vertices.is_cuda and triangles.is_cuda):
+        # this mode is an option of a device mesh only (its corner table is built there): asking for it on a host mesh is a bad option value
+        raise ValueError(f"normals='vertex' takes a mesh on the GPU (got {vertices.device}, {triangles.device}); the vertex normals have no CPU path")
     vertices, triangles = _check_mesh(vertices, triangles)
     w, h = (int(resolution), int(resolution)) if np.isscalar(resolution) else (int(r) for r in resolution)
     if h < 2 or w < 2:
@@ -200,6 +214,11 @@ def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shad
         if not isinstance(planes, _renderer.HWCPlanes) or int(planes.t.shape[0]) != 1:
             raise TypeError("normals='field' takes the HWCPlanes of ONE sample (tri_planes of a batch of one, or HWCPlanes(planes.t[b:b + 1]))")
         point_field = _shapes.field_functions(G.synthesis)[1]
+    vnorm = None
+    if normals == 'vertex':
+        if vertex_normals is not None and tuple(vertex_normals.shape) != tuple(vertices.shape):
+            raise ValueError(f'vertex_normals must be fp32 {tuple(vertices.shape)}, got {tuple(vertex_normals.shape)}')
+        vnorm = _mesh_surface.vertex_normals(vertices, triangles) if vertex_normals is None else vertex_normals
     vrgb = None
     if not field and mode == 'colour':
         vrgb = vertex_colours if vertex_colours.dtype == torch.float32 else vertex_colours.float() / (255.0 if vertex_colours.dtype == torch.uint8 else 1.0)
@@ -216,6 +235,8 @@ def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shad
             stencil = point_field(planes, points.reshape(1, n * STENCIL, 3))
             rgb, normal = _shapes.iso_shade(stencil, status, d, mode=mode, light=light, ambient=ambient, albedo=albedo, background=background)
         else:
+            if vnorm is not None:
+                _mesh_surface.interp_normals(tri, status, t_hit, _lib.f32c(o), _lib.f32c(d), vertices, triangles, vnorm, normal)
             rgb = mesh_shade(normal, status, d, colour=colour, mode=mode, light=light, ambient=ambient, albedo=albedo, background=background)
         k = cs.stop - cs.start
         out.put(cs, slice(0, R), rgb=rgb.reshape(k, R, 3), depth=t_hit.reshape(k, R, 1), normal=normal.reshape(k, R, 3), status=status.reshape(k, R),
@@ -238,7 +259,7 @@ def _camera_slice(camera_params, device, c0, c1):
 
 @torch.no_grad()
 def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=None, crop=None, sheared=True,
-                       mode='shaded', normals='face', plane_batch=4, return_counts=False, components=None, **kw):
+                       mode='shaded', normals='face', plane_batch=4, return_counts=False, components=None, smooth=None, **kw):
     """Mesh frames of every `ws` under its cameras (sample-major: camera n * V + v is view v of sample n).  Per sample: `density_grid` at
     volume_res^3 over a cube of `cube_size` (default the whole field, 2 * cfg.cube_scale) -> `marching_cubes` at `level` -> `grid_to_world`,
     then its V cameras through `render_mesh_views`.  The backbone runs once per plane batch; its planes feed the density grid and, with
@@ -246,6 +267,9 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
     -> TensorGroup(rgb [B*V,R,3], depth, normal, status, tri) as `render_mesh_views`; return_counts=True: also [(vertices, triangles)] per sample.
     components: None (the raw level set), or a dict of `mesh_components.select` keyword arguments (e.g. dict(keep=1)): every sample's mesh goes
     through `mesh_components.clean_mesh` before it is drawn (floaters dropped on the device); the counts are those of the cleaned mesh.
+    smooth: None, or a dict of `mesh_surface.smooth` keyword arguments (e.g. dict(iterations=10)): the mesh is smoothed after the cleaning and
+    before `grid_to_world`, in index units.  normals='vertex': the vertex normals (and, in mode 'colour', the vertex colours) are taken from the
+    final world-space vertices.
     kw: cull, near, light, ambient, albedo, background, max_rays_per_call, t_miss, step of `render_mesh_views`."""
     syn, cfg = G.synthesis, G.cfg
     num_samples = len(ws)
@@ -273,9 +297,11 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
             del sigma
             if components is not None:
                 verts, tris = _mesh_components.clean_mesh(verts, tris, **dict(components))[:2]
+            if smooth is not None:
+                verts = _mesh_surface.smooth(verts, tris, **dict(smooth))
             verts = _geometry.grid_to_world(verts, volume_res, voxel_origin, cube_size, slices, sheared)
             counts.append((int(verts.shape[0]), int(tris.shape[0])))
-            vc = vertex_colours(G, pb, verts) if (mode == 'colour' and normals == 'face') else None
+            vc = vertex_colours(G, pb, verts) if (mode == 'colour' and normals != 'field') else None
             cams = _camera_slice(camera_params, ws.device, (n0 + b) * V, (n0 + b + 1) * V)
             parts.append(render_mesh_views(verts, tris, cams, res, mode=mode, normals=normals, planes=pb if normals == 'field' else None,
                                            G=G, vertex_colours=vc, **kw))

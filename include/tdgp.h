@@ -653,6 +653,71 @@ int     tdgp_mesh_compact_emit(const float* vertices, const int32_t* triangles, 
                                int32_t* out_triangles, int64_t T_out, int32_t* vertex_map, const void* const* attr_in, void* const* attr_out,
                                const int32_t* attr_channels, int num_attr, tdgp_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mesh surfaces (csrc/mesh_surface.hip; the reference's users smooth the mesh and take its vertex normals on the host, trimesh / MeshLab):
+ * the vertex -> triangle incidence of the indexed mesh on the device, in a defined order, and the gathers over it.
+ *   tdgp_mesh_corner_table -> tdgp_mesh_vertex_normals | tdgp_mesh_boundary_vertices | tdgp_mesh_smooth_step (ping-pong, one table)
+ *   tdgp_mesh_resolve -> tdgp_mesh_interp_normals -> tdgp_mesh_shade        (smooth-shaded mesh frames without a field pass)
+ * Common: the rules of the two blocks above, unchanged -- triangles [T,3] int32, vertices [V,3] fp32; a triangle naming an index outside
+ * [0, V) is skipped by every kernel and the index is never dereferenced; arguments are checked before any launch; empty inputs are no-ops;
+ * workspaces are caller-owned, 16-byte aligned, sized by the *_workspace_bytes query (-1 for sizes it refuses); no kernel waits for another
+ * workgroup; there are no floating-point atomics; every floating-point operation is rounded once, in the order written (no contraction into
+ * FMA); `(double)` of a float is exact, `(float)` of a double rounds to nearest even; `/` and sqrt are correctly rounded; comparisons are
+ * ordered.  Here 3 T <= 2^31 - 1 and V <= 2^31 - 2 (corner ids and start[V] are int32).
+ *
+ * tdgp_mesh_corner_table: corner 3t + i is slot i of triangle t.  -> degree int32 [V] = the number of corners of non-skipped triangles that
+ *   name v (a triangle naming v twice counts twice);  start int32 [V+1] = the exclusive prefix sum of degree, start[V] = the total;  corner
+ *   int32, a buffer of 3 T entries of which the first start[V] are written: for each vertex v, at [start[v], start[v+1]), its corners in
+ *   ASCENDING CORNER ID.  The total is also left as one int64 at the START of the workspace, the one number the caller reads back.  The table
+ *   is a pure function of `triangles`: the counts are integer atomics (order-independent), start comes from scans, and a corner's position
+ *   inside its vertex's range is its RANK there (the number of smaller corner ids of the range, counted from a scratch list in the workspace
+ *   whose own order is not relied upon) -- never the arrival order of an atomic.  Cost per vertex O(degree^2) reads spread over degree lanes.
+ *   V == 0: start[0] = 0 and the total 0 are written, nothing else.
+ *
+ * The three gathers take (start, corner) as given -- a caller may pass a table of its own.  The range of v is [start[v], start[v+1]) clamped
+ * into [0, min(start[V], 3T)] (`corner` must hold start[V] entries); d = the length of that range.  An entry outside [0, 3T), or whose
+ * triangle is skipped, adds nothing and is not dereferenced.  One lane per vertex; each sum below is SEQUENTIAL in table order, so the
+ * outputs are pure functions of the arrays as given (the same bytes on every run) but, unlike vis, NOT invariant under a permutation of
+ * the triangles.
+ *
+ * tdgp_mesh_vertex_normals: weight 0 (area) | 1 (uniform) -> normal_out [V,3] fp32.  In double, s = 0; for each corner of v in table order,
+ *   with t = corner / 3 and v0, v1, v2 the triangle's vertices widened:  a = v1 - v0, b = v2 - v0,
+ *   g = (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0)  (tdgp_mesh_resolve's g).   weight 0: s_c = s_c + g_c.   weight 1: q = (g0*g0 + g1*g1)
+ *   + g2*g2; if q > 0 and q < inf: s_c = s_c + g_c / sqrt(q), else the corner adds nothing.   Then q = (s0*s0 + s1*s1) + s2*s2; if q > 0 and
+ *   q < inf: n_c = (float)(s_c / sqrt(q)), else n = 0 (so does a vertex no triangle names).
+ *
+ * tdgp_mesh_boundary_vertices: -> rim_out uint8 [V].  A neighbour of v is the vertex in the next or the previous slot of one of v's corners
+ *   (v itself is not its own neighbour).  rim[v] = 1 iff some neighbour w is named next to v in exactly ONE of v's triangles (a triangle
+ *   naming v in two slots is one triangle): v lies on an edge that one triangle uses.  Integer only; a pure function of the mesh.  The count
+ *   is direct -- for each of the 2 d candidates, one walk over the d corners: O(d^2) per vertex; a vertex of more than 32 corners has its
+ *   candidates spread over its wave.
+ *
+ * tdgp_mesh_smooth_step: factor (finite double), pinned uint8 [V] or NULL -> vertices_out [V,3], which must not overlap vertices_in.  Per
+ *   vertex with d > 0 and not pinned, in double, s = 0; for each corner (t, i) in table order:  s = s + (double)v[tri[t][(i+1)%3]], then
+ *   s = s + (double)v[tri[t][(i+2)%3]], component-wise.   m_c = s_c / (double)(2 d);   out_c = (float)(x_c + factor * (m_c - x_c)) with x the
+ *   vertex's own position widened.  Pinned and d == 0 vertices are copied bit for bit.  (The umbrella operator with multiplicity: on a closed
+ *   manifold every neighbour is counted twice, which is the plain neighbour mean -- no de-duplication is needed.)
+ *
+ * tdgp_mesh_interp_normals: tri int32 [rays], status int32 [rays], t_hit [rays] as tdgp_mesh_resolve wrote them, ray_o / ray_d [rays,3], the
+ *   mesh, vertex_normal [V,3] -> normal [rays,3] IN PLACE.  Per ray with status == 1 and a triangle inside [0, T) whose indices lie in [0, V):
+ *   x_c = o_c + d_c * t_hit (fp32, as tdgp_mesh_resolve forms it);  b0, b1, b2 EXACTLY tdgp_mesh_resolve's colour weights (one __device__
+ *   function, csrc/mesh_bary.h, serves both);  m_c = (b0*n0_c + b1*n1_c) + b2*n2_c in double with n_i the vertex normals widened;
+ *   q = (m0*m0 + m1*m1) + m2*m2;  if q > 0 and q < inf: normal_c = (float)(m_c / sqrt(q)), else the face normal already there stays.  Every
+ *   other ray is not touched.  One writer per element.
+ * --------------------------------------------------------------------------------------------- */
+int64_t tdgp_mesh_corner_table_workspace_bytes(int64_t T, int64_t V);
+int     tdgp_mesh_corner_table(const int32_t* triangles, int64_t T, int64_t V, int32_t* degree, int32_t* start, int32_t* corner,
+                               void* workspace, int64_t workspace_bytes, tdgp_stream_t stream);
+int     tdgp_mesh_vertex_normals(const float* vertices, const int32_t* triangles, int64_t T, int64_t V, const int32_t* start,
+                                 const int32_t* corner, int weight, float* normal_out, tdgp_stream_t stream);
+int     tdgp_mesh_boundary_vertices(const int32_t* triangles, int64_t T, int64_t V, const int32_t* start, const int32_t* corner,
+                                    uint8_t* rim_out, tdgp_stream_t stream);
+int     tdgp_mesh_smooth_step(const float* vertices_in, const int32_t* triangles, int64_t T, int64_t V, const int32_t* start,
+                              const int32_t* corner, double factor, const uint8_t* pinned, float* vertices_out, tdgp_stream_t stream);
+int     tdgp_mesh_interp_normals(const int32_t* tri, const int32_t* status, const float* t_hit, const float* ray_o, const float* ray_d,
+                                 int64_t rays, const float* vertices, int64_t V, const int32_t* triangles, int64_t T,
+                                 const float* vertex_normal, float* normal, tdgp_stream_t stream);
+
 /* Exact order statistics without a sort: the quantile behind the marchers' `cut_quantile` option (tri_plane_renderer.py:324-326, 366-368:
  * torch.quantile of the activated densities; the non-flatness score renders with 0.5, non_flatness_score.py:9-11).
  * out3[0] = sorted(x)[k_lo] and out3[1] = sorted(x)[k_hi], exact bits; out3[2] = torch.lerp(out3[0], out3[1], weight), i.e.

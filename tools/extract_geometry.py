@@ -54,6 +54,12 @@ def build_parser():
                    help="keep only the K largest connected components of the mesh ('all': no limit; default: the raw level set, floaters included)")
     p.add_argument('--component-by', choices=['triangles', 'area'], default=argparse.SUPPRESS, help='what "largest" measures (default: triangles)')
     p.add_argument('--min-component-triangles', type=int, default=argparse.SUPPRESS, metavar='N', help='drop components with fewer than N triangles')
+    # so is the surface pass (mesh_surface.py): Taubin smoothing of the extracted mesh and vertex normals in the .obj / .ply
+    p.add_argument('--smooth-iters', type=int, default=argparse.SUPPRESS, metavar='N', help='Taubin-smooth the mesh on the device: N lambda | mu iterations (default: none)')
+    p.add_argument('--smooth-lambda', type=float, default=argparse.SUPPRESS, help='the shrinking step (default 0.5)')
+    p.add_argument('--smooth-mu', type=float, default=argparse.SUPPRESS, help='the inflating step (default -0.53)')
+    p.add_argument('--smooth-free-boundary', action='store_true', default=argparse.SUPPRESS, help='let the open rims (crop, grid boundary) move too')
+    p.add_argument('--vertex-normals', action='store_true', default=argparse.SUPPRESS, help='write area-weighted vertex normals into the .obj / .ply')
     return p
 
 
@@ -72,6 +78,17 @@ def component_options(args):
     if keep is None and least is None:
         return None
     return dict(keep='all' if keep is None else keep, by=getattr(args, 'component_by', 'triangles'), min_triangles=least or 0)
+
+
+def smooth_options(args):
+    """The `smooth` argument of geometry.extract_geometry / mesh.render_mesh_frames from the command line: None unless --smooth-iters asks for it."""
+    iters = getattr(args, 'smooth_iters', None)
+    if not iters:
+        return None
+    if iters < 0:
+        raise SystemExit(f'--smooth-iters takes a non-negative integer, got {iters}')
+    return dict(iterations=iters, lam=getattr(args, 'smooth_lambda', 0.5), mu=getattr(args, 'smooth_mu', -0.53),
+                fix_boundary=not getattr(args, 'smooth_free_boundary', False))
 
 
 def parse_args(argv=None):
@@ -107,16 +124,17 @@ def main(argv=None):
     names = sample_names(seeds, args.classes)
     os.makedirs(args.output_dir, exist_ok=True)
     need_mesh = args.save_obj or args.save_ply
-    comp = component_options(args)
+    comp, smooth, with_normals = component_options(args), smooth_options(args), getattr(args, 'vertex_normals', False)
     for name, w in zip(names, ws.split(1, dim=0)):
         if need_mesh:
             shape = geometry.extract_geometry(G, w, volume_res=args.volume_res, voxel_origin=args.voxel_origin, cube_size=args.cube_size,
-                                              thresh_value=args.thresh_value, crop='reference', normalize=True, components=comp)[0]
+                                              thresh_value=args.thresh_value, crop='reference', normalize=True, components=comp, smooth=smooth)[0]
             sigma = shape.sigma
+            normals = tdgp.mesh_surface.vertex_normals(shape.vertices, shape.triangles) if with_normals else None
             if args.save_obj:
-                geometry.save_obj(os.path.join(args.output_dir, f'{name}.obj'), shape.vertices, shape.triangles)
+                geometry.save_obj(os.path.join(args.output_dir, f'{name}.obj'), shape.vertices, shape.triangles, normals=normals)
             if args.save_ply:
-                geometry.save_ply(os.path.join(args.output_dir, f'{name}.ply'), shape.vertices, shape.triangles)
+                geometry.save_ply(os.path.join(args.output_dir, f'{name}.ply'), shape.vertices, shape.triangles, normals=normals)
             if args.verbose:
                 print(f'{name}: {shape.vertices.shape[0]} vertices, {shape.triangles.shape[0]} triangles')
                 if comp is not None:

@@ -11,7 +11,8 @@ one strip per sample, its views side by side; .png (the strips stacked into one 
 `--vis shape_grid` / `--vis shape_strips`: the same two layouts of SHAPE frames -- the surface where the raw density reaches `--level`, found on
 the rays and shaded (`--shape-mode shaded | normals | colour`, `--num-refine`, `--ambient`, `--background`; `--depth` shows the hit depths).
 `--vis mesh_grid` / `--vis mesh_strips`: the same layouts of MESH frames -- the surface extracted once per sample (`--volume-res`, `--cube-size`,
-marching cubes at `--level`) and rasterised for every frame; `--mesh-normals face` shades the flat facets, `field` takes the normals from the field.
+marching cubes at `--level`) and rasterised for every frame; `--mesh-normals face` shades the flat facets, `vertex` interpolates the mesh's own vertex normals, `field` takes the normals from the field;
+`--mesh-smooth-iters N` Taubin-smooths every mesh on the device before it is drawn.
 """
 import argparse
 import importlib
@@ -54,8 +55,19 @@ def build_trajectory(args):
     return t
 
 
+class _Parser(argparse.ArgumentParser):
+    """The surface options act on mesh frames alone: given with another --vis they are a usage error, not silently ignored."""
+    def parse_args(self, args=None, namespace=None):
+        a = super().parse_args(args, namespace)
+        if not a.vis.startswith('mesh_') and (a.mesh_normals == 'vertex' or a.mesh_smooth_iters):
+            self.error('--mesh-normals vertex and --mesh-smooth-iters need --vis mesh_grid or mesh_strips')
+        if a.mesh_smooth_iters < 0:
+            self.error(f'--mesh-smooth-iters takes a non-negative integer, got {a.mesh_smooth_iters}')
+        return a
+
+
 def build_parser():
-    p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    p = _Parser(description=__doc__.split('\n')[0])
     p.add_argument('--ckpt', required=True, metavar='DIR', help='directory written by tools/export_reference_checkpoint.py')
     p.add_argument('--seeds', type=parse_range, default=parse_range('0-15'), help="e.g. '0-15' or '1,4,7'")
     p.add_argument('--classes', type=parse_range, default=None, help='class indices of a conditional generator (every seed under every class)')
@@ -85,7 +97,9 @@ def build_parser():
     p.add_argument('--background', type=float, default=1.0, help='shape frames: grey level of the rays that miss, in [-1, 1]')
     p.add_argument('--volume-res', type=int, default=256, help='mesh frames: points per side of the density grid the mesh is extracted from')
     p.add_argument('--cube-size', type=float, default=None, help='mesh frames: side of the cube the grid spans (default: the whole field, 2 * cube_scale)')
-    p.add_argument('--mesh-normals', choices=['face', 'field'], default='face', help='mesh frames: flat facet normals, or normals from the field at the hits')
+    p.add_argument('--mesh-normals', choices=['face', 'field', 'vertex'], default='face',
+                   help='mesh frames: flat facet normals, normals from the field at the hits, or interpolated vertex normals of the mesh')
+    p.add_argument('--mesh-smooth-iters', type=int, default=0, metavar='N', help='mesh frames: Taubin-smooth each mesh, N lambda | mu iterations (default: none)')
     p.add_argument('--keep-components', type=parse_keep, default=None, metavar='K',
                    help="mesh frames: draw only the K largest connected components of each mesh ('all': no limit; default: the raw level set)")
     p.add_argument('--component-by', choices=['triangles', 'area'], default='triangles', help='mesh frames: what "largest" measures')
@@ -125,7 +139,8 @@ def shape_options(args):
 def mesh_options(args):
     """The options of mesh.render_mesh_frames, from the command line."""
     return dict(level=args.level, volume_res=args.volume_res, cube_size=args.cube_size, mode=args.shape_mode, normals=args.mesh_normals,
-                ambient=args.ambient, background=(args.background,) * 3, plane_batch=args.plane_batch, components=component_options(args))
+                ambient=args.ambient, background=(args.background,) * 3, plane_batch=args.plane_batch, components=component_options(args),
+                smooth=dict(iterations=args.mesh_smooth_iters) if args.mesh_smooth_iters > 0 else None)
 
 
 def main(argv=None):
@@ -172,7 +187,8 @@ def main(argv=None):
         line.update(level=args.level, shape_mode=args.shape_mode, num_refine=args.num_refine)
     if args.vis.startswith('mesh_'):
         line.update(level=args.level, shape_mode=args.shape_mode, volume_res=args.volume_res, cube_size=args.cube_size, mesh_normals=args.mesh_normals,
-                    vertices=[v for v, _ in counts], triangles=[t for _, t in counts], components=component_options(args))
+                    vertices=[v for v, _ in counts], triangles=[t for _, t in counts], components=component_options(args),
+                    mesh_smooth_iters=args.mesh_smooth_iters)
     print(json.dumps(line))
 
 
