@@ -96,6 +96,15 @@ _PROTOTYPES = {
     'tdgp_mesh_boundary_vertices': (c_int, [P, c_int64, c_int64, P, P, P, P]),
     'tdgp_mesh_smooth_step': (c_int, [P, P, c_int64, c_int64, P, P, c_double, P, P, P]),
     'tdgp_mesh_interp_normals': (c_int, [P, P, P, P, P, c_int64, P, c_int64, P, c_int64, P, P, P]),
+    'tdgp_mesh_cluster_keys': (c_int, [P, c_int64, POINTER(c_double), POINTER(c_double), P, P]),
+    'tdgp_mesh_cluster_ids_workspace_bytes': (c_int64, [c_int64]),
+    'tdgp_mesh_cluster_ids': (c_int, [P, P, c_int64, P, P, P, P, c_int64, P]),
+    'tdgp_mesh_cluster_triangles_relabel': (c_int, [P, c_int64, c_int64, P, P, P, P]),
+    'tdgp_mesh_cluster_triangles_workspace_bytes': (c_int64, [c_int64]),
+    'tdgp_mesh_cluster_triangles_count': (c_int, [P, P, c_int64, P, P, c_int64, P]),
+    'tdgp_mesh_cluster_triangles_emit': (c_int, [P, c_int64, P, P, c_int64, P, c_int64, P, P]),
+    'tdgp_mesh_cluster_place': (c_int, [P, c_int64, P, P, P, c_int64, POINTER(c_double), POINTER(c_double), P, c_int64, P, P, c_int, c_double, P, P]),
+    'tdgp_mesh_cluster_attribute': (c_int, [P, c_int, c_int64, P, P, c_int64, P, P]),
     'tdgp_quantile_select_workspace_bytes': (c_int64, [c_int64]),
     'tdgp_quantile_select': (c_int, [P, c_int64, c_int64, c_int64, c_float, P, P, c_int64, P]),
     'tdgp_depth_histc': (c_int, [P, c_int64, c_int64, c_float, c_float, c_int, P, P]),

@@ -20,6 +20,15 @@ from . import _lib
 from . import renderer as _renderer
 
 Shape = collections.namedtuple('Shape', ['vertices', 'triangles', 'sigma'])
+
+
+class MeshCount(tuple):
+    """(vertices, triangles) of a finished mesh -- a plain pair to whoever unpacks or compares it -- with `.triangles_before`, the triangles it
+    had before `simplify=` (the same number without it)."""
+    def __new__(cls, vertices, triangles, triangles_before=None):
+        self = super().__new__(cls, (int(vertices), int(triangles)))
+        self.triangles_before = int(triangles if triangles_before is None else triangles_before)
+        return self
 FIELD_POINTS_MAX = (2 ** 31 - 1) // 4          # points one tdgp_triplane_field call takes (csrc/field.hip)
 
 
@@ -161,7 +170,8 @@ def grid_to_world(vertices, volume_res, voxel_origin=(0.0, 0.0, 0.0), cube_size=
 
 @torch.no_grad()
 def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=0.3, thresh_value=25.0, crop='reference', normalize=True,
-                     slab_points=2 ** 22, noise_mode='const', units='index', sheared=True, components=None, smooth=None):
+                     slab_points=2 ** 22, noise_mode='const', units='index', sheared=True, components=None, smooth=None, simplify=None,
+                     return_counts=False):
     """scripts/extract_geometry.py:26-42 per sample of `ws`: density grid -> crop -> marching cubes -> (optionally) scale.  Returns a list of
     Shape(vertices [V,3] fp32, triangles [T,3] int32, sigma [D,H,W] fp32 -- the cropped grid), all on the device.
     crop: 'reference' (extract_geometry.py:33), None, or three slices.  normalize: divide the vertices by the length of their bounding-box
@@ -171,9 +181,17 @@ def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_s
     components: None (the raw level set), or a dict of `mesh_components.select` keyword arguments (e.g. dict(keep=1)): the marching-cubes
     output goes through `mesh_components.clean_mesh` BEFORE it is scaled, so `normalize` divides by the diagonal of the cleaned mesh.
     smooth: None, or a dict of `mesh_surface.smooth` keyword arguments (e.g. dict(iterations=10)): applied after the cleaning and before the
-    scaling, in index units.  Vertex normals are the caller's: `mesh_surface.vertex_normals` of the final vertices."""
+    scaling, in index units.  Vertex normals are the caller's: `mesh_surface.vertex_normals` of the final vertices.
+    simplify: None, or a dict of `mesh_simplify.simplify` keyword arguments with either `cell` (in voxels: dict(cell=2.0)) or `max_triangles`
+    (dict(max_triangles=100000): the first cell of `mesh_simplify.cell_for_triangles`' ladder that leaves no more): vertex clustering with
+    quadric placement after the smoothing and before the scaling, in index units.  return_counts=True: also a list of `MeshCount` per sample
+    (vertices, triangles; `.triangles_before` the simplification)."""
     if units not in ('index', 'world'):
         raise ValueError(f"units must be 'index' or 'world', got {units!r}")
+    if simplify is not None:
+        from . import mesh_simplify as _mesh_simplify
+        _mesh_simplify.check_options(simplify)
+    counts = []
     crop = _crop_slices(crop, volume_res)
     out = []
     for b in range(ws.shape[0]):               # one sample's grid alive at a time, as the reference loops
@@ -187,6 +205,10 @@ def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_s
         if smooth is not None:
             from . import mesh_surface as _mesh_surface
             verts = _mesh_surface.smooth(verts, tris, **dict(smooth))
+        before = int(tris.shape[0])
+        if simplify is not None:
+            verts, tris = _mesh_simplify.apply(verts, tris, simplify)[:2]
+        counts.append(MeshCount(verts.shape[0], tris.shape[0], before))
         if units == 'world':
             verts = grid_to_world(verts, volume_res, voxel_origin, cube_size, crop, sheared)
         elif normalize and verts.shape[0] > 0:
@@ -194,7 +216,7 @@ def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_s
             if float(diag) > 0:
                 verts = verts / diag
         out.append(Shape(verts, tris, sigma))
-    return out
+    return (out, counts) if return_counts else out
 
 
 # ---- writers: host side, numpy only --------------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@ from . import _lib
 from . import geometry as _geometry
 from . import inference as _inference
 from . import mesh_components as _mesh_components
+from . import mesh_simplify as _mesh_simplify
 from . import mesh_surface as _mesh_surface
 from . import renderer as _renderer
 from . import shapes as _shapes
@@ -259,7 +260,7 @@ def _camera_slice(camera_params, device, c0, c1):
 
 @torch.no_grad()
 def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=None, crop=None, sheared=True,
-                       mode='shaded', normals='face', plane_batch=4, return_counts=False, components=None, smooth=None, **kw):
+                       mode='shaded', normals='face', plane_batch=4, return_counts=False, components=None, smooth=None, simplify=None, **kw):
     """Mesh frames of every `ws` under its cameras (sample-major: camera n * V + v is view v of sample n).  Per sample: `density_grid` at
     volume_res^3 over a cube of `cube_size` (default the whole field, 2 * cfg.cube_scale) -> `marching_cubes` at `level` -> `grid_to_world`,
     then its V cameras through `render_mesh_views`.  The backbone runs once per plane batch; its planes feed the density grid and, with
@@ -270,6 +271,9 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
     smooth: None, or a dict of `mesh_surface.smooth` keyword arguments (e.g. dict(iterations=10)): the mesh is smoothed after the cleaning and
     before `grid_to_world`, in index units.  normals='vertex': the vertex normals (and, in mode 'colour', the vertex colours) are taken from the
     final world-space vertices.
+    simplify: None, or a dict as `geometry.extract_geometry` takes it (dict(cell=2.0), dict(max_triangles=N), ...): `mesh_simplify.simplify` after
+    the smoothing and before `grid_to_world`, `cell` in voxels; normals and colours are those of the simplified mesh, and the counts are
+    `geometry.MeshCount`s whose `.triangles_before` holds what the mesh had before.
     kw: cull, near, light, ambient, albedo, background, max_rays_per_call, t_miss, step of `render_mesh_views`."""
     syn, cfg = G.synthesis, G.cfg
     num_samples = len(ws)
@@ -281,6 +285,8 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
     if syn.training:
         raise RuntimeError('render_mesh_frames is the inference route: call .eval() first (training mode renders patches with density noise)')
     _lib.require_cuda(ws, 'ws')
+    if simplify is not None:
+        _mesh_simplify.check_options(simplify)
     cube_size = 2.0 * float(cfg.cube_scale) if cube_size is None else float(cube_size)
     slices = _geometry._crop_slices(crop, volume_res)
     res = syn.test_resolution
@@ -299,8 +305,11 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
                 verts, tris = _mesh_components.clean_mesh(verts, tris, **dict(components))[:2]
             if smooth is not None:
                 verts = _mesh_surface.smooth(verts, tris, **dict(smooth))
+            before = int(tris.shape[0])
+            if simplify is not None:
+                verts, tris = _mesh_simplify.apply(verts, tris, simplify)[:2]
             verts = _geometry.grid_to_world(verts, volume_res, voxel_origin, cube_size, slices, sheared)
-            counts.append((int(verts.shape[0]), int(tris.shape[0])))
+            counts.append(_geometry.MeshCount(verts.shape[0], tris.shape[0], before))
             vc = vertex_colours(G, pb, verts) if (mode == 'colour' and normals != 'field') else None
             cams = _camera_slice(camera_params, ws.device, (n0 + b) * V, (n0 + b + 1) * V)
             parts.append(render_mesh_views(verts, tris, cams, res, mode=mode, normals=normals, planes=pb if normals == 'field' else None,

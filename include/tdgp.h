@@ -718,6 +718,82 @@ int     tdgp_mesh_interp_normals(const int32_t* tri, const int32_t* status, cons
                                  int64_t rays, const float* vertices, int64_t V, const int32_t* triangles, int64_t T,
                                  const float* vertex_normal, float* normal, tdgp_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mesh simplification (csrc/mesh_simplify.hip; the reference's users decimate a host copy of the mesh, trimesh / MeshLab): vertex clustering
+ * on a uniform grid, each cluster's representative placed by its error quadric (Rossignac-Borrel 1993; Lindstrom 2000).
+ *   tdgp_mesh_cluster_keys -> [stable sort of the keys: the caller's] -> tdgp_mesh_cluster_ids
+ *   -> tdgp_mesh_cluster_triangles_relabel -> [stable sorts of the rotated triples: the caller's] -> _triangles_count -> _triangles_emit
+ *   -> tdgp_mesh_corner_table(cluster_triangles, T, C) -> tdgp_mesh_cluster_place, tdgp_mesh_cluster_attribute
+ * Common: the rules of the mesh blocks above, unchanged (skipped indices, checked arguments, empty inputs, caller-owned 16-byte aligned
+ * workspaces sized by a query that answers -1 for sizes it refuses, no waiting between workgroups, no floating-point atomics, every
+ * floating-point operation rounded once in the order written).  3 T <= 2^31 - 1, V <= 2^31 - 2.  cell and origin are three doubles each
+ * on the HOST; every cell[c] is positive and finite, every origin[c] finite.  Every output is a pure function of the arrays as given.
+ *
+ * tdgp_mesh_cluster_keys: -> key int64 [V].  Per axis c, in double: q_c = floor(((double)v_c - origin_c) / cell_c).  If every q_c lies in
+ *   [-2^20, 2^20): key = ((q_2 + 2^20) * 2^21 + (q_1 + 2^20)) * 2^21 + (q_0 + 2^20) -- the index (k_z * N + k_y) * N + k_x, N = 2^21, of the
+ *   cell on a lattice whose indices are biased by 2^20 so that a key is never negative; it ascends with (q_2, q_1, q_0).  Otherwise (a
+ *   non-finite coordinate, a cell outside the lattice) key = -1: the vertex belongs to no cluster.
+ *
+ * tdgp_mesh_cluster_ids: sorted_key int64 [V] ascending and order int32 [V], the STABLE permutation that sorted it (sorted_key[i] =
+ *   key[order[i]]; equal keys by ascending vertex id; keys of -1 first) -> cluster int32 [V], start int32 (a buffer of V + 1 entries of which
+ *   the first C + 1 are written), cluster_key int64 (a buffer of V entries, C written), and C as one int64 at the START of the workspace: the
+ *   one number the caller reads back.  Position i is a head when sorted_key[i] >= 0 and (i == 0 or sorted_key[i-1] != sorted_key[i]); the id
+ *   of a head is the number of heads before it (scans, no atomics), so clusters are numbered by ascending key.  start[id] = i and
+ *   cluster_key[id] = sorted_key[i] at a head, start[C] = V: the members of cluster c are order[start[c] : start[c+1]], ascending vertex id,
+ *   and order[0 : start[0]] are the vertices of no cluster.  cluster[order[i]] = the id of the run i lies in, -1 where sorted_key[i] < 0 (and
+ *   for a vertex `order` does not name).  V == 0: start[0] = 0, C = 0.
+ *
+ * tdgp_mesh_cluster_triangles_relabel: -> cluster_triangles int32 [T,3] and rotated int32 [T,3].  cluster_triangles[t][i] =
+ *   cluster[triangles[t][i]] (negative ids as -1), or -1 in all three slots when any index of t lies outside [0, V): what
+ *   tdgp_mesh_corner_table takes with V = C.  A triangle SURVIVES when its three clusters are >= 0 and pairwise distinct; rotated[t] is then
+ *   its triple rotated so that the smallest id comes first (the winding is kept: (a, b, c) and (a, c, b) stay different), else (-1, -1, -1).
+ *
+ * tdgp_mesh_cluster_triangles_count: rotated, perm int32 [T] or NULL -> keep uint8 [T] and the number kept as one int64 at the START of the
+ *   workspace.  perm NULL: keep[t] = t survives.  perm: a permutation that sorts the rows of `rotated` lexicographically, STABLE (equal rows by
+ *   ascending t): keep[perm[i]] = perm[i] survives and (i == 0 or rotated[perm[i-1]] != rotated[perm[i]]) -- of the triangles that share a
+ *   triple up to rotation, the one of lowest index.  An entry of perm outside [0, T) is passed over.
+ * tdgp_mesh_cluster_triangles_emit: the same workspace, untouched since the count -> out_triangles int32 [T_out,3] = cluster_triangles[t] for
+ *   the kept t in ascending t, triangle_map int32 [T_out] = those t.  Positions come from scans; one beyond T_out is not written.
+ *
+ * tdgp_mesh_cluster_place: placement 0 (mean) | 1 (quadric) -> out_vertices [C,3] fp32.  One lane per cluster,
+ *   everything in double and sequential.  The cell indices q_c are decoded from cluster_key; centre_c = origin_c + ((double)q_c + 0.5) *
+ *   cell_c.  A position p of vertex v is RELATIVE: p_c = (double)v_c - centre_c.
+ *   mean: s = 0; for each member in `order`: s_c = s_c + p_c; m_c = s_c / (double)members.   x = m.
+ *   quadric: (corner_start, corner) is the corner table of cluster_triangles with V = C (ranges clamped as the gathers above clamp them).
+ *   A = 0 (upper triangle), b = 0.  For each corner of the cluster in table order, t = corner / 3, with p0, p1, p2 the relative positions of
+ *   triangles[t]'s vertices (a triangle naming an index outside [0, V) adds nothing):  e1 = p1 - p0, e2 = p2 - p0,
+ *   n = (e1_1*e2_2 - e1_2*e2_1, e1_2*e2_0 - e1_0*e2_2, e1_0*e2_1 - e1_1*e2_0),  d = -((n_0*p0_0 + n_1*p0_1) + n_2*p0_2),
+ *   A_rc = A_rc + n_r*n_c for r <= c,  b_r = b_r + n_r*d.  Once per corner: a triangle with two corners in the cluster counts twice, and a
+ *   triangle that collapses counts too.  No corner: x = m.  Otherwise r_c = -b_c - ((A_c0*m_0 + A_c1*m_1) + A_c2*m_2), and the symmetric A is
+ *   diagonalised by cyclic Jacobi: u = I; 8 sweeps over the pairs (0,1), (0,2), (1,2); a pair (p, q; the third index r) with a_pq == 0 is
+ *   skipped, else  theta = (a_qq - a_pp) / (2 * a_pq),  t = (theta >= 0 ? 1 : -1) / (|theta| + sqrt(theta*theta + 1)),  c = 1 / sqrt(t*t + 1),
+ *   s = t*c;  a_pp = a_pp - t*a_pq, a_qq = a_qq + t*a_pq, a_pq = a_qp = 0;  a_rp = a_pr = c*a_rp - s*a_rq and a_rq = a_qr = s*a_rp + c*a_rq
+ *   (both from the old values);  for k = 0, 1, 2: u_kp = c*u_kp - s*u_kq and u_kq = s*u_kp + c*u_kq (old values).  l_i = a_ii,
+ *   l_max = the largest.  For i = 0, 1, 2 with l_i > rank_tol * l_max: coef = ((u_0i*r_0 + u_1i*r_1) + u_2i*r_2) / l_i, x_c = x_c + u_ci*coef.
+ *   If any x_c is not inside [-cell_c * 0.5, cell_c * 0.5] (NaN included): x = m (Lindstrom's fallback).
+ *   Both: out_c = (float)(centre_c + x_c).
+ * tdgp_mesh_cluster_attribute: attribute fp32 [V, channels], 1 <= channels <= 64 -> out fp32 [C, channels]: per cluster and channel the sum
+ *   of the members' values in `order`, in double, divided by their number, rounded once.
+ * --------------------------------------------------------------------------------------------- */
+int     tdgp_mesh_cluster_keys(const float* vertices, int64_t V, const double* cell, const double* origin, int64_t* key, tdgp_stream_t stream);
+int64_t tdgp_mesh_cluster_ids_workspace_bytes(int64_t V);
+int     tdgp_mesh_cluster_ids(const int64_t* sorted_key, const int32_t* order, int64_t V, int32_t* cluster, int32_t* start,
+                              int64_t* cluster_key, void* workspace, int64_t workspace_bytes, tdgp_stream_t stream);
+int     tdgp_mesh_cluster_triangles_relabel(const int32_t* triangles, int64_t T, int64_t V, const int32_t* cluster,
+                                            int32_t* cluster_triangles, int32_t* rotated, tdgp_stream_t stream);
+int64_t tdgp_mesh_cluster_triangles_workspace_bytes(int64_t T);
+int     tdgp_mesh_cluster_triangles_count(const int32_t* rotated, const int32_t* perm, int64_t T, uint8_t* keep, void* workspace,
+                                          int64_t workspace_bytes, tdgp_stream_t stream);
+int     tdgp_mesh_cluster_triangles_emit(const int32_t* cluster_triangles, int64_t T, const uint8_t* keep, void* workspace,
+                                         int64_t workspace_bytes, int32_t* out_triangles, int64_t T_out, int32_t* triangle_map,
+                                         tdgp_stream_t stream);
+int     tdgp_mesh_cluster_place(const float* vertices, int64_t V, const int32_t* order, const int32_t* start, const int64_t* cluster_key,
+                                int64_t C, const double* cell, const double* origin, const int32_t* triangles, int64_t T,
+                                const int32_t* corner_start, const int32_t* corner, int placement, double rank_tol, float* out_vertices,
+                                tdgp_stream_t stream);
+int     tdgp_mesh_cluster_attribute(const float* attribute, int channels, int64_t V, const int32_t* order, const int32_t* start, int64_t C,
+                                    float* out, tdgp_stream_t stream);
+
 /* Exact order statistics without a sort: the quantile behind the marchers' `cut_quantile` option (tri_plane_renderer.py:324-326, 366-368:
  * torch.quantile of the activated densities; the non-flatness score renders with 0.5, non_flatness_score.py:9-11).
  * out3[0] = sorted(x)[k_lo] and out3[1] = sorted(x)[k_hi], exact bits; out3[2] = torch.lerp(out3[0], out3[1], weight), i.e.

@@ -9,6 +9,7 @@ configs/scripts/extract_geometry.yaml; exactly one of --seeds / --num-seeds must
 """
 import argparse
 import importlib
+import json
 import os
 import re
 import sys
@@ -60,6 +61,11 @@ def build_parser():
     p.add_argument('--smooth-mu', type=float, default=argparse.SUPPRESS, help='the inflating step (default -0.53)')
     p.add_argument('--smooth-free-boundary', action='store_true', default=argparse.SUPPRESS, help='let the open rims (crop, grid boundary) move too')
     p.add_argument('--vertex-normals', action='store_true', default=argparse.SUPPRESS, help='write area-weighted vertex normals into the .obj / .ply')
+    # and the simplification (mesh_simplify.py): vertex clustering with quadric placement, after the smoothing, cells in voxels
+    p.add_argument('--simplify-cell', type=float, default=argparse.SUPPRESS, metavar='X', help='simplify the mesh on the device: one vertex per cell of X voxels (default: none)')
+    p.add_argument('--simplify-max-triangles', type=int, default=argparse.SUPPRESS, metavar='N',
+                   help='simplify with the first cell of the ladder 1, 1.41, 2, ... voxels that leaves at most N triangles')
+    p.add_argument('--simplify-placement', choices=['quadric', 'mean'], default=argparse.SUPPRESS, help='where a cell puts its vertex (default quadric)')
     return p
 
 
@@ -91,9 +97,27 @@ def smooth_options(args):
                 fix_boundary=not getattr(args, 'smooth_free_boundary', False))
 
 
+def simplify_options(args):
+    """The `simplify` argument of geometry.extract_geometry from the command line: None unless --simplify-cell or --simplify-max-triangles asks for it."""
+    cell, most = getattr(args, 'simplify_cell', None), getattr(args, 'simplify_max_triangles', None)
+    if cell is None and most is None:
+        return None
+    opts = dict(cell=cell) if cell is not None else dict(max_triangles=most)
+    opts['placement'] = getattr(args, 'simplify_placement', 'quadric')
+    return opts
+
+
 def parse_args(argv=None):
     p = build_parser()
     args = p.parse_args(argv)
+    if hasattr(args, 'simplify_cell') and hasattr(args, 'simplify_max_triangles'):
+        p.error('--simplify-cell and --simplify-max-triangles exclude each other')
+    if hasattr(args, 'simplify_placement') and simplify_options(args) is None:
+        p.error('--simplify-placement needs --simplify-cell or --simplify-max-triangles')
+    if not 0 < getattr(args, 'simplify_cell', 1.0) < float('inf'):                  # false for NaN too
+        p.error(f'--simplify-cell takes a positive finite number, got {args.simplify_cell}')
+    if getattr(args, 'simplify_max_triangles', 0) < 0:
+        p.error(f'--simplify-max-triangles takes a non-negative integer, got {args.simplify_max_triangles}')
     if args.seeds is None and args.num_seeds is None:
         p.error('You must specify either `num_seeds` or `seeds`')
     if args.seeds is not None and args.num_seeds is not None:
@@ -125,10 +149,13 @@ def main(argv=None):
     os.makedirs(args.output_dir, exist_ok=True)
     need_mesh = args.save_obj or args.save_ply
     comp, smooth, with_normals = component_options(args), smooth_options(args), getattr(args, 'vertex_normals', False)
+    simplify = simplify_options(args)
     for name, w in zip(names, ws.split(1, dim=0)):
         if need_mesh:
-            shape = geometry.extract_geometry(G, w, volume_res=args.volume_res, voxel_origin=args.voxel_origin, cube_size=args.cube_size,
-                                              thresh_value=args.thresh_value, crop='reference', normalize=True, components=comp, smooth=smooth)[0]
+            shapes, counts = geometry.extract_geometry(G, w, volume_res=args.volume_res, voxel_origin=args.voxel_origin, cube_size=args.cube_size,
+                                                       thresh_value=args.thresh_value, crop='reference', normalize=True, components=comp, smooth=smooth,
+                                                       simplify=simplify, return_counts=True)
+            shape = shapes[0]
             sigma = shape.sigma
             normals = tdgp.mesh_surface.vertex_normals(shape.vertices, shape.triangles) if with_normals else None
             if args.save_obj:
@@ -137,6 +164,8 @@ def main(argv=None):
                 geometry.save_ply(os.path.join(args.output_dir, f'{name}.ply'), shape.vertices, shape.triangles, normals=normals)
             if args.verbose:
                 print(f'{name}: {shape.vertices.shape[0]} vertices, {shape.triangles.shape[0]} triangles')
+                if simplify is not None:
+                    print(json.dumps(dict(name=name, simplify=simplify, vertices=counts[0][0], triangles=counts[0][1], triangles_before_simplify=counts[0].triangles_before)))
                 if comp is not None:
                     # the report measures the raw level set of the grid the shape was cut from (one more marching-cubes pass, verbose runs only)
                     raw_v, raw_t = geometry.marching_cubes(sigma, args.thresh_value)

@@ -12,7 +12,8 @@ one strip per sample, its views side by side; .png (the strips stacked into one 
 the rays and shaded (`--shape-mode shaded | normals | colour`, `--num-refine`, `--ambient`, `--background`; `--depth` shows the hit depths).
 `--vis mesh_grid` / `--vis mesh_strips`: the same layouts of MESH frames -- the surface extracted once per sample (`--volume-res`, `--cube-size`,
 marching cubes at `--level`) and rasterised for every frame; `--mesh-normals face` shades the flat facets, `vertex` interpolates the mesh's own vertex normals, `field` takes the normals from the field;
-`--mesh-smooth-iters N` Taubin-smooths every mesh on the device before it is drawn.
+`--mesh-smooth-iters N` Taubin-smooths every mesh on the device before it is drawn; `--mesh-simplify-cell X` then clusters its vertices in cells of
+X voxels (quadric placement) and draws the simplified mesh.
 """
 import argparse
 import importlib
@@ -61,6 +62,11 @@ class _Parser(argparse.ArgumentParser):
         a = super().parse_args(args, namespace)
         if not a.vis.startswith('mesh_') and (a.mesh_normals == 'vertex' or a.mesh_smooth_iters):
             self.error('--mesh-normals vertex and --mesh-smooth-iters need --vis mesh_grid or mesh_strips')
+        if a.mesh_simplify_cell is not None:
+            if not a.vis.startswith('mesh_'):
+                self.error('--mesh-simplify-cell needs --vis mesh_grid or mesh_strips')
+            if not 0 < a.mesh_simplify_cell < float('inf'):
+                self.error(f'--mesh-simplify-cell takes a positive finite number, got {a.mesh_simplify_cell}')
         if a.mesh_smooth_iters < 0:
             self.error(f'--mesh-smooth-iters takes a non-negative integer, got {a.mesh_smooth_iters}')
         return a
@@ -100,6 +106,8 @@ def build_parser():
     p.add_argument('--mesh-normals', choices=['face', 'field', 'vertex'], default='face',
                    help='mesh frames: flat facet normals, normals from the field at the hits, or interpolated vertex normals of the mesh')
     p.add_argument('--mesh-smooth-iters', type=int, default=0, metavar='N', help='mesh frames: Taubin-smooth each mesh, N lambda | mu iterations (default: none)')
+    p.add_argument('--mesh-simplify-cell', type=float, default=None, metavar='X',
+                   help='mesh frames: simplify each mesh on the device, one vertex per cell of X voxels, placed by its error quadric (default: none)')
     p.add_argument('--keep-components', type=parse_keep, default=None, metavar='K',
                    help="mesh frames: draw only the K largest connected components of each mesh ('all': no limit; default: the raw level set)")
     p.add_argument('--component-by', choices=['triangles', 'area'], default='triangles', help='mesh frames: what "largest" measures')
@@ -140,7 +148,8 @@ def mesh_options(args):
     """The options of mesh.render_mesh_frames, from the command line."""
     return dict(level=args.level, volume_res=args.volume_res, cube_size=args.cube_size, mode=args.shape_mode, normals=args.mesh_normals,
                 ambient=args.ambient, background=(args.background,) * 3, plane_batch=args.plane_batch, components=component_options(args),
-                smooth=dict(iterations=args.mesh_smooth_iters) if args.mesh_smooth_iters > 0 else None)
+                smooth=dict(iterations=args.mesh_smooth_iters) if args.mesh_smooth_iters > 0 else None,
+                simplify=dict(cell=args.mesh_simplify_cell) if args.mesh_simplify_cell is not None else None)
 
 
 def main(argv=None):
@@ -188,7 +197,8 @@ def main(argv=None):
     if args.vis.startswith('mesh_'):
         line.update(level=args.level, shape_mode=args.shape_mode, volume_res=args.volume_res, cube_size=args.cube_size, mesh_normals=args.mesh_normals,
                     vertices=[v for v, _ in counts], triangles=[t for _, t in counts], components=component_options(args),
-                    mesh_smooth_iters=args.mesh_smooth_iters)
+                    mesh_smooth_iters=args.mesh_smooth_iters, mesh_simplify_cell=args.mesh_simplify_cell,
+                    triangles_before_simplify=[c.triangles_before for c in counts])
     print(json.dumps(line))
 
 
