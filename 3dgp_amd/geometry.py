@@ -20,13 +20,15 @@ from . import _lib
 from . import renderer as _renderer
 
 Shape = collections.namedtuple('Shape', ['vertices', 'triangles', 'sigma'])
+TexturedShape = collections.namedtuple('TexturedShape', ['vertices', 'triangles', 'sigma', 'texture'])
 
 
 class MeshCount(tuple):
     """(vertices, triangles) of a finished mesh -- a plain pair to whoever unpacks or compares it -- with `.triangles_before`, the triangles it
-    had before `simplify=` (the same number without it)."""
+    had before `simplify=` (the same number without it), and `.atlas`, the `mesh_texture.Atlas` of its texture (None without `texture=`)."""
     def __new__(cls, vertices, triangles, triangles_before=None):
         self = super().__new__(cls, (int(vertices), int(triangles)))
+        self.atlas = None
         self.triangles_before = int(triangles if triangles_before is None else triangles_before)
         return self
 FIELD_POINTS_MAX = (2 ** 31 - 1) // 4          # points one tdgp_triplane_field call takes (csrc/field.hip)
@@ -171,7 +173,7 @@ def grid_to_world(vertices, volume_res, voxel_origin=(0.0, 0.0, 0.0), cube_size=
 @torch.no_grad()
 def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=0.3, thresh_value=25.0, crop='reference', normalize=True,
                      slab_points=2 ** 22, noise_mode='const', units='index', sheared=True, components=None, smooth=None, simplify=None,
-                     return_counts=False):
+                     return_counts=False, texture=None):
     """scripts/extract_geometry.py:26-42 per sample of `ws`: density grid -> crop -> marching cubes -> (optionally) scale.  Returns a list of
     Shape(vertices [V,3] fp32, triangles [T,3] int32, sigma [D,H,W] fp32 -- the cropped grid), all on the device.
     crop: 'reference' (extract_geometry.py:33), None, or three slices.  normalize: divide the vertices by the length of their bounding-box
@@ -185,17 +187,31 @@ def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_s
     simplify: None, or a dict of `mesh_simplify.simplify` keyword arguments with either `cell` (in voxels: dict(cell=2.0)) or `max_triangles`
     (dict(max_triangles=100000): the first cell of `mesh_simplify.cell_for_triangles`' ladder that leaves no more): vertex clustering with
     quadric placement after the smoothing and before the scaling, in index units.  return_counts=True: also a list of `MeshCount` per sample
-    (vertices, triangles; `.triangles_before` the simplification)."""
+    (vertices, triangles; `.triangles_before` the simplification).
+    texture: None (this function as it was: `Shape`s), or a dict(texels=8) (also fill, points_per_call of `mesh_texture.bake`): the planes are
+    computed once per sample and feed both the density grid and the bake; the texture is baked on the `grid_to_world` vertices of the final
+    mesh WHATEVER `units` returns (the field lives in world units), and every item is a TexturedShape(vertices, triangles, sigma, texture)
+    whose `texture` is a `mesh_texture.Texture`; the counts carry its `.atlas`."""
     if units not in ('index', 'world'):
         raise ValueError(f"units must be 'index' or 'world', got {units!r}")
     if simplify is not None:
         from . import mesh_simplify as _mesh_simplify
         _mesh_simplify.check_options(simplify)
+    bake_kw = None
+    if texture is not None:
+        from . import mesh_texture as _mesh_texture
+        bake_kw, _ = _mesh_texture.check_options(texture)
     counts = []
     crop = _crop_slices(crop, volume_res)
     out = []
     for b in range(ws.shape[0]):               # one sample's grid alive at a time, as the reference loops
-        sigma = density_grid(G, ws[b:b + 1], volume_res, voxel_origin, cube_size, slab_points, noise_mode)[0]
+        if texture is None:
+            sigma = density_grid(G, ws[b:b + 1], volume_res, voxel_origin, cube_size, slab_points, noise_mode)[0]
+        else:
+            syn = G.synthesis
+            _lib.require_cuda(ws, 'ws')
+            planes = _renderer.planes_to_hwc(syn.tri_plane_decoder(ws[b:b + 1, :syn.tri_plane_decoder.num_ws], hwc=True, noise_mode=noise_mode))
+            sigma = density_grid_from_planes(G, planes, volume_res, voxel_origin, cube_size, slab_points)[0]
         if crop is not None:
             sigma = sigma[crop]
         verts, tris = marching_cubes(sigma, thresh_value)
@@ -209,13 +225,17 @@ def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_s
         if simplify is not None:
             verts, tris = _mesh_simplify.apply(verts, tris, simplify)[:2]
         counts.append(MeshCount(verts.shape[0], tris.shape[0], before))
+        if texture is not None:
+            world = grid_to_world(verts, volume_res, voxel_origin, cube_size, crop, sheared)
+            tex = _mesh_texture.bake_field(G, planes, world, tris, **bake_kw)
+            counts[-1].atlas = tex.atlas
         if units == 'world':
             verts = grid_to_world(verts, volume_res, voxel_origin, cube_size, crop, sheared)
         elif normalize and verts.shape[0] > 0:
             diag = (verts.max(dim=0).values - verts.min(dim=0).values).norm()
             if float(diag) > 0:
                 verts = verts / diag
-        out.append(Shape(verts, tris, sigma))
+        out.append(Shape(verts, tris, sigma) if texture is None else TexturedShape(verts, tris, sigma, tex))
     return (out, counts) if return_counts else out
 
 
@@ -234,11 +254,22 @@ def _check_normals(normals, v):
     return n
 
 
-def save_obj(path, vertices, triangles, normals=None):
+def save_obj(path, vertices, triangles, normals=None, uvs=None, texture=None):
     """Wavefront .obj: `v x y z` lines (shortest text that reads back as the same fp32) and 1-based `f a b c` lines.  normals [V,3]: `vn x y z`
-    lines after the vertices (the same shortest text) and faces as `f a//a b//b c//c`."""
+    lines after the vertices (the same shortest text) and faces as `f a//a b//b c//c`.
+    uvs [T,3,2] (`mesh_texture.atlas_uvs`: one pair per corner): `vt u v` lines (the same shortest text) after the vertices and normals, corner
+    i of triangle t being vt 3t + i + 1, and faces as `f a/ta b/tb c/tc`, or `a/ta/na` with normals.  texture (needs uvs): a uint8 [H,W,3]
+    image (or a `mesh_texture.Texture`, whose uvs are then the default) written with PIL as NAME.png next to NAME.obj, with NAME.mtl
+    (`newmtl baked`, `Kd 1 1 1`, `map_Kd NAME.png`) and `mtllib NAME.mtl` / `usemtl baked` in the .obj.  uvs=None writes the bytes this
+    function always wrote."""
     v, f = _host(vertices, np.float32).reshape(-1, 3), _host(triangles, np.int32).reshape(-1, 3)
     text = lambda x: np.format_float_positional(x, unique=True, trim='-')              # noqa: E731
+    if texture is not None and hasattr(texture, 'image') and hasattr(texture, 'uvs'):
+        uvs, texture = (texture.uvs if uvs is None else uvs), texture.image
+    if uvs is not None:
+        return _save_obj_uv(path, v, f, normals, uvs, texture, text)
+    if texture is not None:
+        raise ValueError('save_obj: a texture needs uvs (mesh_texture.atlas_uvs)')
     with open(path, 'w') as fh:
         fh.write(''.join(f'v {text(x)} {text(y)} {text(z)}\n' for x, y, z in v))
         if normals is None:
@@ -246,6 +277,40 @@ def save_obj(path, vertices, triangles, normals=None):
         else:
             fh.write(''.join(f'vn {text(x)} {text(y)} {text(z)}\n' for x, y, z in _check_normals(normals, v)))
             fh.write(''.join(f'f {a + 1}//{a + 1} {b + 1}//{b + 1} {c + 1}//{c + 1}\n' for a, b, c in f.tolist()))
+
+
+def _save_obj_uv(path, v, f, normals, uvs, image, text):
+    """save_obj with texture coordinates (and the .mtl / .png pair when there is an image)."""
+    import os
+    uv = _host(uvs, np.float32)
+    if uv.shape != (len(f), 3, 2):
+        raise ValueError(f'uvs must be [T,3,2] for the {len(f)} triangles, got {uv.shape}')
+    n = None if normals is None else _check_normals(normals, v)
+    stem = os.path.splitext(os.path.basename(path))[0]
+    if image is not None:
+        from PIL import Image
+        img = _host(image, np.uint8)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError(f'texture must be a uint8 [H,W,3] image, got {img.shape}')
+        if img.shape[0] == 0 or img.shape[1] == 0:
+            raise ValueError('texture is empty (a mesh without triangles has no atlas): write the .obj without it')
+        folder = os.path.dirname(path)
+        Image.fromarray(img).save(os.path.join(folder, stem + '.png'))
+        with open(os.path.join(folder, stem + '.mtl'), 'w') as fh:
+            fh.write(f'newmtl baked\nKd 1 1 1\nmap_Kd {stem}.png\n')
+    with open(path, 'w') as fh:
+        if image is not None:
+            fh.write(f'mtllib {stem}.mtl\n')
+        fh.write(''.join(f'v {text(x)} {text(y)} {text(z)}\n' for x, y, z in v))
+        if n is not None:
+            fh.write(''.join(f'vn {text(x)} {text(y)} {text(z)}\n' for x, y, z in n))
+        fh.write(''.join(f'vt {text(a)} {text(b)}\n' for a, b in uv.reshape(-1, 2)))
+        if image is not None:
+            fh.write('usemtl baked\n')
+        if n is None:
+            fh.write(''.join(f'f {a + 1}/{3 * t + 1} {b + 1}/{3 * t + 2} {c + 1}/{3 * t + 3}\n' for t, (a, b, c) in enumerate(f.tolist())))
+        else:
+            fh.write(''.join(f'f {a + 1}/{3 * t + 1}/{a + 1} {b + 1}/{3 * t + 2}/{b + 1} {c + 1}/{3 * t + 3}/{c + 1}\n' for t, (a, b, c) in enumerate(f.tolist())))
 
 
 def save_ply(path, vertices, triangles, colours=None, normals=None):

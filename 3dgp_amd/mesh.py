@@ -6,7 +6,8 @@ and every frame is a visibility buffer of that mesh: tdgp_mesh_visibility (one t
 triangle) per covered pixel) -> tdgp_mesh_resolve (depth, face normal, colour, the 7 stencil points) -> tdgp_mesh_shade.  Smooth normals come either
 from the mesh itself (normals='vertex': tdgp_mesh_interp_normals between the two, the vertex normals of mesh_surface.py interpolated at the
 hit -- any mesh, no generator) or from the field (normals='field': the field at the 7 points and tdgp_iso_shade: 7 field points per pixel
-instead of 87).
+instead of 87).  The colour of mode 'colour' is interpolated from one value per vertex by resolve, or, with a `mesh_texture.Texture`, fetched
+from the per-triangle atlas baked from the field (tdgp_mesh_sample_texture between resolve and shade; mesh_texture.py).
 
 The arithmetic of the three kernels is fixed operation by operation (include/tdgp.h); the minimum does not depend on the order of its
 operands, so frames are the same bytes on every run, under every permutation of the triangles and every chunking of the cameras.  Limits:
@@ -22,6 +23,7 @@ from . import inference as _inference
 from . import mesh_components as _mesh_components
 from . import mesh_simplify as _mesh_simplify
 from . import mesh_surface as _mesh_surface
+from . import mesh_texture as _mesh_texture
 from . import renderer as _renderer
 from . import shapes as _shapes
 from .generator import TensorGroup
@@ -135,7 +137,7 @@ def mesh_shade(normal, status, ray_d, colour=None, mode='shaded', light=None, am
 # ----------------------------------------------------------------------------------------------------------------------
 # frames
 # ----------------------------------------------------------------------------------------------------------------------
-def _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_call, vertex_normals=None):
+def _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_call, vertex_normals=None, texture=None, texture_filter='bilinear'):
     if mode not in MODES:
         raise ValueError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
     if normals not in NORMALS:
@@ -144,7 +146,14 @@ def _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_
         raise ValueError(f'cull must be one of {sorted(CULL)}, got {cull!r}')
     if normals == 'field' and (planes is None or G is None):
         raise ValueError("normals='field' evaluates the field at the hits: it needs the generator G and the sample's planes (G.synthesis.tri_planes)")
-    if normals != 'field' and mode == 'colour' and vertex_colours is None:
+    if texture is not None:
+        if normals == 'field':
+            raise ValueError("texture is fetched with face or vertex normals; normals='field' takes its colour from the field at the hit")
+        if mode != 'colour':
+            raise ValueError(f"texture is the colour of mode='colour', got mode={mode!r}")
+        if texture_filter not in _mesh_texture.FILTERS:
+            raise ValueError(f'texture_filter must be one of {sorted(_mesh_texture.FILTERS)}, got {texture_filter!r}')
+    if normals != 'field' and mode == 'colour' and vertex_colours is None and texture is None:
         raise ValueError(f"mode='colour' with normals={normals!r} needs vertex_colours [V,3] (mesh.vertex_colours)")
     if vertex_normals is not None:
         if normals != 'vertex':
@@ -172,7 +181,7 @@ def vertex_colours(G, planes, vertices, points_per_call=2 ** 22):
 @torch.no_grad()
 def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shaded', normals='face', cull='none', near=None, planes=None, G=None,
                       vertex_colours=None, light=None, ambient=0.2, albedo=(0.8, 0.8, 0.8), background=(1.0, 1.0, 1.0), max_rays_per_call=None,
-                      t_miss=None, step=None, vertex_normals=None):
+                      t_miss=None, step=None, vertex_normals=None, texture=None, texture_filter='bilinear'):
     """C frames of ONE mesh (vertices [V,3] fp32 in world units, triangles [T,3] int32, on the device) under C cameras (`camera_params`: angles,
     radius, look_at, fov as the renderer takes them) at `resolution` (a side, or (w, h)).
 
@@ -185,10 +194,14 @@ def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shad
     tri-plane texel).  normals='vertex': smooth normals from the mesh alone -- `vertex_normals` [V,3] fp32 (default: `mesh_surface.vertex_normals`
     of this mesh, area weight, computed once per call) interpolated at every hit with the weights of the colour interpolation and normalised
     (tdgp_mesh_interp_normals); no generator is needed.  A mesh on the CPU is refused as a bad option (ValueError): the mode exists on the device only.  mode='colour' with face or vertex normals interpolates `vertex_colours` [V,3] in [0, 1].
+    texture: None, or the `mesh_texture.Texture` baked for THIS mesh (its uvs have T rows, else ValueError): mode='colour' with face or vertex
+    normals then takes the colour of every hit from the texture (tdgp_mesh_sample_texture between resolve and shade; texture_filter
+    'bilinear' | 'nearest') instead of `vertex_colours`, which is not needed.  The colour is still lit: ambient=1.0 gives the unlit texture.
+    texture with normals='field', or with another mode, is a ValueError.
     cull: 'none' | 'back' | 'front'.  near (default cfg.ray_start with a generator, else 1e-3): a triangle with a vertex nearer is dropped whole.
     Cameras are taken in chunks of whole frames, max_rays_per_call rays at most (default 16 frames; never less than one frame): they are
     independent, so the chunking does not change a byte."""
-    _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_call, vertex_normals)
+    _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_call, vertex_normals, texture, texture_filter)
     if normals == 'vertex' and isinstance(vertices, torch.Tensor) and isinstance(triangles, torch.Tensor) and not (vertices.is_cuda and triangles.is_cuda):
         # this mode is an option of a device mesh only (its corner table is built there): asking for it on a host mesh is a bad option value
         raise ValueError(f"normals='vertex' takes a mesh on the GPU (got {vertices.device}, {triangles.device}); the vertex normals have no CPU path")
@@ -220,8 +233,10 @@ def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shad
         if vertex_normals is not None and tuple(vertex_normals.shape) != tuple(vertices.shape):
             raise ValueError(f'vertex_normals must be fp32 {tuple(vertices.shape)}, got {tuple(vertex_normals.shape)}')
         vnorm = _mesh_surface.vertex_normals(vertices, triangles) if vertex_normals is None else vertex_normals
+    if texture is not None:
+        _mesh_texture._check_texture(texture, int(triangles.shape[0]))
     vrgb = None
-    if not field and mode == 'colour':
+    if not field and mode == 'colour' and texture is None:
         vrgb = vertex_colours if vertex_colours.dtype == torch.float32 else vertex_colours.float() / (255.0 if vertex_colours.dtype == torch.uint8 else 1.0)
     max_rays = 16 * R if max_rays_per_call is None else int(max_rays_per_call)
     cstep = max(1, min(max_rays, FIELD_POINTS_MAX // STENCIL) // R)
@@ -238,6 +253,8 @@ def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shad
         else:
             if vnorm is not None:
                 _mesh_surface.interp_normals(tri, status, t_hit, _lib.f32c(o), _lib.f32c(d), vertices, triangles, vnorm, normal)
+            if texture is not None:
+                colour = _mesh_texture.sample_texture(tri, status, t_hit, _lib.f32c(o), _lib.f32c(d), vertices, triangles, texture, texture_filter)
             rgb = mesh_shade(normal, status, d, colour=colour, mode=mode, light=light, ambient=ambient, albedo=albedo, background=background)
         k = cs.stop - cs.start
         out.put(cs, slice(0, R), rgb=rgb.reshape(k, R, 3), depth=t_hit.reshape(k, R, 1), normal=normal.reshape(k, R, 3), status=status.reshape(k, R),
@@ -260,7 +277,7 @@ def _camera_slice(camera_params, device, c0, c1):
 
 @torch.no_grad()
 def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=None, crop=None, sheared=True,
-                       mode='shaded', normals='face', plane_batch=4, return_counts=False, components=None, smooth=None, simplify=None, **kw):
+                       mode='shaded', normals='face', plane_batch=4, return_counts=False, components=None, smooth=None, simplify=None, texture=None, **kw):
     """Mesh frames of every `ws` under its cameras (sample-major: camera n * V + v is view v of sample n).  Per sample: `density_grid` at
     volume_res^3 over a cube of `cube_size` (default the whole field, 2 * cfg.cube_scale) -> `marching_cubes` at `level` -> `grid_to_world`,
     then its V cameras through `render_mesh_views`.  The backbone runs once per plane batch; its planes feed the density grid and, with
@@ -274,6 +291,10 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
     simplify: None, or a dict as `geometry.extract_geometry` takes it (dict(cell=2.0), dict(max_triangles=N), ...): `mesh_simplify.simplify` after
     the smoothing and before `grid_to_world`, `cell` in voxels; normals and colours are those of the simplified mesh, and the counts are
     `geometry.MeshCount`s whose `.triangles_before` holds what the mesh had before.
+    texture: None, or a dict(texels=8, filter='bilinear') (also fill, points_per_call of `mesh_texture.bake`): every sample's texture is baked
+    from the planes in hand on its FINAL world-space mesh -- after components, smoothing, simplification and `grid_to_world` -- and the frames
+    take their colour from it (mode='colour', face or vertex normals) instead of the vertex colours; every count's `.atlas` is then the sample's
+    `mesh_texture.Atlas` (None without a texture).
     kw: cull, near, light, ambient, albedo, background, max_rays_per_call, t_miss, step of `render_mesh_views`."""
     syn, cfg = G.synthesis, G.cfg
     num_samples = len(ws)
@@ -281,7 +302,8 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
     V = _renderer.views_per_sample(int(get('angles').shape[0]), num_samples, f'{num_samples} samples')
     if int(plane_batch) < 1:
         raise ValueError(f'plane_batch must be positive, got {plane_batch!r}')
-    _check_options(mode, normals, kw.get('cull', 'none'), True, G, True, kw.get('max_rays_per_call'))
+    bake_kw, tex_filter = (None, 'bilinear') if texture is None else _mesh_texture.check_options(texture)
+    _check_options(mode, normals, kw.get('cull', 'none'), True, G, True, kw.get('max_rays_per_call'), None, texture, tex_filter)
     if syn.training:
         raise RuntimeError('render_mesh_frames is the inference route: call .eval() first (training mode renders patches with density noise)')
     _lib.require_cuda(ws, 'ws')
@@ -310,10 +332,14 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
                 verts, tris = _mesh_simplify.apply(verts, tris, simplify)[:2]
             verts = _geometry.grid_to_world(verts, volume_res, voxel_origin, cube_size, slices, sheared)
             counts.append(_geometry.MeshCount(verts.shape[0], tris.shape[0], before))
-            vc = vertex_colours(G, pb, verts) if (mode == 'colour' and normals != 'field') else None
+            tex = None
+            if texture is not None:
+                tex = _mesh_texture.bake_field(G, pb, verts, tris, **bake_kw)
+                counts[-1].atlas = tex.atlas
+            vc = vertex_colours(G, pb, verts) if (mode == 'colour' and normals != 'field' and tex is None) else None
             cams = _camera_slice(camera_params, ws.device, (n0 + b) * V, (n0 + b + 1) * V)
             parts.append(render_mesh_views(verts, tris, cams, res, mode=mode, normals=normals, planes=pb if normals == 'field' else None,
-                                           G=G, vertex_colours=vc, **kw))
+                                           G=G, vertex_colours=vc, **({} if tex is None else dict(texture=tex, texture_filter=tex_filter)), **kw))
     frames = parts[0] if len(parts) == 1 else TensorGroup.cat(parts, dim=0)
     return (frames, counts) if return_counts else frames
 

@@ -794,6 +794,58 @@ int     tdgp_mesh_cluster_place(const float* vertices, int64_t V, const int32_t*
 int     tdgp_mesh_cluster_attribute(const float* attribute, int channels, int64_t V, const int32_t* order, const int32_t* start, int64_t C,
                                     float* out, tdgp_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mesh textures (csrc/mesh_texture.hip; the reference's users bake a texture in MeshLab / Blender after decimating): a per-triangle atlas
+ * whose layout is a pure function of the triangle count, filled from the field, and fetched at the hits of a mesh frame.
+ *   tdgp_atlas_points -> [the field's colour at the points: the caller's] -> tdgp_atlas_texels
+ *   tdgp_mesh_resolve -> tdgp_mesh_sample_texture -> tdgp_mesh_shade        (where tdgp_mesh_interp_normals sits for the normals)
+ * Common: the rules of the mesh blocks above, unchanged -- triangles [T,3] int32, vertices [V,3] fp32, 0 <= T, V <= 2^31 - 1; a triangle
+ * naming an index outside [0, V) is never dereferenced; arguments are checked before any launch; one writer per element, no atomics, no
+ * workspace; every floating-point operation is rounded once in the order written (no contraction into FMA); `(double)` of a float or an
+ * integer is exact, `(float)` of a double rounds to nearest even; `/` is correctly rounded; comparisons are ordered.
+ *
+ * THE ATLAS of T triangles at n texels (2 <= n <= 64; TDGP_EINVAL outside):  S = n + 2;  P = ceil(T / 2);  r = the smallest integer with
+ *   r*r >= P;  W = r*S;  H = ceil(P / r)*S (T == 0: r = W = H = 0, nothing is launched).  W, H <= 16384, else TDGP_EUNSUPPORTED; any other
+ *   (r, W, H) than these is TDGP_EINVAL.  The image is uint8 [H,W,3], row 0 at the top.  Tile k has its origin at (X0, Y0) = ((k % r)*S,
+ *   (k / r)*S) and holds triangle 2k ("lower") and triangle 2k + 1 ("upper").  Texel (px, py) of a tile belongs to the lower triangle iff
+ *   px + py <= n, else to the upper one; the owner's texel coordinates are (qx, qy) = (px, py) for the lower and (S-1-px, S-1-py) for the
+ *   upper triangle, and its barycentric coordinates  b1 = qx / (n-1),  b2 = qy / (n-1),  b0 = (1 - b1) - b2  in double, NOT CLAMPED.
+ *   Texel centres with qx + qy <= n - 1 lie on the triangle: its corners and edges are texel centres (v0 at q = (0,0), v1 at (n-1,0), v2 at
+ *   (0,n-1)).  The diagonals beyond the hypotenuse (one for a lower, two for an upper triangle) are the gutter: they are sampled on the
+ *   triangle's plane just outside it, b0 < 0.  This extrapolation is what makes a bilinear fetch reproduce a colour that is linear in
+ *   position exactly, the hypotenuse included: the four taps of any point of the triangle lie in the triangle's own half tile.
+ *   A texel of a tile >= P, and the upper half of the last tile when T is odd, is unowned.
+ *
+ * tdgp_atlas_points: -> points fp32 [H*W,3], owner int32 [H*W], one lane per texel, texel-major (texel i is row i / W, column i % W).
+ *   owner = the triangle's index; -1 for an unowned texel and for a triangle with a vertex outside [0, V).  Owned:
+ *   point_c = (float)((b0*v0_c + b1*v1_c) + b2*v2_c) in double with v_i the triangle's vertices widened.  owner -1: the point (0, 0, 0).
+ *   There is no division other than by n - 1: a needle or a triangle of no area is well defined.
+ *
+ * tdgp_atlas_texels: rgb = the colour of texel i at rgb[i*rgb_stride + c], c = 0, 1, 2 (3 <= rgb_stride <= 1024 elements: the field's
+ *   [., 4] rows are read in place), in the renderer's range [-1, 1]; owner int32 [texels]; fill = a HOST pointer to 3 bytes -> image uint8
+ *   [texels,3].  A call may cover any run of texels (the pointers offset alike).  owner >= 0, in fp32:  k = c * 0.5 + 0.5;  if not (k > 0)
+ *   then k = 0 (so does a NaN);  if k > 1 then k = 1;  byte = (uint8)rintf(k * 255) (round half to even).  owner < 0: byte_c = fill_c.
+ *
+ * tdgp_mesh_sample_texture: tri int32 [rays], status int32 [rays], t_hit [rays] as tdgp_mesh_resolve wrote them, ray_o / ray_d [rays,3], the
+ *   mesh, image uint8 [H,W,3], (n, r, W, H) its atlas, filter 0 (nearest) | 1 (bilinear) -> colour fp32 [rays,3] in [0, 1], what
+ *   tdgp_mesh_shade takes in mode 2.  A ray with status != 1, or a triangle k outside [0, T) or with an index outside [0, V): colour = 0.
+ *   Otherwise x_c = o_c + d_c * t_hit (fp32, as tdgp_mesh_resolve forms it);  b0, b1, b2 EXACTLY tdgp_mesh_resolve's colour weights (one
+ *   __device__ function, csrc/mesh_bary.h, serves all three kernels: they are clamped onto the triangle);  in double  u = b1 * (n-1),
+ *   v = b2 * (n-1);  the tile coordinates are (tx, ty) = (u, v) for a lower (k even) and ((S-1) - u, (S-1) - v) for an upper triangle,
+ *   each then brought into [0, S-1]: if not (tx >= 0) then tx = 0 (so does a NaN); if tx > S-1 then tx = S-1.  The tile is k / 2.
+ *   nearest: x = rint(tx), y = rint(ty) (round half to even);  colour_c = (float)((double)byte(X0 + x, Y0 + y, c) / 255).
+ *   bilinear: x0 = floor(tx), y0 = floor(ty);  fx = tx - x0, fy = ty - y0;  x1 = min(x0 + 1, S-1), y1 = min(y0 + 1, S-1) (the tap index is
+ *   clamped to the tile);  gx = 1 - fx, gy = 1 - fy;  w00 = gx*gy, w10 = fx*gy, w01 = gx*fy, w11 = fx*fy;  t_ij = (double)byte(X0 + x_i,
+ *   Y0 + y_j, c);  colour_c = (float)(((w00*t00 + w10*t10) + (w01*t01 + w11*t11)) / 255).
+ * --------------------------------------------------------------------------------------------- */
+int     tdgp_atlas_points(const float* vertices, int64_t V, const int32_t* triangles, int64_t T, int n, int r, int W, int H, float* points,
+                          int32_t* owner, tdgp_stream_t stream);
+int     tdgp_atlas_texels(const float* rgb, int64_t rgb_stride, const int32_t* owner, int64_t texels, const uint8_t* fill, uint8_t* image,
+                          tdgp_stream_t stream);
+int     tdgp_mesh_sample_texture(const int32_t* tri, const int32_t* status, const float* t_hit, const float* ray_o, const float* ray_d,
+                                 int64_t rays, const float* vertices, int64_t V, const int32_t* triangles, int64_t T, const uint8_t* image,
+                                 int n, int r, int W, int H, int filter, float* colour, tdgp_stream_t stream);
+
 /* Exact order statistics without a sort: the quantile behind the marchers' `cut_quantile` option (tri_plane_renderer.py:324-326, 366-368:
  * torch.quantile of the activated densities; the non-flatness score renders with 0.5, non_flatness_score.py:9-11).
  * out3[0] = sorted(x)[k_lo] and out3[1] = sorted(x)[k_hi], exact bits; out3[2] = torch.lerp(out3[0], out3[1], weight), i.e.

@@ -66,6 +66,9 @@ def build_parser():
     p.add_argument('--simplify-max-triangles', type=int, default=argparse.SUPPRESS, metavar='N',
                    help='simplify with the first cell of the ladder 1, 1.41, 2, ... voxels that leaves at most N triangles')
     p.add_argument('--simplify-placement', choices=['quadric', 'mean'], default=argparse.SUPPRESS, help='where a cell puts its vertex (default quadric)')
+    # and the texture (mesh_texture.py): a per-triangle atlas baked from the field on the final mesh, written next to the .obj
+    p.add_argument('--texture-texels', type=int, default=argparse.SUPPRESS, metavar='N',
+                   help='bake a texture of N texels per triangle leg (2..64) and write NAME.obj with vt lines, NAME.mtl and NAME.png (needs --save-obj; default: none)')
     return p
 
 
@@ -107,9 +110,20 @@ def simplify_options(args):
     return opts
 
 
+def texture_options(args):
+    """The `texture` argument of geometry.extract_geometry from the command line: None unless --texture-texels asks for it."""
+    texels = getattr(args, 'texture_texels', None)
+    return None if texels is None else dict(texels=texels)
+
+
 def parse_args(argv=None):
     p = build_parser()
     args = p.parse_args(argv)
+    if hasattr(args, 'texture_texels'):
+        if not 2 <= args.texture_texels <= 64:
+            p.error(f'--texture-texels takes an integer in [2, 64], got {args.texture_texels}')
+        if not args.save_obj:
+            p.error('--texture-texels writes the texture next to the .obj: it needs --save-obj (a .ply carries no texture coordinates)')
     if hasattr(args, 'simplify_cell') and hasattr(args, 'simplify_max_triangles'):
         p.error('--simplify-cell and --simplify-max-triangles exclude each other')
     if hasattr(args, 'simplify_placement') and simplify_options(args) is None:
@@ -149,23 +163,30 @@ def main(argv=None):
     os.makedirs(args.output_dir, exist_ok=True)
     need_mesh = args.save_obj or args.save_ply
     comp, smooth, with_normals = component_options(args), smooth_options(args), getattr(args, 'vertex_normals', False)
-    simplify = simplify_options(args)
+    simplify, texture = simplify_options(args), texture_options(args)
     for name, w in zip(names, ws.split(1, dim=0)):
         if need_mesh:
             shapes, counts = geometry.extract_geometry(G, w, volume_res=args.volume_res, voxel_origin=args.voxel_origin, cube_size=args.cube_size,
                                                        thresh_value=args.thresh_value, crop='reference', normalize=True, components=comp, smooth=smooth,
-                                                       simplify=simplify, return_counts=True)
+                                                       simplify=simplify, return_counts=True, **({} if texture is None else dict(texture=texture)))
             shape = shapes[0]
             sigma = shape.sigma
             normals = tdgp.mesh_surface.vertex_normals(shape.vertices, shape.triangles) if with_normals else None
             if args.save_obj:
-                geometry.save_obj(os.path.join(args.output_dir, f'{name}.obj'), shape.vertices, shape.triangles, normals=normals)
+                if texture is not None and shape.triangles.shape[0] > 0:
+                    geometry.save_obj(os.path.join(args.output_dir, f'{name}.obj'), shape.vertices, shape.triangles, normals=normals, texture=shape.texture)
+                else:
+                    geometry.save_obj(os.path.join(args.output_dir, f'{name}.obj'), shape.vertices, shape.triangles, normals=normals)
             if args.save_ply:
                 geometry.save_ply(os.path.join(args.output_dir, f'{name}.ply'), shape.vertices, shape.triangles, normals=normals)
             if args.verbose:
                 print(f'{name}: {shape.vertices.shape[0]} vertices, {shape.triangles.shape[0]} triangles')
                 if simplify is not None:
                     print(json.dumps(dict(name=name, simplify=simplify, vertices=counts[0][0], triangles=counts[0][1], triangles_before_simplify=counts[0].triangles_before)))
+                if texture is not None:
+                    atlas = counts[0].atlas
+                    print(json.dumps(dict(name=name, texture_texels=atlas.texels, atlas=[atlas.width, atlas.height], tiles_per_row=atlas.tiles_per_row,
+                                          triangles=counts[0][1])))
                 if comp is not None:
                     # the report measures the raw level set of the grid the shape was cut from (one more marching-cubes pass, verbose runs only)
                     raw_v, raw_t = geometry.marching_cubes(sigma, args.thresh_value)

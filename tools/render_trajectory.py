@@ -13,7 +13,8 @@ the rays and shaded (`--shape-mode shaded | normals | colour`, `--num-refine`, `
 `--vis mesh_grid` / `--vis mesh_strips`: the same layouts of MESH frames -- the surface extracted once per sample (`--volume-res`, `--cube-size`,
 marching cubes at `--level`) and rasterised for every frame; `--mesh-normals face` shades the flat facets, `vertex` interpolates the mesh's own vertex normals, `field` takes the normals from the field;
 `--mesh-smooth-iters N` Taubin-smooths every mesh on the device before it is drawn; `--mesh-simplify-cell X` then clusters its vertices in cells of
-X voxels (quadric placement) and draws the simplified mesh.
+X voxels (quadric placement) and draws the simplified mesh; `--mesh-texture-texels N` bakes a texture of N texels per triangle leg from the field
+on every final mesh and draws the frames in colour mode from it (`--mesh-texture-filter nearest | bilinear`).
 """
 import argparse
 import importlib
@@ -67,6 +68,15 @@ class _Parser(argparse.ArgumentParser):
                 self.error('--mesh-simplify-cell needs --vis mesh_grid or mesh_strips')
             if not 0 < a.mesh_simplify_cell < float('inf'):
                 self.error(f'--mesh-simplify-cell takes a positive finite number, got {a.mesh_simplify_cell}')
+        if a.mesh_texture_texels is not None or a.mesh_texture_filter is not None:
+            if not a.vis.startswith('mesh_'):
+                self.error('--mesh-texture-texels and --mesh-texture-filter need --vis mesh_grid or mesh_strips')
+            if a.mesh_texture_texels is None:
+                self.error('--mesh-texture-filter needs --mesh-texture-texels')
+            if not 2 <= a.mesh_texture_texels <= 64:
+                self.error(f'--mesh-texture-texels takes an integer in [2, 64], got {a.mesh_texture_texels}')
+            if a.mesh_normals == 'field':
+                self.error('--mesh-texture-texels draws with face or vertex normals (--mesh-normals field takes its colour from the field)')
         if a.mesh_smooth_iters < 0:
             self.error(f'--mesh-smooth-iters takes a non-negative integer, got {a.mesh_smooth_iters}')
         return a
@@ -108,6 +118,9 @@ def build_parser():
     p.add_argument('--mesh-smooth-iters', type=int, default=0, metavar='N', help='mesh frames: Taubin-smooth each mesh, N lambda | mu iterations (default: none)')
     p.add_argument('--mesh-simplify-cell', type=float, default=None, metavar='X',
                    help='mesh frames: simplify each mesh on the device, one vertex per cell of X voxels, placed by its error quadric (default: none)')
+    p.add_argument('--mesh-texture-texels', type=int, default=None, metavar='N',
+                   help='mesh frames: bake a texture of N texels per triangle leg (2..64) on each final mesh and draw it (implies --shape-mode colour; default: none)')
+    p.add_argument('--mesh-texture-filter', choices=['nearest', 'bilinear'], default=None, help='mesh frames: how the texture is fetched (default bilinear)')
     p.add_argument('--keep-components', type=parse_keep, default=None, metavar='K',
                    help="mesh frames: draw only the K largest connected components of each mesh ('all': no limit; default: the raw level set)")
     p.add_argument('--component-by', choices=['triangles', 'area'], default='triangles', help='mesh frames: what "largest" measures')
@@ -146,10 +159,11 @@ def shape_options(args):
 
 def mesh_options(args):
     """The options of mesh.render_mesh_frames, from the command line."""
-    return dict(level=args.level, volume_res=args.volume_res, cube_size=args.cube_size, mode=args.shape_mode, normals=args.mesh_normals,
+    texture = None if args.mesh_texture_texels is None else dict(texels=args.mesh_texture_texels, filter=args.mesh_texture_filter or 'bilinear')
+    return dict(level=args.level, volume_res=args.volume_res, cube_size=args.cube_size, mode='colour' if texture else args.shape_mode, normals=args.mesh_normals,
                 ambient=args.ambient, background=(args.background,) * 3, plane_batch=args.plane_batch, components=component_options(args),
                 smooth=dict(iterations=args.mesh_smooth_iters) if args.mesh_smooth_iters > 0 else None,
-                simplify=dict(cell=args.mesh_simplify_cell) if args.mesh_simplify_cell is not None else None)
+                simplify=dict(cell=args.mesh_simplify_cell) if args.mesh_simplify_cell is not None else None, **({'texture': texture} if texture else {}))
 
 
 def main(argv=None):
@@ -199,6 +213,9 @@ def main(argv=None):
                     vertices=[v for v, _ in counts], triangles=[t for _, t in counts], components=component_options(args),
                     mesh_smooth_iters=args.mesh_smooth_iters, mesh_simplify_cell=args.mesh_simplify_cell,
                     triangles_before_simplify=[c.triangles_before for c in counts])
+        if args.mesh_texture_texels is not None:
+            line.update(shape_mode='colour', mesh_texture_texels=args.mesh_texture_texels, mesh_texture_filter=args.mesh_texture_filter or 'bilinear',
+                        atlas=[[c.atlas.width, c.atlas.height] for c in counts])
     print(json.dumps(line))
 
 
