@@ -80,6 +80,9 @@ _PROTOTYPES = {
     'tdgp_mesh_visibility': (c_int, [P, c_int64, P, c_int64, P, P, P, c_int, c_int, c_int, c_float, c_int, P, P]),
     'tdgp_mesh_resolve': (c_int, [P, P, c_int64, P, c_int64, P, P, c_int64, c_float, c_float, P, P, P, P, P, P, P, P]),
     'tdgp_mesh_shade': (c_int, [P, P, P, P, c_int64, c_int, POINTER(c_float), c_float, POINTER(c_float), POINTER(c_float), P, P]),
+    'tdgp_mesh_visibility_ms': (c_int, [P, c_int64, P, c_int64, P, P, c_int, c_int, c_int, c_int, c_float, c_int, P, P]),
+    'tdgp_mesh_resolve_ms': (c_int, [P, P, c_int64, P, c_int64, P, P, c_int, c_int, c_int, c_int, c_float, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     POINTER(c_float), c_float, POINTER(c_float), POINTER(c_float), P, P, P, P, P, P, P]),
     'tdgp_mesh_labels_workspace_bytes': (c_int64, [c_int64, c_int64]),
     'tdgp_mesh_labels': (c_int, [P, c_int64, c_int64, P, P, c_int64, P]),
     'tdgp_mesh_component_ids_workspace_bytes': (c_int64, [c_int64]),

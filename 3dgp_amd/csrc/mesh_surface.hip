@@ -20,7 +20,7 @@
 // no kernel waits for another workgroup.
 #include "common.h"
 #include "device_scan.h"
-#include "mesh_bary.h"
+#include "mesh_hit.h"
 
 namespace {
 
@@ -263,25 +263,12 @@ __global__ __launch_bounds__(MS_BLOCK) void interp_normals_kernel(const int32_t*
 #pragma unroll
     for (int c = 0; c < 3; c++) x[c] = ray_o[ray * 3 + c] + ray_d[ray * 3 + c] * th;
     double a[3], b[3], v0[3], w[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        v0[c] = (double)verts[(int64_t)idx[0] * 3 + c];
-        a[c] = (double)verts[(int64_t)idx[1] * 3 + c] - v0[c];
-        b[c] = (double)verts[(int64_t)idx[2] * 3 + c] - v0[c];
-    }
+    mesh_tri_frame(verts, idx, a, b, v0);
     mesh_bary_weights(a, b, v0, x, w);
-    double m[3];
+    float n[3];
+    if (!mesh_vertex_normal(w, idx, vnormal, n)) return;                       // the face normal tdgp_mesh_resolve wrote stays
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const double n0 = (double)vnormal[(int64_t)idx[0] * 3 + c], n1 = (double)vnormal[(int64_t)idx[1] * 3 + c];
-        const double n2 = (double)vnormal[(int64_t)idx[2] * 3 + c];
-        m[c] = (w[0] * n0 + w[1] * n1) + w[2] * n2;
-    }
-    const double q = (m[0] * m[0] + m[1] * m[1]) + m[2] * m[2];
-    if (!(q > 0.0 && q < (double)__builtin_inff())) return;                    // the face normal tdgp_mesh_resolve wrote stays
-    const double r = sqrt(q);
-#pragma unroll
-    for (int c = 0; c < 3; c++) normal[ray * 3 + c] = (float)(m[c] / r);
+    for (int c = 0; c < 3; c++) normal[ray * 3 + c] = n[c];
 }
 
 inline bool ms_sizes_ok(int64_t T, int64_t V) { return T >= 0 && V >= 0 && T <= MS_T_MAX && V <= (int64_t)INT32_MAX - 1; }

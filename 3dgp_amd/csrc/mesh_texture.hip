@@ -11,7 +11,7 @@
 // ordered comparisons, one writer per element, no atomics, no workspace.  A numpy restatement reproduces all three bit for bit
 // (tests/mesh_texture_reference.py).
 #include "common.h"
-#include "mesh_bary.h"
+#include "mesh_hit.h"
 
 namespace {
 
@@ -78,13 +78,6 @@ __global__ __launch_bounds__(MT_BLOCK) void atlas_texels_kernel(const float* __r
     }
 }
 
-// a tile coordinate brought into [0, S - 1] before it is turned into an index (a NaN goes to 0)
-__device__ __forceinline__ double tile_clamp(double x, double hi) {
-    if (!(x >= 0.0)) x = 0.0;
-    if (x > hi) x = hi;
-    return x;
-}
-
 __global__ __launch_bounds__(MT_BLOCK) void sample_texture_kernel(const int32_t* __restrict__ tri, const int32_t* __restrict__ status, const float* __restrict__ t_hit,
                                                                   const float* __restrict__ ray_o, const float* __restrict__ ray_d, int64_t rays,
                                                                   const float* __restrict__ verts, int64_t V, const int32_t* __restrict__ tris, int64_t T,
@@ -108,54 +101,12 @@ __global__ __launch_bounds__(MT_BLOCK) void sample_texture_kernel(const int32_t*
 #pragma unroll
         for (int c = 0; c < 3; c++) x[c] = ray_o[ray * 3 + c] + ray_d[ray * 3 + c] * th;
         double a[3], b[3], v0[3], w[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            v0[c] = (double)verts[(int64_t)idx[0] * 3 + c];
-            a[c] = (double)verts[(int64_t)idx[1] * 3 + c] - v0[c];
-            b[c] = (double)verts[(int64_t)idx[2] * 3 + c] - v0[c];
-        }
+        mesh_tri_frame(verts, idx, a, b, v0);
         mesh_bary_weights(a, b, v0, x, w);                              // shared with tdgp_mesh_resolve and tdgp_mesh_interp_normals (mesh_bary.h)
-        const int S = n + 2;
-        const double m = (double)(n - 1), hi = (double)(S - 1);
-        const double u = w[1] * m, v = w[2] * m;
-        const bool upper = (k & 1) != 0;
-        const double tx = tile_clamp(upper ? hi - u : u, hi), ty = tile_clamp(upper ? hi - v : v, hi);
-        const int tile = k >> 1;
-        const int trow = tile / r;
-        const int64_t X0 = (int64_t)(tile - trow * r) * S, Y0 = (int64_t)trow * S;
-        const uint8_t* base = image + (Y0 * W + X0) * 3;
-        if (filter == 0) {
-            const int x0 = (int)rint(tx), y0 = (int)rint(ty);
-            const uint8_t* t00 = base + ((int64_t)y0 * W + x0) * 3;
-#pragma unroll
-            for (int c = 0; c < 3; c++) out[c] = (float)((double)t00[c] / 255.0);
-        } else {
-            const double fx0 = floor(tx), fy0 = floor(ty);
-            const double fx = tx - fx0, fy = ty - fy0;
-            const int x0 = (int)fx0, y0 = (int)fy0;
-            const int x1 = min(x0 + 1, S - 1), y1 = min(y0 + 1, S - 1);
-            const double gx = 1.0 - fx, gy = 1.0 - fy;
-            const double w00 = gx * gy, w10 = fx * gy, w01 = gx * fy, w11 = fx * fy;
-            const uint8_t* t00 = base + ((int64_t)y0 * W + x0) * 3;
-            const uint8_t* t10 = base + ((int64_t)y0 * W + x1) * 3;
-            const uint8_t* t01 = base + ((int64_t)y1 * W + x0) * 3;
-            const uint8_t* t11 = base + ((int64_t)y1 * W + x1) * 3;
-#pragma unroll
-            for (int c = 0; c < 3; c++)
-                out[c] = (float)(((w00 * (double)t00[c] + w10 * (double)t10[c]) + (w01 * (double)t01[c] + w11 * (double)t11[c])) / 255.0);
-        }
+        mesh_texture_fetch(w, k, image, n, r, W, filter, out);          // shared with tdgp_mesh_resolve_ms (mesh_hit.h)
     }
 #pragma unroll
     for (int c = 0; c < 3; c++) colour[ray * 3 + c] = out[c];
-}
-
-// the layout of tdgp.h from (T, n): -> false when (r, W, H) are not the atlas of T triangles at n texels
-inline bool atlas_is(int64_t T, int n, int r, int W, int H) {
-    const int64_t S = n + 2, P = (T + 1) / 2;
-    int64_t rr = 0;
-    while (rr * rr < P) rr++;
-    const int64_t rows = rr == 0 ? 0 : (P + rr - 1) / rr;
-    return (int64_t)r == rr && (int64_t)W == rr * S && (int64_t)H == rows * S;
 }
 
 // shared argument checks of the three entry points; `what` names the caller in the message

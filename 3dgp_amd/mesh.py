@@ -12,7 +12,12 @@ from the per-triangle atlas baked from the field (tdgp_mesh_sample_texture betwe
 The arithmetic of the three kernels is fixed operation by operation (include/tdgp.h); the minimum does not depend on the order of its
 operands, so frames are the same bytes on every run, under every permutation of the triangles and every chunking of the cameras.  Limits:
 no clipping at the near plane (a triangle with a vertex nearer than `near` is dropped whole: the cameras sit outside the cube), one mesh per
-call, no anti-aliasing.  GPU only: the kernels have no CPU path.
+call.  GPU only: the kernels have no CPU path.
+
+Anti-aliasing: `samples=4 | 16` decides coverage at 4 or 16 fixed sub-pixel positions per pixel in one pass --
+tdgp_mesh_visibility_ms (one 8-byte key per sample, no ray table) -> tdgp_mesh_resolve_ms (every sample resolved and shaded with the
+per-hit bodies of the one-sample kernels, averaged per pixel) -- and returns the covered fraction of every pixel.  The 16-sample pattern is
+an ordered grid; normals from the field are not supersampled.
 """
 import numpy as np
 import torch
@@ -135,9 +140,105 @@ def mesh_shade(normal, status, ray_d, colour=None, mode='shaded', light=None, am
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# the two multisample kernels on tensors
+# ----------------------------------------------------------------------------------------------------------------------
+# offsets (ox, oy) of the samples from the pixel centre in 1/256 pixel, x to the right and y down, in sample order (include/tdgp.h)
+SAMPLE_PATTERNS = {4: ((-32, -96), (96, -32), (-96, 32), (32, 96)),
+                   16: tuple((ox, oy) for oy in (-96, -32, 32, 96) for ox in (-96, -32, 32, 96))}
+SAMPLES = (1,) + tuple(SAMPLE_PATTERNS)
+
+
+def _check_samples_ms(samples):
+    if samples not in SAMPLE_PATTERNS:
+        raise ValueError(f'samples must be one of {sorted(SAMPLE_PATTERNS)} here (one sample per pixel is mesh_visibility / mesh_resolve), got {samples!r}')
+    return int(samples)
+
+
+def _check_cameras_ms(what, c2w, focal, resolution):
+    w, h = (int(resolution), int(resolution)) if np.isscalar(resolution) else (int(r) for r in resolution)
+    _lib.require_cuda(c2w, 'c2w')
+    c2w, focal = _lib.f32c(c2w), _lib.f32c(focal)
+    C = int(c2w.shape[0]) if c2w.ndim == 3 else -1
+    if tuple(c2w.shape) != (C, 4, 4) or focal.numel() != C:
+        raise ValueError(f'{what}: c2w [C,4,4] and focal [C] expected, got {tuple(c2w.shape)}, {tuple(focal.shape)}')
+    return c2w, focal, C, h, w
+
+
+def mesh_visibility_ms(vertices, triangles, c2w, focal, resolution, samples, near=1e-3, cull='none'):
+    """tdgp_mesh_visibility_ms: vertices [V,3] fp32 (world), triangles [T,3] int32, c2w [C,4,4], focal [C] -> vis int64 [C,h*w,samples] (the
+    kernel's uint64 keys, one per sample of SAMPLE_PATTERNS[samples]: -1 is an empty sample, otherwise (bits(t) << 32) | triangle).  No ray
+    table is read: the ray of a sample follows from its position.  resolution: (w, h) as `sample_rays` takes it."""
+    if cull not in CULL:
+        raise ValueError(f'cull must be one of {sorted(CULL)}, got {cull!r}')
+    S = _check_samples_ms(samples)
+    vertices, triangles = _check_mesh(vertices, triangles)
+    c2w, focal, C, h, w = _check_cameras_ms('mesh_visibility_ms', c2w, focal, resolution)
+    if not float(near) > 0.0:
+        raise ValueError(f'near must be positive, got {near!r}')
+    vis = torch.empty([C, h * w, S], dtype=torch.int64, device=vertices.device)
+    with torch.cuda.device(vertices.device):
+        _lib.call('tdgp_mesh_visibility_ms', vertices.data_ptr(), vertices.shape[0], triangles.data_ptr(), triangles.shape[0], c2w.data_ptr(), focal.data_ptr(),
+                  C, h, w, S, float(near), CULL[cull], vis.data_ptr(), _lib.stream_of(vertices))
+    return vis
+
+
+def mesh_resolve_ms(vis, vertices, triangles, c2w, focal, resolution, t_miss, vertex_normals=None, vertex_rgb=None, texture=None, texture_filter='bilinear',
+                    mode='shaded', light=None, ambient=0.2, albedo=(0.8, 0.8, 0.8), background=(1.0, 1.0, 1.0)):
+    """tdgp_mesh_resolve_ms: vis int64 [C,h*w,S] of `mesh_visibility_ms` -> (rgb [C*h*w,3], coverage [C*h*w], status int32 [C*h*w], depth
+    [C*h*w], tri int32 [C*h*w], normal [C*h*w,3]).  Every sample is resolved and shaded as a ray of `mesh_resolve` (+ `interp_normals` with
+    vertex_normals [V,3], + `sample_texture` with a texture) -> `mesh_shade` would be; rgb is the mean of the S colours, a miss counting as
+    `background`; coverage the fraction of samples that hit; depth, tri and normal those of the nearest hit sample (t_miss, -1, 0 without one).
+    mode 'colour' takes vertex_rgb [V,3] in [0, 1] or a `mesh_texture.Texture`, not both."""
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
+    if texture_filter not in _mesh_texture.FILTERS:
+        raise ValueError(f'texture_filter must be one of {sorted(_mesh_texture.FILTERS)}, got {texture_filter!r}')
+    vertices, triangles = _check_mesh(vertices, triangles)
+    c2w, focal, C, h, w = _check_cameras_ms('mesh_resolve_ms', c2w, focal, resolution)
+    _lib.require_cuda(vis, 'vis')
+    if vis.dtype != torch.int64 or vis.ndim != 3 or tuple(vis.shape[:2]) != (C, h * w) or vis.shape[2] not in SAMPLE_PATTERNS:
+        raise ValueError(f'vis must be the int64 [{C}, {h * w}, 4 or 16] tensor mesh_visibility_ms returns, got {vis.dtype} {tuple(vis.shape)}')
+    vis, S = vis.contiguous(), int(vis.shape[2])
+    if vertex_rgb is not None and texture is not None:
+        raise ValueError('the colour comes from vertex_rgb or from the texture, not both')
+    if mode == 'colour' and vertex_rgb is None and texture is None:
+        raise ValueError("mode 'colour' needs vertex_rgb [V,3] or a texture")
+    for t, what in ((vertex_normals, 'vertex_normals'), (vertex_rgb, 'vertex_rgb')):
+        if t is not None:
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != tuple(vertices.shape):
+                raise ValueError(f'{what} must be fp32 {tuple(vertices.shape)}, got {getattr(t, "dtype", type(t).__name__)} {tuple(getattr(t, "shape", ()))}')
+            _lib.require_cuda(t, what)
+    vertex_normals = None if vertex_normals is None else vertex_normals.contiguous()
+    vertex_rgb = None if vertex_rgb is None else vertex_rgb.contiguous()
+    image, atlas = None, _mesh_texture.Atlas(0, 0, 0, 0, 0)
+    if texture is not None:
+        atlas = _mesh_texture._check_texture(texture, int(triangles.shape[0]))
+        _lib.require_cuda(texture.image, 'texture.image')
+        image = texture.image.contiguous()
+    dev, P = vertices.device, C * h * w
+    rgb = torch.empty([P, 3], dtype=torch.float32, device=dev)
+    coverage = torch.empty([P], dtype=torch.float32, device=dev)
+    status = torch.empty([P], dtype=torch.int32, device=dev)
+    depth = torch.empty([P], dtype=torch.float32, device=dev)
+    tri = torch.empty([P], dtype=torch.int32, device=dev)
+    normal = torch.empty([P, 3], dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call('tdgp_mesh_resolve_ms', vis.data_ptr(), vertices.data_ptr(), vertices.shape[0], triangles.data_ptr(), triangles.shape[0], c2w.data_ptr(),
+                  focal.data_ptr(), C, h, w, S, float(t_miss), _lib.ptr(vertex_normals), _lib.ptr(vertex_rgb), _lib.ptr(image), atlas.texels, atlas.tiles_per_row,
+                  atlas.width, atlas.height, _mesh_texture.FILTERS[texture_filter], MODES[mode], None if light is None else _shapes._vec3(light, 'light'),
+                  float(ambient), _shapes._vec3(albedo, 'albedo'), _shapes._vec3(background, 'background'), rgb.data_ptr(), coverage.data_ptr(),
+                  status.data_ptr(), depth.data_ptr(), tri.data_ptr(), normal.data_ptr(), _lib.stream_of(vertices))
+    return rgb, coverage, status, depth, tri, normal
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # frames
 # ----------------------------------------------------------------------------------------------------------------------
-def _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_call, vertex_normals=None, texture=None, texture_filter='bilinear'):
+def _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_call, vertex_normals=None, texture=None, texture_filter='bilinear', samples=1):
+    if isinstance(samples, bool) or samples not in SAMPLES:
+        raise ValueError(f'samples must be one of {SAMPLES}, got {samples!r}')
+    if samples > 1 and normals == 'field':
+        raise ValueError("samples > 1 renders with normals='face' or 'vertex': normals='field' evaluates the field once per pixel and is not supersampled")
     if mode not in MODES:
         raise ValueError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
     if normals not in NORMALS:
@@ -181,7 +282,7 @@ def vertex_colours(G, planes, vertices, points_per_call=2 ** 22):
 @torch.no_grad()
 def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shaded', normals='face', cull='none', near=None, planes=None, G=None,
                       vertex_colours=None, light=None, ambient=0.2, albedo=(0.8, 0.8, 0.8), background=(1.0, 1.0, 1.0), max_rays_per_call=None,
-                      t_miss=None, step=None, vertex_normals=None, texture=None, texture_filter='bilinear'):
+                      t_miss=None, step=None, vertex_normals=None, texture=None, texture_filter='bilinear', samples=1):
     """C frames of ONE mesh (vertices [V,3] fp32 in world units, triangles [T,3] int32, on the device) under C cameras (`camera_params`: angles,
     radius, look_at, fov as the renderer takes them) at `resolution` (a side, or (w, h)).
 
@@ -200,8 +301,14 @@ def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shad
     texture with normals='field', or with another mode, is a ValueError.
     cull: 'none' | 'back' | 'front'.  near (default cfg.ray_start with a generator, else 1e-3): a triangle with a vertex nearer is dropped whole.
     Cameras are taken in chunks of whole frames, max_rays_per_call rays at most (default 16 frames; never less than one frame): they are
-    independent, so the chunking does not change a byte."""
-    _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_call, vertex_normals, texture, texture_filter)
+    independent, so the chunking does not change a byte.
+    samples: 1 (one point sample at the pixel centre: the route above), 4 (a rotated grid) or 16 (the 4 x 4 grid) coverage samples per pixel
+    (SAMPLE_PATTERNS), with face or vertex normals.  Every sample is visible, resolved and shaded on its own ray, in two launches per chunk
+    (tdgp_mesh_visibility_ms -> tdgp_mesh_resolve_ms, 8 bytes per sample between them): rgb is the mean of the sample colours over
+    `background`, and the group gains coverage [C,R], the fraction of the pixel's samples the mesh covers (composite another background B as
+    rgb + (1 - coverage) * (B - background)).  status is 1 where any sample hit; depth, tri and normal are those of the nearest hit sample.  The
+    frame stays on the pixel grid of the one-sample frame and of the renderer's frames of the same cameras.  The chunks shrink by `samples`."""
+    _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_call, vertex_normals, texture, texture_filter, samples)
     if normals == 'vertex' and isinstance(vertices, torch.Tensor) and isinstance(triangles, torch.Tensor) and not (vertices.is_cuda and triangles.is_cuda):
         # this mode is an option of a device mesh only (its corner table is built there): asking for it on a host mesh is a bad option value
         raise ValueError(f"normals='vertex' takes a mesh on the GPU (got {vertices.device}, {triangles.device}); the vertex normals have no CPU path")
@@ -220,7 +327,8 @@ def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shad
     c2w = _renderer.compute_cam2world_matrix(camera_params)
     C = int(c2w.shape[0])
     focal = focal_lengths(get('fov'), C, dev)
-    ray_o, ray_d = _renderer.sample_rays(c2w, fov=get('fov'), resolution=(w, h))
+    if samples == 1:
+        ray_o, ray_d = _renderer.sample_rays(c2w, fov=get('fov'), resolution=(w, h))
     field = normals == 'field'
     if field:
         if G.synthesis.training:
@@ -239,11 +347,20 @@ def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shad
     if not field and mode == 'colour' and texture is None:
         vrgb = vertex_colours if vertex_colours.dtype == torch.float32 else vertex_colours.float() / (255.0 if vertex_colours.dtype == torch.uint8 else 1.0)
     max_rays = 16 * R if max_rays_per_call is None else int(max_rays_per_call)
-    cstep = max(1, min(max_rays, FIELD_POINTS_MAX // STENCIL) // R)
+    cstep = max(1, min(max_rays, FIELD_POINTS_MAX // STENCIL) // (R * samples))
     out = _renderer.Gather(C, R)
     for c0 in range(0, C, cstep):
         cs = slice(c0, min(c0 + cstep, C))
         n = (cs.stop - cs.start) * R
+        if samples > 1:
+            vis = mesh_visibility_ms(vertices, triangles, c2w[cs], focal[cs], (w, h), samples, near=near, cull=cull)
+            rgb, coverage, status, t_hit, tri, normal = mesh_resolve_ms(vis, vertices, triangles, c2w[cs], focal[cs], (w, h), t_miss, vertex_normals=vnorm,
+                                                                        vertex_rgb=vrgb, texture=texture, texture_filter=texture_filter, mode=mode,
+                                                                        light=light, ambient=ambient, albedo=albedo, background=background)
+            k = cs.stop - cs.start
+            out.put(cs, slice(0, R), rgb=rgb.reshape(k, R, 3), depth=t_hit.reshape(k, R, 1), normal=normal.reshape(k, R, 3), status=status.reshape(k, R),
+                    tri=tri.reshape(k, R), coverage=coverage.reshape(k, R))
+            continue
         o, d = ray_o[cs].reshape(n, 3), ray_d[cs].reshape(n, 3)
         vis = mesh_visibility(vertices, triangles, c2w[cs], focal[cs], d, (w, h), near=near, cull=cull)
         t_hit, status, tri, normal, colour, points = mesh_resolve(vis.reshape(n), vertices, triangles, o, d, step, t_miss, vertex_rgb=vrgb)
@@ -261,7 +378,10 @@ def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shad
                 tri=tri.reshape(k, R))
     if C == 0:
         e = lambda *s, dt=torch.float32: torch.empty([0, R, *s], dtype=dt, device=dev)      # noqa: E731
-        return TensorGroup(rgb=e(3), depth=e(1), normal=e(3), status=e(dt=torch.int32), tri=e(dt=torch.int32))
+        return TensorGroup(rgb=e(3), depth=e(1), normal=e(3), status=e(dt=torch.int32), tri=e(dt=torch.int32), **(dict(coverage=e()) if samples > 1 else {}))
+    if samples > 1:
+        rgb, depth, normal, status, tri, coverage = out.result()
+        return TensorGroup(rgb=rgb, depth=depth, normal=normal, status=status, tri=tri, coverage=coverage)
     rgb, depth, normal, status, tri = out.result()
     return TensorGroup(rgb=rgb, depth=depth, normal=normal, status=status, tri=tri)
 
@@ -295,7 +415,8 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
     from the planes in hand on its FINAL world-space mesh -- after components, smoothing, simplification and `grid_to_world` -- and the frames
     take their colour from it (mode='colour', face or vertex normals) instead of the vertex colours; every count's `.atlas` is then the sample's
     `mesh_texture.Atlas` (None without a texture).
-    kw: cull, near, light, ambient, albedo, background, max_rays_per_call, t_miss, step of `render_mesh_views`."""
+    kw: cull, near, light, ambient, albedo, background, max_rays_per_call, t_miss, step, samples of `render_mesh_views` (samples=4 | 16: multisampled
+    frames, and the group gains `coverage`; the grids and strips below take it the same way)."""
     syn, cfg = G.synthesis, G.cfg
     num_samples = len(ws)
     get = _renderer.cam_get(camera_params)
@@ -303,7 +424,7 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
     if int(plane_batch) < 1:
         raise ValueError(f'plane_batch must be positive, got {plane_batch!r}')
     bake_kw, tex_filter = (None, 'bilinear') if texture is None else _mesh_texture.check_options(texture)
-    _check_options(mode, normals, kw.get('cull', 'none'), True, G, True, kw.get('max_rays_per_call'), None, texture, tex_filter)
+    _check_options(mode, normals, kw.get('cull', 'none'), True, G, True, kw.get('max_rays_per_call'), None, texture, tex_filter, kw.get('samples', 1))
     if syn.training:
         raise RuntimeError('render_mesh_frames is the inference route: call .eval() first (training mode renders patches with density noise)')
     _lib.require_cuda(ws, 'ws')

@@ -601,6 +601,49 @@ int tdgp_mesh_shade(const float* normal, const int32_t* status, const float* ray
                     const float* light, float ambient, const float* albedo, const float* background, float* rgb, tdgp_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Multisampled mesh frames (csrc/mesh_raster.hip, csrc/mesh_hit.h): S = 4 or 16 coverage samples per pixel in one pass, with the fraction of
+ * a pixel the mesh covers.    tdgp_mesh_visibility_ms -> tdgp_mesh_resolve_ms        (two launches and 8 bytes per sample between them)
+ * The rules of the mesh frames above hold unchanged: the arithmetic contract, the checks, the empty inputs, the one order-free atomic.
+ * THE PATTERNS, offsets (ox, oy) from the pixel centre in 1/256 pixel, x to the right and y down, in sample order:
+ *   S = 4  (a rotated grid):  (-32,-96), (96,-32), (-96,32), (32,96).
+ *   S = 16 (the 4 x 4 grid):  ox = -96 + 64*(j % 4),  oy = -96 + 64*(j / 4).
+ *   Sample j of pixel (row, col) sits at the integer position (sx, sy) = (256 col + ox_j, 256 row + oy_j).  Any other S is TDGP_EINVAL.
+ * THE RAY OF A SAMPLE (double), the projection of tdgp_mesh_visibility inverted -- no ray table is read:
+ *   u = (((double)sx / (256 * ((w-1)*0.5))) - 1) / focal;   v = (1 - ((double)sy / (256 * ((h-1)*0.5)))) / focal;   len = sqrt((u*u + v*v) + 1).
+ *   Its origin is the camera's position o_c = m[c][3]; its direction d_c = (float)(((u*m[c][0] + v*m[c][1]) + (double)(-m[c][2])) / len).
+ *
+ * tdgp_mesh_visibility_ms: the mesh, c2w [C,4,4], focal [C] -> vis uint64 [C,h*w,S], first set to all ones.  C*h*w*S <= 2^30, C*T <= 2^38.
+ *   Per (camera, triangle): the vertices, the culls, the near test, area2 and s EXACTLY as tdgp_mesh_visibility, once for all S samples.
+ *   For every sample position P = (sx, sy) of the frame inside the triangle's box (min X <= sx <= max X, min Y <= sy <= max Y): e_i at P, the
+ *   cover test with the top-left rule and depth as tdgp_mesh_visibility writes them;   t = (float)(depth * len);   not (t > 0 and t < inf):
+ *   skipped;   key = ((uint64)bits(t) << 32) | (uint32)k;   vis[pixel][j] = min(vis[pixel][j], key).
+ *   Work shape: one lane per (camera, triangle).  The positions of the 16-pattern form one regular lattice of pitch 64 (four per pixel each
+ *   way), those of the 4-pattern one per pixel on each of its four rows: a lane walks the lattice box of its triangle -- the work of
+ *   tdgp_mesh_visibility at 4x (2x) the resolution, not S tests per touched pixel -- and a box wider or taller than 8 candidates is handed
+ *   to the wave, as in tdgp_mesh_visibility.
+ *
+ * tdgp_mesh_resolve_ms: vis [C,h*w,S], the mesh, c2w, focal, vertex_normal [V,3] or NULL (face normals), vertex_rgb [V,3] or NULL, image
+ *   uint8 [H,W,3] or NULL with (n, r, W, H) its atlas and filter as tdgp_mesh_sample_texture takes them (at most one of vertex_rgb and image;
+ *   mode 2 needs one), mode / light / ambient / albedo / background as tdgp_mesh_shade (HOST pointers) -> rgb [C*h*w,3], coverage [C*h*w],
+ *   status int32 [C*h*w], depth [C*h*w], tri int32 [C*h*w], normal [C*h*w,3].  One lane per sample, no per-sample buffer.  Per sample j:
+ *   a miss (tdgp_mesh_resolve's rule on the key): colour_j = background.  A hit: t = the float in the high word, x_c = o_c + d_c * t (fp32);
+ *   n = tdgp_mesh_resolve's face normal (its fallback reads this d);  with vertex_normal: b0, b1, b2 of tdgp_mesh_resolve at x and
+ *   tdgp_mesh_interp_normals' normal, the face normal staying where that one leaves it;  mode 2: tdgp_mesh_resolve's colour from vertex_rgb,
+ *   or tdgp_mesh_sample_texture's from the image, at the same weights;  colour_j = tdgp_mesh_shade's out for (n, d, colour).
+ *   Each of those is ONE __device__ function (csrc/mesh_hit.h, mesh_bary.h, shade.h) compiled into the one-sample kernels and into this one.
+ *   Per pixel:  rgb_c = (float)(((..((0.0 + (double)colour_0c) + (double)colour_1c) ..) + (double)colour_(S-1)c) / (double)S);
+ *   coverage = (float)hits / (float)S (exact: S is a power of two);  status = hits > 0;  depth, tri, normal = t, k, n of the hit sample with
+ *   the smallest t (fp32 `<`, a tie goes to the lower sample index);  no hit: depth = t_miss, tri = -1, normal = 0.
+ * --------------------------------------------------------------------------------------------- */
+int tdgp_mesh_visibility_ms(const float* vertices, int64_t V, const int32_t* triangles, int64_t T, const float* c2w, const float* focal, int C,
+                            int h, int w, int samples, float near_, int cull, uint64_t* vis, tdgp_stream_t stream);
+int tdgp_mesh_resolve_ms(const uint64_t* vis, const float* vertices, int64_t V, const int32_t* triangles, int64_t T, const float* c2w,
+                         const float* focal, int C, int h, int w, int samples, float t_miss, const float* vertex_normal, const float* vertex_rgb,
+                         const uint8_t* image, int n, int r, int W, int H, int filter, int mode, const float* light, float ambient,
+                         const float* albedo, const float* background, float* rgb, float* coverage, int32_t* status, float* depth, int32_t* tri,
+                         float* normal, tdgp_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Mesh components (csrc/mesh_components.hip; the reference's users split the mesh on the host with trimesh): connected components of the
  * indexed mesh tdgp_mcubes_emit leaves on the device, per-component measurements, and an order-preserving filter.
  *   tdgp_mesh_labels -> tdgp_mesh_component_ids -> tdgp_mesh_component_stats (+ a stable sort by the caller) -> tdgp_mesh_component_sums

@@ -14,7 +14,8 @@ the rays and shaded (`--shape-mode shaded | normals | colour`, `--num-refine`, `
 marching cubes at `--level`) and rasterised for every frame; `--mesh-normals face` shades the flat facets, `vertex` interpolates the mesh's own vertex normals, `field` takes the normals from the field;
 `--mesh-smooth-iters N` Taubin-smooths every mesh on the device before it is drawn; `--mesh-simplify-cell X` then clusters its vertices in cells of
 X voxels (quadric placement) and draws the simplified mesh; `--mesh-texture-texels N` bakes a texture of N texels per triangle leg from the field
-on every final mesh and draws the frames in colour mode from it (`--mesh-texture-filter nearest | bilinear`).
+on every final mesh and draws the frames in colour mode from it (`--mesh-texture-filter nearest | bilinear`); `--mesh-samples 4 | 16` draws the
+frames with 4 or 16 coverage samples per pixel (anti-aliased silhouettes; face or vertex normals).
 """
 import argparse
 import importlib
@@ -77,6 +78,11 @@ class _Parser(argparse.ArgumentParser):
                 self.error(f'--mesh-texture-texels takes an integer in [2, 64], got {a.mesh_texture_texels}')
             if a.mesh_normals == 'field':
                 self.error('--mesh-texture-texels draws with face or vertex normals (--mesh-normals field takes its colour from the field)')
+        if a.mesh_samples is not None:
+            if not a.vis.startswith('mesh_'):
+                self.error('--mesh-samples needs --vis mesh_grid or mesh_strips')
+            if a.mesh_samples > 1 and a.mesh_normals == 'field':
+                self.error('--mesh-samples 4 | 16 draws with face or vertex normals (--mesh-normals field is evaluated once per pixel)')
         if a.mesh_smooth_iters < 0:
             self.error(f'--mesh-smooth-iters takes a non-negative integer, got {a.mesh_smooth_iters}')
         return a
@@ -121,6 +127,8 @@ def build_parser():
     p.add_argument('--mesh-texture-texels', type=int, default=None, metavar='N',
                    help='mesh frames: bake a texture of N texels per triangle leg (2..64) on each final mesh and draw it (implies --shape-mode colour; default: none)')
     p.add_argument('--mesh-texture-filter', choices=['nearest', 'bilinear'], default=None, help='mesh frames: how the texture is fetched (default bilinear)')
+    p.add_argument('--mesh-samples', type=int, choices=[1, 4, 16], default=None, metavar='S',
+                   help='mesh frames: coverage samples per pixel, 1 | 4 | 16 (default 1: one point sample at the pixel centre)')
     p.add_argument('--keep-components', type=parse_keep, default=None, metavar='K',
                    help="mesh frames: draw only the K largest connected components of each mesh ('all': no limit; default: the raw level set)")
     p.add_argument('--component-by', choices=['triangles', 'area'], default='triangles', help='mesh frames: what "largest" measures')
@@ -163,7 +171,8 @@ def mesh_options(args):
     return dict(level=args.level, volume_res=args.volume_res, cube_size=args.cube_size, mode='colour' if texture else args.shape_mode, normals=args.mesh_normals,
                 ambient=args.ambient, background=(args.background,) * 3, plane_batch=args.plane_batch, components=component_options(args),
                 smooth=dict(iterations=args.mesh_smooth_iters) if args.mesh_smooth_iters > 0 else None,
-                simplify=dict(cell=args.mesh_simplify_cell) if args.mesh_simplify_cell is not None else None, **({'texture': texture} if texture else {}))
+                simplify=dict(cell=args.mesh_simplify_cell) if args.mesh_simplify_cell is not None else None, **({'texture': texture} if texture else {}),
+                **({'samples': args.mesh_samples} if (args.mesh_samples or 1) > 1 else {}))
 
 
 def main(argv=None):
@@ -212,7 +221,7 @@ def main(argv=None):
         line.update(level=args.level, shape_mode=args.shape_mode, volume_res=args.volume_res, cube_size=args.cube_size, mesh_normals=args.mesh_normals,
                     vertices=[v for v, _ in counts], triangles=[t for _, t in counts], components=component_options(args),
                     mesh_smooth_iters=args.mesh_smooth_iters, mesh_simplify_cell=args.mesh_simplify_cell,
-                    triangles_before_simplify=[c.triangles_before for c in counts])
+                    triangles_before_simplify=[c.triangles_before for c in counts], mesh_samples=args.mesh_samples or 1)
         if args.mesh_texture_texels is not None:
             line.update(shape_mode='colour', mesh_texture_texels=args.mesh_texture_texels, mesh_texture_filter=args.mesh_texture_filter or 'bilinear',
                         atlas=[[c.atlas.width, c.atlas.height] for c in counts])
