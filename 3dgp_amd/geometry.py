@@ -180,62 +180,31 @@ def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_s
     diagonal (`mesh.apply_scale(1.0 / mesh.scale)`, extract_geometry.py:42 -- trimesh's `scale`; no translation).
     units='world': the vertices go through `grid_to_world` with this call's volume_res / voxel_origin / cube_size / crop (and `sheared`)
     instead of `normalize` -- the mesh `mesh.render_mesh_views` takes.
-    components: None (the raw level set), or a dict of `mesh_components.select` keyword arguments (e.g. dict(keep=1)): the marching-cubes
-    output goes through `mesh_components.clean_mesh` BEFORE it is scaled, so `normalize` divides by the diagonal of the cleaned mesh.
-    smooth: None, or a dict of `mesh_surface.smooth` keyword arguments (e.g. dict(iterations=10)): applied after the cleaning and before the
-    scaling, in index units.  Vertex normals are the caller's: `mesh_surface.vertex_normals` of the final vertices.
-    simplify: None, or a dict of `mesh_simplify.simplify` keyword arguments with either `cell` (in voxels: dict(cell=2.0)) or `max_triangles`
-    (dict(max_triangles=100000): the first cell of `mesh_simplify.cell_for_triangles`' ladder that leaves no more): vertex clustering with
-    quadric placement after the smoothing and before the scaling, in index units.  return_counts=True: also a list of `MeshCount` per sample
-    (vertices, triangles; `.triangles_before` the simplification).
-    texture: None (this function as it was: `Shape`s), or a dict(texels=8) (also fill, points_per_call of `mesh_texture.bake`): the planes are
-    computed once per sample and feed both the density grid and the bake; the texture is baked on the `grid_to_world` vertices of the final
-    mesh WHATEVER `units` returns (the field lives in world units), and every item is a TexturedShape(vertices, triangles, sigma, texture)
-    whose `texture` is a `mesh_texture.Texture`; the counts carry its `.atlas`."""
+    components, smooth, simplify, texture: the stages of `mesh_build.check_stages`, run on the marching-cubes output BEFORE it is scaled
+    (`normalize` divides by the diagonal of the finished mesh; vertex normals are the caller's: `mesh_surface.vertex_normals` of the final
+    vertices).  With texture= every item is a TexturedShape(vertices, triangles, sigma, texture) whose `texture` is a `mesh_texture.Texture`,
+    baked on the `grid_to_world` vertices WHATEVER `units` returns.  return_counts=True: also a list of `MeshCount` per sample."""
     if units not in ('index', 'world'):
         raise ValueError(f"units must be 'index' or 'world', got {units!r}")
-    if simplify is not None:
-        from . import mesh_simplify as _mesh_simplify
-        _mesh_simplify.check_options(simplify)
-    bake_kw = None
-    if texture is not None:
-        from . import mesh_texture as _mesh_texture
-        bake_kw, _ = _mesh_texture.check_options(texture)
-    counts = []
+    from . import mesh_build as _mesh_build          # the mesh modules behind it import this one
+    stages = _mesh_build.check_stages(components, smooth, simplify, texture)
     crop = _crop_slices(crop, volume_res)
-    out = []
+    out, counts = [], []
     for b in range(ws.shape[0]):               # one sample's grid alive at a time, as the reference loops
-        if texture is None:
-            sigma = density_grid(G, ws[b:b + 1], volume_res, voxel_origin, cube_size, slab_points, noise_mode)[0]
-        else:
-            syn = G.synthesis
-            _lib.require_cuda(ws, 'ws')
-            planes = _renderer.planes_to_hwc(syn.tri_plane_decoder(ws[b:b + 1, :syn.tri_plane_decoder.num_ws], hwc=True, noise_mode=noise_mode))
-            sigma = density_grid_from_planes(G, planes, volume_res, voxel_origin, cube_size, slab_points)[0]
-        if crop is not None:
-            sigma = sigma[crop]
-        verts, tris = marching_cubes(sigma, thresh_value)
-        if components is not None:
-            from . import mesh_components as _mesh_components
-            verts, tris = _mesh_components.clean_mesh(verts, tris, **dict(components))[:2]
-        if smooth is not None:
-            from . import mesh_surface as _mesh_surface
-            verts = _mesh_surface.smooth(verts, tris, **dict(smooth))
-        before = int(tris.shape[0])
-        if simplify is not None:
-            verts, tris = _mesh_simplify.apply(verts, tris, simplify)[:2]
-        counts.append(MeshCount(verts.shape[0], tris.shape[0], before))
-        if texture is not None:
-            world = grid_to_world(verts, volume_res, voxel_origin, cube_size, crop, sheared)
-            tex = _mesh_texture.bake_field(G, planes, world, tris, **bake_kw)
-            counts[-1].atlas = tex.atlas
+        _lib.require_cuda(ws, 'ws')
+        decoder = G.synthesis.tri_plane_decoder
+        planes = _renderer.planes_to_hwc(decoder(ws[b:b + 1, :decoder.num_ws], hwc=True, noise_mode=noise_mode))
+        m = _mesh_build.build_mesh(G, planes, stages, volume_res=volume_res, voxel_origin=voxel_origin, cube_size=cube_size, level=thresh_value,
+                                   crop_slices=crop, sheared=sheared, slab_points=slab_points, keep_grid=True, world=units == 'world')
+        verts = m.vertices
         if units == 'world':
-            verts = grid_to_world(verts, volume_res, voxel_origin, cube_size, crop, sheared)
+            verts = m.world
         elif normalize and verts.shape[0] > 0:
             diag = (verts.max(dim=0).values - verts.min(dim=0).values).norm()
             if float(diag) > 0:
                 verts = verts / diag
-        out.append(Shape(verts, tris, sigma) if texture is None else TexturedShape(verts, tris, sigma, tex))
+        counts.append(m.count)
+        out.append(Shape(verts, m.triangles, m.sigma) if m.texture is None else TexturedShape(verts, m.triangles, m.sigma, m.texture))
     return (out, counts) if return_counts else out
 
 

@@ -25,8 +25,7 @@ import torch
 from . import _lib
 from . import geometry as _geometry
 from . import inference as _inference
-from . import mesh_components as _mesh_components
-from . import mesh_simplify as _mesh_simplify
+from . import mesh_build as _mesh_build
 from . import mesh_surface as _mesh_surface
 from . import mesh_texture as _mesh_texture
 from . import renderer as _renderer
@@ -234,7 +233,8 @@ def mesh_resolve_ms(vis, vertices, triangles, c2w, focal, resolution, t_miss, ve
 # ----------------------------------------------------------------------------------------------------------------------
 # frames
 # ----------------------------------------------------------------------------------------------------------------------
-def _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_call, vertex_normals=None, texture=None, texture_filter='bilinear', samples=1):
+def _check_options(mode, normals, cull, max_rays_per_call, texture=None, texture_filter='bilinear', samples=1):
+    """The options of a frame that do not depend on the mesh (texture: only whether there is one)."""
     if isinstance(samples, bool) or samples not in SAMPLES:
         raise ValueError(f'samples must be one of {SAMPLES}, got {samples!r}')
     if samples > 1 and normals == 'field':
@@ -245,8 +245,6 @@ def _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_
         raise ValueError(f'normals must be one of {NORMALS}, got {normals!r}')
     if cull not in CULL:
         raise ValueError(f'cull must be one of {sorted(CULL)}, got {cull!r}')
-    if normals == 'field' and (planes is None or G is None):
-        raise ValueError("normals='field' evaluates the field at the hits: it needs the generator G and the sample's planes (G.synthesis.tri_planes)")
     if texture is not None:
         if normals == 'field':
             raise ValueError("texture is fetched with face or vertex normals; normals='field' takes its colour from the field at the hit")
@@ -254,14 +252,6 @@ def _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_
             raise ValueError(f"texture is the colour of mode='colour', got mode={mode!r}")
         if texture_filter not in _mesh_texture.FILTERS:
             raise ValueError(f'texture_filter must be one of {sorted(_mesh_texture.FILTERS)}, got {texture_filter!r}')
-    if normals != 'field' and mode == 'colour' and vertex_colours is None and texture is None:
-        raise ValueError(f"mode='colour' with normals={normals!r} needs vertex_colours [V,3] (mesh.vertex_colours)")
-    if vertex_normals is not None:
-        if normals != 'vertex':
-            raise ValueError(f"vertex_normals are read by normals='vertex' only, got normals={normals!r}")
-        if not isinstance(vertex_normals, torch.Tensor) or vertex_normals.dtype != torch.float32 or vertex_normals.ndim != 2 or vertex_normals.shape[1] != 3:
-            raise ValueError(f'vertex_normals must be an fp32 [V,3] tensor (mesh_surface.vertex_normals), got {getattr(vertex_normals, "dtype", type(vertex_normals).__name__)} '
-                             f'{tuple(getattr(vertex_normals, "shape", ()))}')
     if max_rays_per_call is not None and int(max_rays_per_call) < 1:
         raise ValueError(f'max_rays_per_call must be positive, got {max_rays_per_call!r}')
 
@@ -277,6 +267,11 @@ def vertex_colours(G, planes, vertices, points_per_call=2 ** 22):
         v = _lib.f32c(vertices[i0:i0 + step]).unsqueeze(0)
         out[i0:i0 + step] = (point_field(planes, v)[0, :, :3] * 0.5 + 0.5).clamp_(0.0, 1.0)
     return out
+
+
+# the pieces of a frame: name, trailing shape, dtype; `coverage` with samples > 1 only
+FIELDS = (('rgb', (3,), torch.float32), ('depth', (1,), torch.float32), ('normal', (3,), torch.float32), ('status', (), torch.int32),
+          ('tri', (), torch.int32), ('coverage', (), torch.float32))
 
 
 @torch.no_grad()
@@ -308,7 +303,18 @@ def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shad
     `background`, and the group gains coverage [C,R], the fraction of the pixel's samples the mesh covers (composite another background B as
     rgb + (1 - coverage) * (B - background)).  status is 1 where any sample hit; depth, tri and normal are those of the nearest hit sample.  The
     frame stays on the pixel grid of the one-sample frame and of the renderer's frames of the same cameras.  The chunks shrink by `samples`."""
-    _check_options(mode, normals, cull, planes, G, vertex_colours, max_rays_per_call, vertex_normals, texture, texture_filter, samples)
+    _check_options(mode, normals, cull, max_rays_per_call, texture, texture_filter, samples)
+    # what those options need of this mesh: the field behind it, its colours, its normals
+    if normals == 'field' and (planes is None or G is None):
+        raise ValueError("normals='field' evaluates the field at the hits: it needs the generator G and the sample's planes (G.synthesis.tri_planes)")
+    if normals != 'field' and mode == 'colour' and vertex_colours is None and texture is None:
+        raise ValueError(f"mode='colour' with normals={normals!r} needs vertex_colours [V,3] (mesh.vertex_colours)")
+    if vertex_normals is not None:
+        if normals != 'vertex':
+            raise ValueError(f"vertex_normals are read by normals='vertex' only, got normals={normals!r}")
+        if not isinstance(vertex_normals, torch.Tensor) or vertex_normals.dtype != torch.float32 or vertex_normals.ndim != 2 or vertex_normals.shape[1] != 3:
+            raise ValueError(f'vertex_normals must be an fp32 [V,3] tensor (mesh_surface.vertex_normals), got {getattr(vertex_normals, "dtype", type(vertex_normals).__name__)} '
+                             f'{tuple(getattr(vertex_normals, "shape", ()))}')
     if normals == 'vertex' and isinstance(vertices, torch.Tensor) and isinstance(triangles, torch.Tensor) and not (vertices.is_cuda and triangles.is_cuda):
         # this mode is an option of a device mesh only (its corner table is built there): asking for it on a host mesh is a bad option value
         raise ValueError(f"normals='vertex' takes a mesh on the GPU (got {vertices.device}, {triangles.device}); the vertex normals have no CPU path")
@@ -329,8 +335,8 @@ def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shad
     focal = focal_lengths(get('fov'), C, dev)
     if samples == 1:
         ray_o, ray_d = _renderer.sample_rays(c2w, fov=get('fov'), resolution=(w, h))
-    field = normals == 'field'
-    if field:
+    point_field = None
+    if normals == 'field':
         if G.synthesis.training:
             raise RuntimeError('render_mesh_views is the inference route: call .eval() first')
         if not isinstance(planes, _renderer.HWCPlanes) or int(planes.t.shape[0]) != 1:
@@ -344,46 +350,40 @@ def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shad
     if texture is not None:
         _mesh_texture._check_texture(texture, int(triangles.shape[0]))
     vrgb = None
-    if not field and mode == 'colour' and texture is None:
+    if point_field is None and mode == 'colour' and texture is None:
         vrgb = vertex_colours if vertex_colours.dtype == torch.float32 else vertex_colours.float() / (255.0 if vertex_colours.dtype == torch.uint8 else 1.0)
     max_rays = 16 * R if max_rays_per_call is None else int(max_rays_per_call)
     cstep = max(1, min(max_rays, FIELD_POINTS_MAX // STENCIL) // (R * samples))
-    out = _renderer.Gather(C, R)
-    for c0 in range(0, C, cstep):
-        cs = slice(c0, min(c0 + cstep, C))
-        n = (cs.stop - cs.start) * R
-        if samples > 1:
-            vis = mesh_visibility_ms(vertices, triangles, c2w[cs], focal[cs], (w, h), samples, near=near, cull=cull)
-            rgb, coverage, status, t_hit, tri, normal = mesh_resolve_ms(vis, vertices, triangles, c2w[cs], focal[cs], (w, h), t_miss, vertex_normals=vnorm,
-                                                                        vertex_rgb=vrgb, texture=texture, texture_filter=texture_filter, mode=mode,
-                                                                        light=light, ambient=ambient, albedo=albedo, background=background)
-            k = cs.stop - cs.start
-            out.put(cs, slice(0, R), rgb=rgb.reshape(k, R, 3), depth=t_hit.reshape(k, R, 1), normal=normal.reshape(k, R, 3), status=status.reshape(k, R),
-                    tri=tri.reshape(k, R), coverage=coverage.reshape(k, R))
-            continue
-        o, d = ray_o[cs].reshape(n, 3), ray_d[cs].reshape(n, 3)
+    shade = dict(mode=mode, light=light, ambient=ambient, albedo=albedo, background=background)
+    fields = FIELDS if samples > 1 else FIELDS[:-1]
+
+    def one_sample(cs):                         # a chunk of cameras -> its pieces by name, ray-flat
+        o, d = ray_o[cs].reshape(-1, 3), ray_d[cs].reshape(-1, 3)
+        n = o.shape[0]
         vis = mesh_visibility(vertices, triangles, c2w[cs], focal[cs], d, (w, h), near=near, cull=cull)
         t_hit, status, tri, normal, colour, points = mesh_resolve(vis.reshape(n), vertices, triangles, o, d, step, t_miss, vertex_rgb=vrgb)
-        if field:
-            stencil = point_field(planes, points.reshape(1, n * STENCIL, 3))
-            rgb, normal = _shapes.iso_shade(stencil, status, d, mode=mode, light=light, ambient=ambient, albedo=albedo, background=background)
+        if point_field is not None:
+            rgb, normal = _shapes.iso_shade(point_field(planes, points.reshape(1, n * STENCIL, 3)), status, d, **shade)
         else:
             if vnorm is not None:
                 _mesh_surface.interp_normals(tri, status, t_hit, _lib.f32c(o), _lib.f32c(d), vertices, triangles, vnorm, normal)
             if texture is not None:
                 colour = _mesh_texture.sample_texture(tri, status, t_hit, _lib.f32c(o), _lib.f32c(d), vertices, triangles, texture, texture_filter)
-            rgb = mesh_shade(normal, status, d, colour=colour, mode=mode, light=light, ambient=ambient, albedo=albedo, background=background)
-        k = cs.stop - cs.start
-        out.put(cs, slice(0, R), rgb=rgb.reshape(k, R, 3), depth=t_hit.reshape(k, R, 1), normal=normal.reshape(k, R, 3), status=status.reshape(k, R),
-                tri=tri.reshape(k, R))
-    if C == 0:
-        e = lambda *s, dt=torch.float32: torch.empty([0, R, *s], dtype=dt, device=dev)      # noqa: E731
-        return TensorGroup(rgb=e(3), depth=e(1), normal=e(3), status=e(dt=torch.int32), tri=e(dt=torch.int32), **(dict(coverage=e()) if samples > 1 else {}))
-    if samples > 1:
-        rgb, depth, normal, status, tri, coverage = out.result()
-        return TensorGroup(rgb=rgb, depth=depth, normal=normal, status=status, tri=tri, coverage=coverage)
-    rgb, depth, normal, status, tri = out.result()
-    return TensorGroup(rgb=rgb, depth=depth, normal=normal, status=status, tri=tri)
+            rgb = mesh_shade(normal, status, d, colour=colour, **shade)
+        return dict(rgb=rgb, depth=t_hit, normal=normal, status=status, tri=tri)
+
+    def multisample(cs):                        # the same, with `coverage`
+        vis = mesh_visibility_ms(vertices, triangles, c2w[cs], focal[cs], (w, h), samples, near=near, cull=cull)
+        rgb, coverage, status, depth, tri, normal = mesh_resolve_ms(vis, vertices, triangles, c2w[cs], focal[cs], (w, h), t_miss, vertex_normals=vnorm,
+                                                                    vertex_rgb=vrgb, texture=texture, texture_filter=texture_filter, **shade)
+        return dict(rgb=rgb, depth=depth, normal=normal, status=status, tri=tri, coverage=coverage)
+    out = _renderer.Gather(C, R)
+    for c0 in range(0, C, cstep):
+        cs = slice(c0, min(c0 + cstep, C))
+        pieces = multisample(cs) if samples > 1 else one_sample(cs)
+        out.put(cs, slice(0, R), **{name: pieces[name].reshape(cs.stop - cs.start, R, *shape) for name, shape, _ in fields})
+    values = out.result() if C else [torch.empty([0, R, *shape], dtype=dtype, device=dev) for _, shape, dtype in fields]
+    return TensorGroup(**{name: value for (name, _, _), value in zip(fields, values)})
 
 
 def _camera_slice(camera_params, device, c0, c1):
@@ -398,23 +398,13 @@ def _camera_slice(camera_params, device, c0, c1):
 @torch.no_grad()
 def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=None, crop=None, sheared=True,
                        mode='shaded', normals='face', plane_batch=4, return_counts=False, components=None, smooth=None, simplify=None, texture=None, **kw):
-    """Mesh frames of every `ws` under its cameras (sample-major: camera n * V + v is view v of sample n).  Per sample: `density_grid` at
-    volume_res^3 over a cube of `cube_size` (default the whole field, 2 * cfg.cube_scale) -> `marching_cubes` at `level` -> `grid_to_world`,
-    then its V cameras through `render_mesh_views`.  The backbone runs once per plane batch; its planes feed the density grid and, with
-    normals='field' (or face normals in mode 'colour'), the field lookups of the frames.
-    -> TensorGroup(rgb [B*V,R,3], depth, normal, status, tri) as `render_mesh_views`; return_counts=True: also [(vertices, triangles)] per sample.
-    components: None (the raw level set), or a dict of `mesh_components.select` keyword arguments (e.g. dict(keep=1)): every sample's mesh goes
-    through `mesh_components.clean_mesh` before it is drawn (floaters dropped on the device); the counts are those of the cleaned mesh.
-    smooth: None, or a dict of `mesh_surface.smooth` keyword arguments (e.g. dict(iterations=10)): the mesh is smoothed after the cleaning and
-    before `grid_to_world`, in index units.  normals='vertex': the vertex normals (and, in mode 'colour', the vertex colours) are taken from the
-    final world-space vertices.
-    simplify: None, or a dict as `geometry.extract_geometry` takes it (dict(cell=2.0), dict(max_triangles=N), ...): `mesh_simplify.simplify` after
-    the smoothing and before `grid_to_world`, `cell` in voxels; normals and colours are those of the simplified mesh, and the counts are
-    `geometry.MeshCount`s whose `.triangles_before` holds what the mesh had before.
-    texture: None, or a dict(texels=8, filter='bilinear') (also fill, points_per_call of `mesh_texture.bake`): every sample's texture is baked
-    from the planes in hand on its FINAL world-space mesh -- after components, smoothing, simplification and `grid_to_world` -- and the frames
-    take their colour from it (mode='colour', face or vertex normals) instead of the vertex colours; every count's `.atlas` is then the sample's
-    `mesh_texture.Atlas` (None without a texture).
+    """Mesh frames of every `ws` under its cameras (sample-major: camera n * V + v is view v of sample n).  Per sample: `mesh_build.build_mesh`
+    -- the density grid at volume_res^3 over a cube of `cube_size` (default the whole field, 2 * cfg.cube_scale), marching cubes at `level`, the
+    stages, `grid_to_world` -- then its V cameras through `render_mesh_views`.  The backbone runs once per plane batch; its planes feed the
+    build and, with normals='field' (or face normals in mode 'colour'), the field lookups of the frames.
+    -> TensorGroup(rgb [B*V,R,3], depth, normal, status, tri) as `render_mesh_views`; return_counts=True: also a `geometry.MeshCount` per sample.
+    components, smooth, simplify, texture: the stages of `mesh_build.check_stages`.  Normals, vertex colours (mode 'colour') and counts are
+    those of the finished mesh in world units; with a texture the frames take their colour from it (mode='colour', face or vertex normals).
     kw: cull, near, light, ambient, albedo, background, max_rays_per_call, t_miss, step, samples of `render_mesh_views` (samples=4 | 16: multisampled
     frames, and the group gains `coverage`; the grids and strips below take it the same way)."""
     syn, cfg = G.synthesis, G.cfg
@@ -423,13 +413,11 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
     V = _renderer.views_per_sample(int(get('angles').shape[0]), num_samples, f'{num_samples} samples')
     if int(plane_batch) < 1:
         raise ValueError(f'plane_batch must be positive, got {plane_batch!r}')
-    bake_kw, tex_filter = (None, 'bilinear') if texture is None else _mesh_texture.check_options(texture)
-    _check_options(mode, normals, kw.get('cull', 'none'), True, G, True, kw.get('max_rays_per_call'), None, texture, tex_filter, kw.get('samples', 1))
+    stages = _mesh_build.check_stages(components, smooth, simplify, texture)
+    _check_options(mode, normals, kw.get('cull', 'none'), kw.get('max_rays_per_call'), texture, stages.texture_filter, kw.get('samples', 1))
     if syn.training:
         raise RuntimeError('render_mesh_frames is the inference route: call .eval() first (training mode renders patches with density noise)')
     _lib.require_cuda(ws, 'ws')
-    if simplify is not None:
-        _mesh_simplify.check_options(simplify)
     cube_size = 2.0 * float(cfg.cube_scale) if cube_size is None else float(cube_size)
     slices = _geometry._crop_slices(crop, volume_res)
     res = syn.test_resolution
@@ -439,53 +427,36 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
         planes = syn.tri_planes(ws[n0:n1], noise_mode='const')
         for b in range(n1 - n0):
             pb = _renderer.HWCPlanes(planes.t[b:b + 1])
-            sigma = _geometry.density_grid_from_planes(G, pb, volume_res, voxel_origin, cube_size)[0]
-            if slices is not None:
-                sigma = sigma[slices]
-            verts, tris = _geometry.marching_cubes(sigma, level)
-            del sigma
-            if components is not None:
-                verts, tris = _mesh_components.clean_mesh(verts, tris, **dict(components))[:2]
-            if smooth is not None:
-                verts = _mesh_surface.smooth(verts, tris, **dict(smooth))
-            before = int(tris.shape[0])
-            if simplify is not None:
-                verts, tris = _mesh_simplify.apply(verts, tris, simplify)[:2]
-            verts = _geometry.grid_to_world(verts, volume_res, voxel_origin, cube_size, slices, sheared)
-            counts.append(_geometry.MeshCount(verts.shape[0], tris.shape[0], before))
-            tex = None
-            if texture is not None:
-                tex = _mesh_texture.bake_field(G, pb, verts, tris, **bake_kw)
-                counts[-1].atlas = tex.atlas
-            vc = vertex_colours(G, pb, verts) if (mode == 'colour' and normals != 'field' and tex is None) else None
+            m = _mesh_build.build_mesh(G, pb, stages, volume_res=volume_res, voxel_origin=voxel_origin, cube_size=cube_size, level=level, crop_slices=slices,
+                                       sheared=sheared, keep_grid=False)
+            counts.append(m.count)
+            vc = vertex_colours(G, pb, m.world) if (mode == 'colour' and normals != 'field' and m.texture is None) else None
             cams = _camera_slice(camera_params, ws.device, (n0 + b) * V, (n0 + b + 1) * V)
-            parts.append(render_mesh_views(verts, tris, cams, res, mode=mode, normals=normals, planes=pb if normals == 'field' else None,
-                                           G=G, vertex_colours=vc, **({} if tex is None else dict(texture=tex, texture_filter=tex_filter)), **kw))
+            parts.append(render_mesh_views(m.world, m.triangles, cams, res, mode=mode, normals=normals, planes=pb if normals == 'field' else None, G=G,
+                                           vertex_colours=vc, **({} if m.texture is None else dict(texture=m.texture, texture_filter=stages.texture_filter)), **kw))
     frames = parts[0] if len(parts) == 1 else TensorGroup.cat(parts, dim=0)
     return (frames, counts) if return_counts else frames
 
 
-def _shown_mesh_frames(G, ws, camera_params, show, counts, **kw):
-    """-> a callable for the grid tails: the `show` buffer of `render_mesh_frames`; the per-sample counts are left in the list `counts`."""
+def _mesh_frames_tail(tail, G, ws, camera_params, show, return_counts, kw):
+    """tail(num_samples, V, the `show` buffer of `render_mesh_frames` as a callable) -> what it returns, with the per-sample counts when asked."""
+    num_samples, counts = len(ws), []
+    V = int(_renderer.cam_get(camera_params)('angles').shape[0]) // max(num_samples, 1)
+
     def all_frames():
         frames, counts[:] = render_mesh_frames(G, ws, camera_params, return_counts=True, **kw)
         return frames
-    return lambda: _inference.shown(show, all_frames)
+    out = tail(num_samples, V, lambda: _inference.shown(show, all_frames))
+    return (out, counts) if return_counts else out
 
 
 def render_mesh_video_grid(G, ws, camera_params, nrow='auto', show='rgb', num_videos=None, padding=2, as_numpy=False, return_counts=False, **kw):
     """`shapes.render_shape_video_grid` of mesh frames: frame t of the video is the make_grid of every sample's mesh view t -> uint8
     [T, GH, GW, 3] on the device (as_numpy=True: one copy to the host).  kw: the options of `render_mesh_frames`."""
-    num_samples, counts = len(ws), []
-    V = int(_renderer.cam_get(camera_params)('angles').shape[0]) // max(num_samples, 1)
-    out = _inference.video_grid_of(G, num_samples, V, _shown_mesh_frames(G, ws, camera_params, show, counts, **kw), nrow, num_videos, padding,
-                                   show == 'depth', as_numpy)
-    return (out, counts) if return_counts else out
+    return _mesh_frames_tail(lambda n, V, frames: _inference.video_grid_of(G, n, V, frames, nrow, num_videos, padding, show == 'depth', as_numpy),
+                             G, ws, camera_params, show, return_counts, kw)
 
 
 def render_mesh_strips(G, ws, camera_params, show='rgb', as_numpy=False, return_counts=False, **kw):
     """`shapes.render_shape_strips` of mesh frames: per sample, its mesh views side by side -> uint8 [num_samples, h, V * w, 3] on the device."""
-    num_samples, counts = len(ws), []
-    V = int(_renderer.cam_get(camera_params)('angles').shape[0]) // max(num_samples, 1)
-    out = _inference.strips_of(G, num_samples, V, _shown_mesh_frames(G, ws, camera_params, show, counts, **kw), show == 'depth', as_numpy)
-    return (out, counts) if return_counts else out
+    return _mesh_frames_tail(lambda n, V, frames: _inference.strips_of(G, n, V, frames, show == 'depth', as_numpy), G, ws, camera_params, show, return_counts, kw)

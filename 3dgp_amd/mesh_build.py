@@ -1,0 +1,57 @@
+"""The mesh of one sample, from its planes to the finished mesh: density grid -> crop -> marching cubes -> components -> smoothing ->
+simplification -> world units -> texture.  `geometry.extract_geometry` and `mesh.render_mesh_frames` obtain the planes, each its own way,
+and call `build_mesh` once per sample: a stage is added here, once."""
+import collections
+
+from . import geometry as _geometry
+from . import mesh_components as _mesh_components
+from . import mesh_simplify as _mesh_simplify
+from . import mesh_surface as _mesh_surface
+from . import mesh_texture as _mesh_texture
+
+Stages = collections.namedtuple('Stages', ['components', 'smooth', 'simplify', 'bake_kw', 'texture_filter'])
+Mesh = collections.namedtuple('Mesh', ['vertices', 'triangles', 'world', 'count', 'texture', 'sigma'])
+
+
+def check_stages(components, smooth, simplify, texture):
+    """The stage options of both drivers, in the order they run: each None (the stage is skipped) or a dict, checked before any device work
+    -> Stages (bake_kw is None without a texture).  components and smooth are checked by their stages, not here.
+    components: `mesh_components.select` keyword arguments (dict(keep=1)): `mesh_components.clean_mesh` drops the floaters on the device.
+    smooth: `mesh_surface.smooth` keyword arguments (dict(iterations=10)).
+    simplify: `mesh_simplify.simplify` keyword arguments with either `cell` (in voxels: dict(cell=2.0)) or `max_triangles`
+    (dict(max_triangles=100000): the first cell of `mesh_simplify.cell_for_triangles`' ladder that leaves no more): vertex clustering with
+    quadric placement; a count's `.triangles_before` holds what the mesh had before.
+    texture: dict(texels=8, filter='bilinear') (also fill, points_per_call of `mesh_texture.bake`): baked from the sample's planes on the
+    FINAL mesh in world units, where the field lives; a count's `.atlas` is then its `mesh_texture.Atlas`."""
+    if simplify is not None:
+        _mesh_simplify.check_options(simplify)
+    bake_kw, texture_filter = (None, 'bilinear') if texture is None else _mesh_texture.check_options(texture)
+    return Stages(components, smooth, simplify, bake_kw, texture_filter)
+
+
+def build_mesh(G, planes, stages, *, volume_res, voxel_origin, cube_size, level, crop_slices, sheared, slab_points=2 ** 22, keep_grid, world=True):
+    """planes: the HWCPlanes of ONE sample; crop_slices: `geometry._crop_slices` -> Mesh(vertices in index units of the cropped grid, triangles,
+    world: `grid_to_world` of the vertices, computed once and only for world=True or the bake (else None), count: a `geometry.MeshCount`,
+    texture: a `mesh_texture.Texture` or None, sigma: the cropped grid).  The stages run in index units.  keep_grid=False releases the grid
+    right after marching cubes (sigma is None): nothing O(res^3) lives through the later stages."""
+    sigma = _geometry.density_grid_from_planes(G, planes, volume_res, voxel_origin, cube_size, slab_points)[0]
+    if crop_slices is not None:
+        sigma = sigma[crop_slices]
+    verts, tris = _geometry.marching_cubes(sigma, level)
+    if not keep_grid:
+        sigma = None
+    if stages.components is not None:
+        verts, tris = _mesh_components.clean_mesh(verts, tris, **dict(stages.components))[:2]
+    if stages.smooth is not None:
+        verts = _mesh_surface.smooth(verts, tris, **dict(stages.smooth))
+    before = int(tris.shape[0])
+    if stages.simplify is not None:
+        verts, tris = _mesh_simplify.apply(verts, tris, stages.simplify)[:2]
+    count = _geometry.MeshCount(verts.shape[0], tris.shape[0], before)
+    wv = tex = None
+    if world or stages.bake_kw is not None:
+        wv = _geometry.grid_to_world(verts, volume_res, voxel_origin, cube_size, crop_slices, sheared)
+    if stages.bake_kw is not None:
+        tex = _mesh_texture.bake_field(G, planes, wv, tris, **stages.bake_kw)
+        count.atlas = tex.atlas
+    return Mesh(verts, tris, wv, count, tex, sigma)
