@@ -161,7 +161,14 @@ __global__ __launch_bounds__(256) void planes_to_hwc_kernel(const float* __restr
 template <int FQ, int MT, bool TAPS>
 void launch_field_t(const FieldParams& p, hipStream_t s) {
     const bool walk = FQ % 4 == 0 && p.ray_w > 0 && p.planes_bytes != 0;
-    if constexpr (FQ % 4 == 0 && FQ <= 8) {
+    // hid_dim 16 (MT = 1) is not built as a producer / consumer walk.  In those instantiations the compiler runs out of scalar registers (24-28 SGPRs
+    // spilled, the plane bases of the walk held in vector registers), and the `v_readfirstlane_b32` that brings a plane base back stands 1-4 wait states
+    // in front of the hand-issued `buffer_load_dwordx4` that reads it as its scalar offset.  CDNA wants 5 between a vector instruction that writes an
+    // SGPR and a vector-memory instruction that reads it; the compiler pads its own memory instructions and cannot see into the asm statement, so the
+    // load goes out with whatever the register held before: a memory fault.  (32,16) also needs 48-56 B of scratch there.  Both pairs take the table
+    // walk below, which gives the same bytes; how much slower that is than a working walk2 would be for (32,16) and (16,16) image walks with
+    // S % 4 == 0 and S >= 16 has not been measured.  isa_check refuses any walk2 instantiation with that hazard or with scratch.
+    if constexpr (FQ % 4 == 0 && FQ <= 8 && MT > 1) {
         // producer / consumer walk (field_walk2.inc): whole groups of four samples, a ring that is shorter than a patch's march
         // (the walk addresses ray_o / ray_d / t through scalar base + 32-bit byte offset)
         if (walk && (p.S & 3) == 0 && p.S >= 16 && p.total * 4 < ((int64_t)1 << 32) && (p.total / p.S) * 12 < ((int64_t)1 << 32)) {
@@ -246,7 +253,7 @@ TDGP_API int tdgp_triplane_field(const float* planes_hwc, const float* coords, c
     FIELD_CASE(64, 64) FIELD_CASE(64, 128)
     else ok = false;
 #undef FIELD_CASE
-    TDGP_CHECK(ok, TDGP_EUNSUPPORTED, "triplane_field: no kernel for feat_dim=%d, hid_dim=%d (need feat in {8,16,32,64}, hid in {16,32,64,128})", F, hid);
+    TDGP_CHECK(ok, TDGP_EUNSUPPORTED, "triplane_field: no kernel for feat_dim=%d, hid_dim=%d (the pairs of the table: feat 8 / 16 with hid 16, 32, 64; feat 32 with hid 16, 32, 64, 128; feat 64 with hid 64, 128)", F, hid);
     TDGP_LAUNCH_CHECK();
     return TDGP_OK;
 }

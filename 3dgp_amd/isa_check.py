@@ -87,6 +87,52 @@ def check_kernel(body, fq):
     return dict(loop_instructions=len(loop), tap_loads=nloads, hand_waits=hand_waits, compiler_vmcnt_waits=comp_waits), bad
 
 
+def _sregs(tok):
+    out = set()
+    for m in re.finditer(r's\[(\d+):(\d+)\]', tok):
+        out.update(range(int(m.group(1)), int(m.group(2)) + 1))
+    for m in re.finditer(r'(?<![\w\[:])s(\d+)\b', tok):
+        out.add(int(m.group(1)))
+    return out
+
+
+def check_sgpr_hazard(body):
+    """CDNA: 5 wait states between a vector instruction that writes an SGPR (v_readfirstlane_b32, v_readlane_b32, a compare or a carry-out into an
+    SGPR pair) and a vector-memory instruction that reads that SGPR.  The compiler pads its own memory instructions with `s_nop`; a load issued
+    from an asm statement it cannot see into gets none.  -> [(why, instruction)] over every vector-memory instruction of `body`.
+    The look-back follows the listing upwards through the straight-line code in front of the instruction: a label does not end it (the
+    fall-through is one of the ways in), an instruction that control never falls out of (`s_endpgm`, `s_branch`, `s_setpc_b64`) does -- what
+    stands above it is not a predecessor.  A vector instruction counts as writing every SGPR among its operands up to and including the first one
+    that names a VGPR-or-SGPR destination pair: `v_readlane_b32 s5, ..` writes s5, `v_add_co_u32 v1, s[2:3], ..` writes s[2:3] (operands after
+    the destinations of a VOP3 with carry-out are sources; counting a source as a write can only make the check stricter, never miss one)."""
+    code = [c for c in (ln.split(';')[0].strip() for ln in body) if c and not c.startswith('.') and not c.endswith(':')]
+
+    def written(p):
+        op, ops = p.split(None, 1)[0], [t.strip() for t in p.split(None, 1)[1].split(',')]
+        n = 2 if re.match(r'^v_(add_co|sub_co|subrev_co|addc_co|subb_co|subbrev_co|mad_u64_u32|mad_i64_i32|div_scale)', op) else 1
+        return set().union(*[_sregs(t) for t in ops[:n]])
+
+    bad = []
+    for k, ins in enumerate(code):
+        if not re.match(r'^(buffer_|global_|flat_|scratch_)', ins) or ' ' not in ins:
+            continue
+        need, ws, j = _sregs(ins.split(None, 1)[1]), 0, k - 1
+        while j >= 0 and ws < 5 and need:
+            p = code[j]
+            op = p.split()[0]
+            if op in ('s_endpgm', 's_branch', 's_setpc_b64'):
+                break
+            if op == 's_nop':
+                ws += int(p.split()[1], 0) + 1
+            else:
+                if op.startswith('v_') and ' ' in p and written(p) & need:
+                    bad.append((f'reads an SGPR that `{p}` wrote {ws} wait state(s) earlier (5 needed)', ins))
+                    break
+                ws += 1
+            j -= 1
+    return bad
+
+
 def check_walk2_asm(asm_text):
     """Every triplane_walk2_kernel instantiation in a field.hip assembly listing.  -> {mangled name: (summary, violations)}"""
     lines = asm_text.splitlines()
@@ -96,7 +142,14 @@ def check_walk2_asm(asm_text):
         if not m:
             continue
         end = next((j for j in range(i, len(lines)) if lines[j].strip().startswith('.amdhsa_kernel')), len(lines))
-        out[m.group(1)] = check_kernel(lines[i:end], int(m.group(2)))
+        summary, bad = check_kernel(lines[i:end], int(m.group(2)))
+        # the kernel descriptor follows the body: spills would put the compiler's own scratch loads and stores among the hand-counted ones
+        scratch = next((int(mm.group(1)) for ln2 in lines[end:end + 60] for mm in [re.match(r'\s*\.amdhsa_private_segment_fixed_size\s+(\d+)', ln2)] if mm), 0)
+        summary['scratch_bytes'] = scratch
+        bad.extend(check_sgpr_hazard(lines[i:end]))
+        if scratch:
+            bad.append((f'{scratch} bytes of scratch: the instantiation does not fit the register file (launch_field_t must not select it)', ''))
+        out[m.group(1)] = (summary, bad)
     return out
 
 

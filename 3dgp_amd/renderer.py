@@ -987,5 +987,10 @@ def render_autograd(renderer, planes, decoder, ray_origins, ray_directions, rend
                                       f'feat_dim 64 / hid_dim 64 form is forward-only')
         params = [t for fc in m for t in (fc.weight, fc.bias)]
         return _RenderFunctionDeep.apply(planes, renderer, decoder, ray_origins, ray_directions, rendering_options, *params)
+    if fused_form(decoder):
+        hid, feat = m[0].weight.shape
+        if feat > 32 or hid > 64:           # exactly what tdgp_triplane_field_grad rejects; without this the refusal arrives in the middle of backward()
+            raise NotImplementedError(f'gradients through a two-layer decoder take feat_dim in {{8, 16, 32}} and hid_dim <= 64 (got {feat}, {hid}): the '
+                                      f'(32,128), (64,64) and (64,128) forms are forward-only')
     return _RenderFunction.apply(planes, m[0].weight, m[0].bias, m[1].weight, m[1].bias, renderer, decoder, ray_origins, ray_directions,
                                  rendering_options)

@@ -303,7 +303,10 @@ int tdgp_triplane_features(const float* planes_hwc, const float* coords, float* 
  * tap_idx: optional int32 [B,P,3,2] = (floor ix, floor iy) per plane, for integer-row parity tests.
  * sigma_noise / density_noise: training-time density noise (tri_plane_renderer.py:185-186): sigma += sigma_noise[b,p] * density_noise
  *          with sigma_noise [B,P] standard-normal draws; density_noise = 0 (sigma_noise may be NULL) turns it off.
- * Requires F % 4 == 0, F <= 64, hid % 16 == 0, hid <= 128. */
+ * Requires (F, hid) from the table of instantiated kernels (csrc/field.hip, FIELD_CASE):
+ *     (32,64) (32,32) (32,128) (32,16)   (16,64) (16,32) (16,16)   (8,64) (8,32) (8,16)   (64,64) (64,128);
+ * every other pair returns TDGP_EUNSUPPORTED before anything is launched.  (The gradient below has its own, different range -- F in {8,16,24,32}
+ * and any hid in 1..64 -- so of this table it takes the nine pairs with F <= 32 and hid <= 64.) */
 int tdgp_triplane_field(const float* planes_hwc, const float* coords, const float* ray_o, const float* ray_d,
                         const float* t, const float* w0, const float* b0, const float* w1, const float* b1,
                         const float* sigma_noise, float density_noise, float* rgbs, int32_t* tap_idx, int B, int64_t P,

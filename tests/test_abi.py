@@ -134,6 +134,38 @@ def test_walk2_isa_check_runs_in_the_build(tdgp):
     assert bad and 'touches the destination' in bad[0][0]
 
 
+def test_walk2_isa_check_knows_the_sgpr_hazard_and_scratch(tdgp):
+    """A vector instruction that writes an SGPR needs 5 wait states before a vector-memory instruction reads it; the compiler cannot pad a load
+    issued from an asm statement.  That is how the hid_dim 16 instantiations of triplane_walk2_kernel sent loads out with a stale plane base; the
+    build refuses such a listing now, and one that spills to scratch (hand-counted waits assume the producer's memory instructions are its own)."""
+    import importlib
+    isa = importlib.import_module('3dgp_amd.isa_check')
+    load = '\tbuffer_load_dwordx4 v[4:7], v1, s[4:7], s0 offen'
+    for gap, caught in ((['\ts_waitcnt lgkmcnt(1)'], True), (['\ts_nop 1', '\tv_add_u32_e32 v9, v8, v8'], True), (['\ts_nop 3'], True), (['\ts_nop 4'], False),
+                        (['\tv_mov_b32_e32 v2, v3'] * 5, False)):
+        bad = isa.check_sgpr_hazard(['\tv_readfirstlane_b32 s0, v2'] + gap + [load])
+        assert bool(bad) == caught, (gap, bad)
+    assert not isa.check_sgpr_hazard(['\ts_add_i32 s0, s1, s2', load])                       # a scalar instruction wrote it: no hazard
+    assert not isa.check_sgpr_hazard(['\tv_readfirstlane_b32 s9, v2', load])                 # another register
+    assert isa.check_sgpr_hazard(['\tv_readlane_b32 s5, v255, 3', '.LBB0_1:', load])         # part of the descriptor; a label does not end the look-back
+    assert isa.check_sgpr_hazard(['\tv_add_co_u32_e64 v1, s[0:1], v2, v3', load])            # a carry-out is a write of the pair
+    assert not isa.check_sgpr_hazard(['\tv_add_u32_e32 v1, s0, v2', load])                   # a source is not
+    for end in ('\ts_endpgm', '\ts_branch .LBB0_9'):                                         # control never falls out of these: not a predecessor
+        assert not isa.check_sgpr_hazard(['\tv_readfirstlane_b32 s0, v2', end, '.LBB0_1:', load])
+    assert isa.check_sgpr_hazard(['\tv_readfirstlane_b32 s0, v2', '\ts_cbranch_scc1 .LBB0_9', load])      # a conditional branch falls through
+    build = importlib.import_module('3dgp_amd.build')
+    asm = os.path.join(build.CSRC, 'build', 'field.s')
+    if not os.path.exists(asm):
+        subprocess.check_call([build._hipcc()] + build.FLAGS + ['-S', '--cuda-device-only', '-o', asm, os.path.join(build.CSRC, 'field.hip')], stderr=subprocess.DEVNULL)
+    text = open(asm).read()
+    res = isa.check_walk2_asm(text)
+    assert len(res) == 10 and all(s['scratch_bytes'] == 0 and not bad for s, bad in res.values())      # F 16 / 32 x hid 32 / 64 / 128 (F 16: 32 / 64), with and without taps
+    assert not any('ELi1ELb' in k for k in res), 'hid_dim 16 is kept off the producer / consumer walk (csrc/field.hip: launch_field_t)'
+    name = next(iter(res))
+    spilled = re.sub(r'(\.amdhsa_kernel ' + re.escape(name) + r'\n(?:.*\n){0,8}?\s*\.amdhsa_private_segment_fixed_size) 0', r'\1 48', text, count=1)
+    assert spilled != text and any('scratch' in why for why, _ in isa.check_walk2_asm(spilled)[name][1])
+
+
 def test_wino4_isa_check_runs_in_the_build(tdgp):
     """conv3_wino4_kernel's LDS-direct loads are hand-issued (M0 written inside the asm statement, which hipcc will not let a clobber
     list name) and its pair-form K loop ends in a hand-counted `vmcnt(4)`.  isa_check.check_wino4_asm verifies on the generated code that M0 is
