@@ -108,6 +108,15 @@ _PROTOTYPES = {
     'tdgp_mesh_cluster_triangles_emit': (c_int, [P, c_int64, P, P, c_int64, P, c_int64, P, P]),
     'tdgp_mesh_cluster_place': (c_int, [P, c_int64, P, P, P, c_int64, POINTER(c_double), POINTER(c_double), P, c_int64, P, P, c_int, c_double, P, P]),
     'tdgp_mesh_cluster_attribute': (c_int, [P, c_int, c_int64, P, P, c_int64, P, P]),
+    'tdgp_mesh_decimate_quadrics': (c_int, [P, P, c_int64, c_int64, P, P, P, P, P, P]),
+    'tdgp_mesh_decimate_candidates': (c_int, [P, P, P, P, P, c_int64, c_int64, P, P, c_double, c_double, P, P, P, P]),
+    'tdgp_mesh_decimate_claim': (c_int, [P, P, c_int64, c_int64, P, P, P, P]),
+    'tdgp_mesh_decimate_select_workspace_bytes': (c_int64, [c_int64]),
+    'tdgp_mesh_decimate_select': (c_int, [P, P, P, P, c_int64, c_int64, P, P, P, c_int64, P]),
+    'tdgp_mesh_decimate_apply': (c_int, [P, c_int64, P, c_int64, c_int64, P, P, P, P, P, P, c_int, P, P]),
+    'tdgp_mesh_decimate_gather_workspace_bytes': (c_int64, [c_int64]),
+    'tdgp_mesh_decimate_gather_count': (c_int, [P, c_int64, P, c_int64, P]),
+    'tdgp_mesh_decimate_gather': (c_int, [P, P, c_int, P, c_int64, c_int64, P, c_int64, P, c_int64, P, P, P]),
     'tdgp_atlas_points': (c_int, [P, c_int64, P, c_int64, c_int, c_int, c_int, c_int, P, P, P]),
     'tdgp_atlas_texels': (c_int, [P, c_int64, P, c_int64, P, P, P]),
     'tdgp_mesh_sample_texture': (c_int, [P, P, P, P, P, c_int64, P, c_int64, P, c_int64, P, c_int, c_int, c_int, c_int, c_int, P, P]),

@@ -20,6 +20,7 @@
 // relabelled triangles.
 #include "common.h"
 #include "device_scan.h"
+#include "quadric_solve.h"
 
 namespace {
 
@@ -154,32 +155,6 @@ __global__ __launch_bounds__(SP_BLOCK) void tri_emit_kernel(const int32_t* __res
 }
 
 // ---- placement ---------------------------------------------------------------------------------------------------------------------------
-// One rotation of the cyclic Jacobi method on the symmetric a, pair (p, q), r the third index; the eigenvectors accumulate in the columns of u.
-__device__ __forceinline__ void jacobi_rotate(double (&a)[3][3], double (&u)[3][3], int p, int q, int r) {
-    const double apq = a[p][q];
-    if (apq == 0.0) return;
-    const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-    const double den = fabs(theta) + sqrt(theta * theta + 1.0);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / den;          // Rutishauser: the smaller root of t^2 + 2 t theta - 1 = 0
-    const double c = 1.0 / sqrt(t * t + 1.0);
-    const double s = t * c;
-    a[p][p] = a[p][p] - t * apq;
-    a[q][q] = a[q][q] + t * apq;
-    a[p][q] = 0.0;
-    a[q][p] = 0.0;
-    const double arp = a[r][p], arq = a[r][q];
-    a[r][p] = c * arp - s * arq;
-    a[p][r] = a[r][p];
-    a[r][q] = s * arp + c * arq;
-    a[q][r] = a[r][q];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const double ukp = u[k][p], ukq = u[k][q];
-        u[k][p] = c * ukp - s * ukq;
-        u[k][q] = s * ukp + c * ukq;
-    }
-}
-
 __global__ __launch_bounds__(SP_PLACE_BLOCK) void place_kernel(const float* __restrict__ verts, int64_t V, const int32_t* __restrict__ order,
                                                          const int32_t* __restrict__ start, const int64_t* __restrict__ ckey, int64_t C, Cell3 g,
                                                          const int32_t* __restrict__ tris, int64_t T, const int32_t* __restrict__ cstart,
@@ -249,32 +224,7 @@ __global__ __launch_bounds__(SP_PLACE_BLOCK) void place_kernel(const float* __re
             A[1][0] = A[0][1];
             A[2][0] = A[0][2];
             A[2][1] = A[1][2];
-            double r[3];
-#pragma unroll
-            for (int c = 0; c < 3; c++) r[c] = -bv[c] - ((A[c][0] * m[0] + A[c][1] * m[1]) + A[c][2] * m[2]);
-            double a[3][3], u[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-#pragma unroll
-            for (int i = 0; i < 3; i++)
-#pragma unroll
-                for (int j = 0; j < 3; j++) a[i][j] = A[i][j];
-            for (int sweep = 0; sweep < 8; sweep++) {
-                jacobi_rotate(a, u, 0, 1, 2);
-                jacobi_rotate(a, u, 0, 2, 1);
-                jacobi_rotate(a, u, 1, 2, 0);
-            }
-            double lmax = a[0][0];
-            lmax = a[1][1] > lmax ? a[1][1] : lmax;
-            lmax = a[2][2] > lmax ? a[2][2] : lmax;
-            const double floor_l = rank_tol * lmax;
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-                const double l = a[i][i];
-                if (l > floor_l) {
-                    const double coef = ((u[0][i] * r[0] + u[1][i] * r[1]) + u[2][i] * r[2]) / l;
-#pragma unroll
-                    for (int c = 0; c < 3; c++) x[c] = x[c] + u[c][i] * coef;
-                }
-            }
+            quadric_minimise(A, bv, m, rank_tol, x);         // quadric_solve.h: the Jacobi mesh_decimate.hip shares
             bool ok = true;
 #pragma unroll
             for (int c = 0; c < 3; c++) {

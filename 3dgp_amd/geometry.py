@@ -25,10 +25,12 @@ TexturedShape = collections.namedtuple('TexturedShape', ['vertices', 'triangles'
 
 class MeshCount(tuple):
     """(vertices, triangles) of a finished mesh -- a plain pair to whoever unpacks or compares it -- with `.triangles_before`, the triangles it
-    had before `simplify=` (the same number without it), and `.atlas`, the `mesh_texture.Atlas` of its texture (None without `texture=`)."""
+    had before `simplify=` / `decimate=` (the same number without them), `.atlas`, the `mesh_texture.Atlas` of its texture (None without
+    `texture=`), and `.decimate`, dict(rounds, stopped, triangles_before) of the `decimate=` stage (None without it)."""
     def __new__(cls, vertices, triangles, triangles_before=None):
         self = super().__new__(cls, (int(vertices), int(triangles)))
         self.atlas = None
+        self.decimate = None
         self.triangles_before = int(triangles if triangles_before is None else triangles_before)
         return self
 FIELD_POINTS_MAX = (2 ** 31 - 1) // 4          # points one tdgp_triplane_field call takes (csrc/field.hip)
@@ -173,21 +175,21 @@ def grid_to_world(vertices, volume_res, voxel_origin=(0.0, 0.0, 0.0), cube_size=
 @torch.no_grad()
 def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=0.3, thresh_value=25.0, crop='reference', normalize=True,
                      slab_points=2 ** 22, noise_mode='const', units='index', sheared=True, components=None, smooth=None, simplify=None,
-                     return_counts=False, texture=None):
+                     return_counts=False, texture=None, decimate=None):
     """scripts/extract_geometry.py:26-42 per sample of `ws`: density grid -> crop -> marching cubes -> (optionally) scale.  Returns a list of
     Shape(vertices [V,3] fp32, triangles [T,3] int32, sigma [D,H,W] fp32 -- the cropped grid), all on the device.
     crop: 'reference' (extract_geometry.py:33), None, or three slices.  normalize: divide the vertices by the length of their bounding-box
     diagonal (`mesh.apply_scale(1.0 / mesh.scale)`, extract_geometry.py:42 -- trimesh's `scale`; no translation).
     units='world': the vertices go through `grid_to_world` with this call's volume_res / voxel_origin / cube_size / crop (and `sheared`)
     instead of `normalize` -- the mesh `mesh.render_mesh_views` takes.
-    components, smooth, simplify, texture: the stages of `mesh_build.check_stages`, run on the marching-cubes output BEFORE it is scaled
+    components, smooth, simplify, decimate, texture: the stages of `mesh_build.check_stages`, run on the marching-cubes output BEFORE it is scaled
     (`normalize` divides by the diagonal of the finished mesh; vertex normals are the caller's: `mesh_surface.vertex_normals` of the final
     vertices).  With texture= every item is a TexturedShape(vertices, triangles, sigma, texture) whose `texture` is a `mesh_texture.Texture`,
     baked on the `grid_to_world` vertices WHATEVER `units` returns.  return_counts=True: also a list of `MeshCount` per sample."""
     if units not in ('index', 'world'):
         raise ValueError(f"units must be 'index' or 'world', got {units!r}")
     from . import mesh_build as _mesh_build          # the mesh modules behind it import this one
-    stages = _mesh_build.check_stages(components, smooth, simplify, texture)
+    stages = _mesh_build.check_stages(components, smooth, simplify, texture, decimate)
     crop = _crop_slices(crop, volume_res)
     out, counts = [], []
     for b in range(ws.shape[0]):               # one sample's grid alive at a time, as the reference loops

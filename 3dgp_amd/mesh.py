@@ -397,13 +397,14 @@ def _camera_slice(camera_params, device, c0, c1):
 
 @torch.no_grad()
 def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=None, crop=None, sheared=True,
-                       mode='shaded', normals='face', plane_batch=4, return_counts=False, components=None, smooth=None, simplify=None, texture=None, **kw):
+                       mode='shaded', normals='face', plane_batch=4, return_counts=False, components=None, smooth=None, simplify=None, texture=None, decimate=None,
+                       **kw):
     """Mesh frames of every `ws` under its cameras (sample-major: camera n * V + v is view v of sample n).  Per sample: `mesh_build.build_mesh`
     -- the density grid at volume_res^3 over a cube of `cube_size` (default the whole field, 2 * cfg.cube_scale), marching cubes at `level`, the
     stages, `grid_to_world` -- then its V cameras through `render_mesh_views`.  The backbone runs once per plane batch; its planes feed the
     build and, with normals='field' (or face normals in mode 'colour'), the field lookups of the frames.
     -> TensorGroup(rgb [B*V,R,3], depth, normal, status, tri) as `render_mesh_views`; return_counts=True: also a `geometry.MeshCount` per sample.
-    components, smooth, simplify, texture: the stages of `mesh_build.check_stages`.  Normals, vertex colours (mode 'colour') and counts are
+    components, smooth, simplify, decimate, texture: the stages of `mesh_build.check_stages`.  Normals, vertex colours (mode 'colour') and counts are
     those of the finished mesh in world units; with a texture the frames take their colour from it (mode='colour', face or vertex normals).
     kw: cull, near, light, ambient, albedo, background, max_rays_per_call, t_miss, step, samples of `render_mesh_views` (samples=4 | 16: multisampled
     frames, and the group gains `coverage`; the grids and strips below take it the same way)."""
@@ -413,7 +414,7 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
     V = _renderer.views_per_sample(int(get('angles').shape[0]), num_samples, f'{num_samples} samples')
     if int(plane_batch) < 1:
         raise ValueError(f'plane_batch must be positive, got {plane_batch!r}')
-    stages = _mesh_build.check_stages(components, smooth, simplify, texture)
+    stages = _mesh_build.check_stages(components, smooth, simplify, texture, decimate)
     _check_options(mode, normals, kw.get('cull', 'none'), kw.get('max_rays_per_call'), texture, stages.texture_filter, kw.get('samples', 1))
     if syn.training:
         raise RuntimeError('render_mesh_frames is the inference route: call .eval() first (training mode renders patches with density noise)')

@@ -1,19 +1,20 @@
 """The mesh of one sample, from its planes to the finished mesh: density grid -> crop -> marching cubes -> components -> smoothing ->
-simplification -> world units -> texture.  `geometry.extract_geometry` and `mesh.render_mesh_frames` obtain the planes, each its own way,
+simplification -> decimation -> world units -> texture.  `geometry.extract_geometry` and `mesh.render_mesh_frames` obtain the planes, each its own way,
 and call `build_mesh` once per sample: a stage is added here, once."""
 import collections
 
 from . import geometry as _geometry
 from . import mesh_components as _mesh_components
+from . import mesh_decimate as _mesh_decimate
 from . import mesh_simplify as _mesh_simplify
 from . import mesh_surface as _mesh_surface
 from . import mesh_texture as _mesh_texture
 
-Stages = collections.namedtuple('Stages', ['components', 'smooth', 'simplify', 'bake_kw', 'texture_filter'])
+Stages = collections.namedtuple('Stages', ['components', 'smooth', 'simplify', 'bake_kw', 'texture_filter', 'decimate'], defaults=(None,))
 Mesh = collections.namedtuple('Mesh', ['vertices', 'triangles', 'world', 'count', 'texture', 'sigma'])
 
 
-def check_stages(components, smooth, simplify, texture):
+def check_stages(components, smooth, simplify, texture, decimate=None):
     """The stage options of both drivers, in the order they run: each None (the stage is skipped) or a dict, checked before any device work
     -> Stages (bake_kw is None without a texture).  components and smooth are checked by their stages, not here.
     components: `mesh_components.select` keyword arguments (dict(keep=1)): `mesh_components.clean_mesh` drops the floaters on the device.
@@ -21,12 +22,17 @@ def check_stages(components, smooth, simplify, texture):
     simplify: `mesh_simplify.simplify` keyword arguments with either `cell` (in voxels: dict(cell=2.0)) or `max_triangles`
     (dict(max_triangles=100000): the first cell of `mesh_simplify.cell_for_triangles`' ladder that leaves no more): vertex clustering with
     quadric placement; a count's `.triangles_before` holds what the mesh had before.
+    decimate: `mesh_decimate.decimate` keyword arguments with `target_triangles`, `max_error` (in voxels) or both (dict(target_triangles=100000)):
+    quadric edge collapse that keeps the surface closed, oriented and of the same topology; it runs after `simplify`, and a count's
+    `.decimate` is then dict(rounds, stopped, triangles_before): what the stage was given and how it ended.
     texture: dict(texels=8, filter='bilinear') (also fill, points_per_call of `mesh_texture.bake`): baked from the sample's planes on the
     FINAL mesh in world units, where the field lives; a count's `.atlas` is then its `mesh_texture.Atlas`."""
     if simplify is not None:
         _mesh_simplify.check_options(simplify)
+    if decimate is not None:
+        _mesh_decimate.check_options(decimate)
     bake_kw, texture_filter = (None, 'bilinear') if texture is None else _mesh_texture.check_options(texture)
-    return Stages(components, smooth, simplify, bake_kw, texture_filter)
+    return Stages(components, smooth, simplify, bake_kw, texture_filter, decimate)
 
 
 def build_mesh(G, planes, stages, *, volume_res, voxel_origin, cube_size, level, crop_slices, sheared, slab_points=2 ** 22, keep_grid, world=True):
@@ -47,7 +53,14 @@ def build_mesh(G, planes, stages, *, volume_res, voxel_origin, cube_size, level,
     before = int(tris.shape[0])
     if stages.simplify is not None:
         verts, tris = _mesh_simplify.apply(verts, tris, stages.simplify)[:2]
+    decimated = None
+    if stages.decimate is not None:
+        given = int(tris.shape[0])
+        d = _mesh_decimate.apply(verts, tris, stages.decimate)
+        verts, tris, decimated = d.vertices, d.triangles, dict(rounds=d.rounds, stopped=d.stopped, triangles_before=given)
     count = _geometry.MeshCount(verts.shape[0], tris.shape[0], before)
+    if decimated is not None:
+        count.decimate = decimated
     wv = tex = None
     if world or stages.bake_kw is not None:
         wv = _geometry.grid_to_world(verts, volume_res, voxel_origin, cube_size, crop_slices, sheared)

@@ -841,6 +841,76 @@ int     tdgp_mesh_cluster_attribute(const float* attribute, int channels, int64_
                                     float* out, tdgp_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Mesh decimation (csrc/mesh_decimate.hip; the reference's users decimate a host copy of the mesh, trimesh / MeshLab): round-based quadric
+ * edge collapse (Garland-Heckbert 1997) with a link-condition test.  Every round collapses an independent set of edges at once.
+ *   tdgp_mesh_corner_table -> tdgp_mesh_boundary_vertices (once: the rim is FIXED from round 0) -> tdgp_mesh_decimate_quadrics (once)
+ *   per round: tdgp_mesh_corner_table -> _decimate_candidates -> _decimate_claim -> _decimate_select -> [the count is read back; with a target
+ *   the caller keeps the kmax smallest keys: a sort is plumbing] -> _decimate_apply -> tdgp_mesh_cluster_triangles_relabel (cluster = parent)
+ *   -> _triangles_count (perm NULL) -> _triangles_emit;   at the end: _decimate_gather_count -> _decimate_gather -> _triangles_relabel
+ * Common: the rules of the mesh blocks above, unchanged (skipped indices are never dereferenced, checked arguments, empty inputs, caller-owned
+ * 16-byte aligned workspaces sized by a query that answers -1 for sizes it refuses, no waiting between workgroups, no floating-point atomics,
+ * every floating-point operation rounded once in the order written, `/` and sqrt correctly rounded).  3 T <= 2^31 - 1, V <= 2^31 - 2.  The
+ * working arrays live across the rounds in DOUBLE: position [V,3], quadric [V,10] (the upper triangle of the symmetric 4x4 in the order 00 01
+ * 02 03 11 12 13 22 23 33), weight [V], attribute [V,channels]; parent int32 [V] starts as the identity and parent[removed] = survivor is
+ * never undone (a vertex is alive while parent[v] == v; the current triangles name alive vertices only).  (start, corner) is the corner
+ * table of the CURRENT triangles with V vertices, ranges clamped as the gathers of the mesh-surface block clamp them; N(v) is the set of
+ * vertices in the next or previous slot of v's corners.  Every output is a pure function of the arrays as given.
+ *
+ * tdgp_mesh_decimate_quadrics: position = the vertices widened.  Per vertex, Q = 0, w = 0; for each of its corners in table order, with p0, p1,
+ *   p2 the triangle's vertices in SLOT order, widened:  e1 = p1 - p0, e2 = p2 - p0,  n = (e1_1*e2_2 - e1_2*e2_1, e1_2*e2_0 - e1_0*e2_2,
+ *   e1_0*e2_1 - e1_1*e2_0),  l = sqrt((n_0*n_0 + n_1*n_1) + n_2*n_2);  unless 0 < l < inf the triangle adds nothing;  q = (n_0/l, n_1/l, n_2/l,
+ *   -((q_0*p0_0 + q_1*p0_1) + q_2*p0_2)),  g = l * 0.5;  Q_rc = Q_rc + (g*q_r)*q_c for r <= c;  w = w + g.
+ *
+ * tdgp_mesh_decimate_candidates: one lane per corner k = 3t + i, a = tri[t][i], b = tri[t][(i+1)%3] -> key uint64 [3T], placement double [3T,3],
+ *   opposite int32 [3T,2] (the last two written for passing corners only).  max_error 0: no bound.  key = all ones unless ALL of:
+ *   a < b;  not (rim[a] and rim[b]) (rim uint8 [V] or NULL);  exactly two of a's corners lie in triangles that name b -- c and d are their third
+ *   vertices, in table order -- and c != d;  c and d have more than 3 corners each;  no vertex of N(a) other than a, b, c, d is in N(b) (the link
+ *   condition |N(a) n N(b)| == 2);  Q = Q_a + Q_b, w = w_a + w_b, A = the 3x3 of Q, bv = (Q_03, Q_13, Q_23);  x = p_a if rim[a], else p_b if
+ *   rim[b], else the minimiser of tdgp_mesh_cluster_place (r = -bv - A m, the 8-sweep Jacobi, the eigen-directions above rank_tol * l_max:
+ *   csrc/quadric_solve.h serves both) started from m = (p_a + p_b) * 0.5, and m itself if any x_c is not finite;
+ *   Ax_c = (A_c0*x_0 + A_c1*x_1) + A_c2*x_2,  cost = (((x_0*Ax_0 + x_1*Ax_1) + x_2*Ax_2) + 2 * ((bv_0*x_0 + bv_1*x_1) + bv_2*x_2)) + Q_33;
+ *   cost is not NaN, and below 0 it counts as 0;  with a bound, cost <= (max_error*max_error) * w: the area-weighted RMS distance to the
+ *   accumulated planes, not the Hausdorff distance;  no flip: for every corner of a whose triangle does not name b (then of b, not naming a),
+ *   with p the triangle's positions in slot order and p' the same with that corner's slot moved to x,  n0 = cross(p1-p0, p2-p0),
+ *   n1 = cross(p'1-p'0, p'2-p'0),  (n0_0*n1_0 + n0_1*n1_1) + n0_2*n1_2 > 0.
+ *   Then key = (bits of (float)cost << 32) | mix(k), with mix(h): h ^= h >> 16; h *= 0x7feb352d; h ^= h >> 15; h *= 0x846ca68b; h ^= h >> 16
+ *   on uint32 -- a bijection, so no two corners share a key, and on flat regions (every cost exactly 0) the order is scattered, not a chain.
+ * tdgp_mesh_decimate_claim: best uint64 [V] = all ones, then every passing corner does best[v] = min(best[v], key) for v in {a, b} u N(a) u
+ *   N(b): ONE unsigned 64-bit atomic minimum per vertex (tdgp_mesh_visibility's), whose result does not depend on the order of its operands.
+ * tdgp_mesh_decimate_select: flag[k] = 1 iff key[k] is not all ones and best[v] == key[k] for v in {a, b, c, d};  selected int32 (a buffer of
+ *   3 T entries) = the flagged corners, ascending; their number as one int64 at the START of the workspace.  Two selected edges cannot touch
+ *   each other's one-rings or share an opposite vertex, so every test above still holds when all of them are collapsed together.
+ * tdgp_mesh_decimate_apply: one lane per entry of `selected` [K] (the caller may have trimmed it).  The survivor s is b when rim[b] and not
+ *   rim[a], else a; r is the other.  From the OLD p_a, p_b:  d = p_b - p_a,  t = (((x_0-a_0)*d_0 + (x_1-a_1)*d_1) + (x_2-a_2)*d_2) / ((d_0*d_0 +
+ *   d_1*d_1) + d_2*d_2), clamped into [0, 1] (NaN -> 0);  attribute_s = (1 - t)*attribute_a + t*attribute_b per channel;  Q_s = Q_a + Q_b,
+ *   w_s = w_a + w_b,  p_s = x = placement[k];  parent[r] = s.
+ * tdgp_mesh_decimate_gather_count: the number of alive vertices as one int64 at the START of the workspace (scans).
+ * tdgp_mesh_decimate_gather: the same workspace, untouched -> out_vertices fp32 [V_out,3] and out_attribute fp32 [V_out,channels] = the alive
+ *   vertices in ascending id, each double rounded once;  vertex_map int32 [V] = the output index of the alive vertex at the end of v's parent
+ *   chain (followed for at most max_hops steps: the number of rounds suffices), -1 if none.
+ * --------------------------------------------------------------------------------------------- */
+int     tdgp_mesh_decimate_quadrics(const float* vertices, const int32_t* triangles, int64_t T, int64_t V, const int32_t* start,
+                                    const int32_t* corner, double* position, double* quadric, double* weight, tdgp_stream_t stream);
+int     tdgp_mesh_decimate_candidates(const double* position, const double* quadric, const double* weight, const uint8_t* rim,
+                                      const int32_t* triangles, int64_t T, int64_t V, const int32_t* start, const int32_t* corner,
+                                      double max_error, double rank_tol, uint64_t* key, double* placement, int32_t* opposite,
+                                      tdgp_stream_t stream);
+int     tdgp_mesh_decimate_claim(const uint64_t* key, const int32_t* triangles, int64_t T, int64_t V, const int32_t* start,
+                                 const int32_t* corner, uint64_t* best, tdgp_stream_t stream);
+int64_t tdgp_mesh_decimate_select_workspace_bytes(int64_t T);
+int     tdgp_mesh_decimate_select(const uint64_t* key, const uint64_t* best, const int32_t* opposite, const int32_t* triangles, int64_t T,
+                                  int64_t V, uint8_t* flag, int32_t* selected, void* workspace, int64_t workspace_bytes,
+                                  tdgp_stream_t stream);
+int     tdgp_mesh_decimate_apply(const int32_t* selected, int64_t K, const int32_t* triangles, int64_t T, int64_t V, const uint8_t* rim,
+                                 const double* placement, double* position, double* quadric, double* weight, double* attribute,
+                                 int channels, int32_t* parent, tdgp_stream_t stream);
+int64_t tdgp_mesh_decimate_gather_workspace_bytes(int64_t V);
+int     tdgp_mesh_decimate_gather_count(const int32_t* parent, int64_t V, void* workspace, int64_t workspace_bytes, tdgp_stream_t stream);
+int     tdgp_mesh_decimate_gather(const double* position, const double* attribute, int channels, const int32_t* parent, int64_t V,
+                                  int64_t max_hops, void* workspace, int64_t workspace_bytes, float* out_vertices, int64_t V_out,
+                                  float* out_attribute, int32_t* vertex_map, tdgp_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Mesh textures (csrc/mesh_texture.hip; the reference's users bake a texture in MeshLab / Blender after decimating): a per-triangle atlas
  * whose layout is a pure function of the triangle count, filled from the field, and fetched at the hits of a mesh frame.
  *   tdgp_atlas_points -> [the field's colour at the points: the caller's] -> tdgp_atlas_texels

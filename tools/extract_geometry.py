@@ -66,6 +66,10 @@ def build_parser():
     p.add_argument('--simplify-max-triangles', type=int, default=argparse.SUPPRESS, metavar='N',
                    help='simplify with the first cell of the ladder 1, 1.41, 2, ... voxels that leaves at most N triangles')
     p.add_argument('--simplify-placement', choices=['quadric', 'mean'], default=argparse.SUPPRESS, help='where a cell puts its vertex (default quadric)')
+    # and the decimation (mesh_decimate.py): quadric edge collapse that keeps the surface closed and of the same topology, after the simplification
+    p.add_argument('--decimate-triangles', type=int, default=argparse.SUPPRESS, metavar='N', help='collapse edges on the device until at most N triangles are left (default: none)')
+    p.add_argument('--decimate-max-error', type=float, default=argparse.SUPPRESS, metavar='E',
+                   help='collapse edges while the RMS distance of a new vertex to the planes it stands for stays within E voxels (with --decimate-triangles: both hold)')
     # and the texture (mesh_texture.py): a per-triangle atlas baked from the field on the final mesh, written next to the .obj
     p.add_argument('--texture-texels', type=int, default=argparse.SUPPRESS, metavar='N',
                    help='bake a texture of N texels per triangle leg (2..64) and write NAME.obj with vt lines, NAME.mtl and NAME.png (needs --save-obj; default: none)')
@@ -110,6 +114,14 @@ def simplify_options(args):
     return opts
 
 
+def decimate_options(args):
+    """The `decimate` argument of geometry.extract_geometry from the command line: None unless --decimate-triangles or --decimate-max-error asks for it."""
+    most, err = getattr(args, 'decimate_triangles', None), getattr(args, 'decimate_max_error', None)
+    if most is None and err is None:
+        return None
+    return {k: v for k, v in (('target_triangles', most), ('max_error', err)) if v is not None}
+
+
 def texture_options(args):
     """The `texture` argument of geometry.extract_geometry from the command line: None unless --texture-texels asks for it."""
     texels = getattr(args, 'texture_texels', None)
@@ -132,6 +144,10 @@ def parse_args(argv=None):
         p.error(f'--simplify-cell takes a positive finite number, got {args.simplify_cell}')
     if getattr(args, 'simplify_max_triangles', 0) < 0:
         p.error(f'--simplify-max-triangles takes a non-negative integer, got {args.simplify_max_triangles}')
+    if getattr(args, 'decimate_triangles', 0) < 0:
+        p.error(f'--decimate-triangles takes a non-negative integer, got {args.decimate_triangles}')
+    if not 0 < getattr(args, 'decimate_max_error', 1.0) < float('inf'):             # false for NaN too
+        p.error(f'--decimate-max-error takes a positive finite number, got {args.decimate_max_error}')
     if args.seeds is None and args.num_seeds is None:
         p.error('You must specify either `num_seeds` or `seeds`')
     if args.seeds is not None and args.num_seeds is not None:
@@ -163,12 +179,13 @@ def main(argv=None):
     os.makedirs(args.output_dir, exist_ok=True)
     need_mesh = args.save_obj or args.save_ply
     comp, smooth, with_normals = component_options(args), smooth_options(args), getattr(args, 'vertex_normals', False)
-    simplify, texture = simplify_options(args), texture_options(args)
+    simplify, texture, decimate = simplify_options(args), texture_options(args), decimate_options(args)
     for name, w in zip(names, ws.split(1, dim=0)):
         if need_mesh:
             shapes, counts = geometry.extract_geometry(G, w, volume_res=args.volume_res, voxel_origin=args.voxel_origin, cube_size=args.cube_size,
                                                        thresh_value=args.thresh_value, crop='reference', normalize=True, components=comp, smooth=smooth,
-                                                       simplify=simplify, return_counts=True, **({} if texture is None else dict(texture=texture)))
+                                                       simplify=simplify, return_counts=True, **({} if texture is None else dict(texture=texture)),
+                                                       **({} if decimate is None else dict(decimate=decimate)))
             shape = shapes[0]
             sigma = shape.sigma
             normals = tdgp.mesh_surface.vertex_normals(shape.vertices, shape.triangles) if with_normals else None
@@ -183,6 +200,10 @@ def main(argv=None):
                 print(f'{name}: {shape.vertices.shape[0]} vertices, {shape.triangles.shape[0]} triangles')
                 if simplify is not None:
                     print(json.dumps(dict(name=name, simplify=simplify, vertices=counts[0][0], triangles=counts[0][1], triangles_before_simplify=counts[0].triangles_before)))
+                if decimate is not None:
+                    print(json.dumps(dict(name=name, decimate=decimate, vertices=counts[0][0], triangles=counts[0][1], triangles_before=counts[0].triangles_before,
+                                          triangles_before_decimate=counts[0].decimate['triangles_before'], rounds=counts[0].decimate['rounds'],
+                                          stopped=counts[0].decimate['stopped'])))
                 if texture is not None:
                     atlas = counts[0].atlas
                     print(json.dumps(dict(name=name, texture_texels=atlas.texels, atlas=[atlas.width, atlas.height], tiles_per_row=atlas.tiles_per_row,

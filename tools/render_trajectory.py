@@ -13,7 +13,8 @@ the rays and shaded (`--shape-mode shaded | normals | colour`, `--num-refine`, `
 `--vis mesh_grid` / `--vis mesh_strips`: the same layouts of MESH frames -- the surface extracted once per sample (`--volume-res`, `--cube-size`,
 marching cubes at `--level`) and rasterised for every frame; `--mesh-normals face` shades the flat facets, `vertex` interpolates the mesh's own vertex normals, `field` takes the normals from the field;
 `--mesh-smooth-iters N` Taubin-smooths every mesh on the device before it is drawn; `--mesh-simplify-cell X` then clusters its vertices in cells of
-X voxels (quadric placement) and draws the simplified mesh; `--mesh-texture-texels N` bakes a texture of N texels per triangle leg from the field
+X voxels (quadric placement) and draws the simplified mesh; `--mesh-decimate-triangles N` collapses edges until at most N triangles are left
+(the surface stays closed and of the same topology); `--mesh-texture-texels N` bakes a texture of N texels per triangle leg from the field
 on every final mesh and draws the frames in colour mode from it (`--mesh-texture-filter nearest | bilinear`); `--mesh-samples 4 | 16` draws the
 frames with 4 or 16 coverage samples per pixel (anti-aliased silhouettes; face or vertex normals).
 """
@@ -69,6 +70,11 @@ class _Parser(argparse.ArgumentParser):
                 self.error('--mesh-simplify-cell needs --vis mesh_grid or mesh_strips')
             if not 0 < a.mesh_simplify_cell < float('inf'):
                 self.error(f'--mesh-simplify-cell takes a positive finite number, got {a.mesh_simplify_cell}')
+        if a.mesh_decimate_triangles is not None:
+            if not a.vis.startswith('mesh_'):
+                self.error('--mesh-decimate-triangles needs --vis mesh_grid or mesh_strips')
+            if a.mesh_decimate_triangles < 0:
+                self.error(f'--mesh-decimate-triangles takes a non-negative integer, got {a.mesh_decimate_triangles}')
         if a.mesh_texture_texels is not None or a.mesh_texture_filter is not None:
             if not a.vis.startswith('mesh_'):
                 self.error('--mesh-texture-texels and --mesh-texture-filter need --vis mesh_grid or mesh_strips')
@@ -124,6 +130,8 @@ def build_parser():
     p.add_argument('--mesh-smooth-iters', type=int, default=0, metavar='N', help='mesh frames: Taubin-smooth each mesh, N lambda | mu iterations (default: none)')
     p.add_argument('--mesh-simplify-cell', type=float, default=None, metavar='X',
                    help='mesh frames: simplify each mesh on the device, one vertex per cell of X voxels, placed by its error quadric (default: none)')
+    p.add_argument('--mesh-decimate-triangles', type=int, default=None, metavar='N',
+                   help='mesh frames: collapse edges of each mesh on the device until at most N triangles are left; the surface stays closed (default: none)')
     p.add_argument('--mesh-texture-texels', type=int, default=None, metavar='N',
                    help='mesh frames: bake a texture of N texels per triangle leg (2..64) on each final mesh and draw it (implies --shape-mode colour; default: none)')
     p.add_argument('--mesh-texture-filter', choices=['nearest', 'bilinear'], default=None, help='mesh frames: how the texture is fetched (default bilinear)')
@@ -172,6 +180,7 @@ def mesh_options(args):
                 ambient=args.ambient, background=(args.background,) * 3, plane_batch=args.plane_batch, components=component_options(args),
                 smooth=dict(iterations=args.mesh_smooth_iters) if args.mesh_smooth_iters > 0 else None,
                 simplify=dict(cell=args.mesh_simplify_cell) if args.mesh_simplify_cell is not None else None, **({'texture': texture} if texture else {}),
+                **({'decimate': dict(target_triangles=args.mesh_decimate_triangles)} if args.mesh_decimate_triangles is not None else {}),
                 **({'samples': args.mesh_samples} if (args.mesh_samples or 1) > 1 else {}))
 
 
@@ -222,6 +231,9 @@ def main(argv=None):
                     vertices=[v for v, _ in counts], triangles=[t for _, t in counts], components=component_options(args),
                     mesh_smooth_iters=args.mesh_smooth_iters, mesh_simplify_cell=args.mesh_simplify_cell,
                     triangles_before_simplify=[c.triangles_before for c in counts], mesh_samples=args.mesh_samples or 1)
+        if args.mesh_decimate_triangles is not None:
+            line.update(mesh_decimate_triangles=args.mesh_decimate_triangles, decimate_rounds=[c.decimate['rounds'] for c in counts],
+                        decimate_stopped=[c.decimate['stopped'] for c in counts])
         if args.mesh_texture_texels is not None:
             line.update(shape_mode='colour', mesh_texture_texels=args.mesh_texture_texels, mesh_texture_filter=args.mesh_texture_filter or 'bilinear',
                         atlas=[[c.atlas.width, c.atlas.height] for c in counts])
