@@ -21,6 +21,7 @@ The directory name starts with a digit, so import it with ``importlib.import_mod
   mesh_surface         corner table of the extracted mesh: vertex normals, Taubin smoothing, open rims (smooth-shaded mesh frames, normals in .obj / .ply)
   mesh_simplify        vertex clustering of the extracted mesh with quadric placement: a tenth of the triangles, creases kept, on the device
   mesh_decimate        quadric edge collapse in rounds: N triangles or an error bound, the surface stays closed, oriented, of the same topology
+  mesh_distance        how far one mesh is from another: triangle grid, closest points, sampled two-sided distance (Hausdorff, mean, RMS), error colours
   mesh_texture         a per-triangle texture atlas of the extracted mesh baked from the field: textured mesh frames, .obj with vt / .mtl / .png
   mesh_build           the mesh of one sample from its planes, every stage in order: the one build behind extract_geometry and the mesh frames
   augment              the ADA augmentation pipe: per-sample parameters, geometry, colour, noise and cutout on the device, with adjoints
@@ -37,7 +38,7 @@ from .config import GeneratorConfig  # noqa: F401
 
 def __getattr__(name):
     # torch-dependent submodules are imported on first use
-    if name in ('_lib', 'ops', 'renderer', 'generator', 'adaptors', 'metrics', 'inference', 'discriminator', 'training', 'compat', 'distributed', 'build', 'graphs', 'geometry', 'shapes', 'mesh', 'mesh_components', 'mesh_surface', 'mesh_simplify', 'mesh_decimate', 'mesh_texture', 'mesh_build', 'augment', 'step_tail', 'dataset', 'training_loop', 'instance_selection', 'images', 'data_tools'):
+    if name in ('_lib', 'ops', 'renderer', 'generator', 'adaptors', 'metrics', 'inference', 'discriminator', 'training', 'compat', 'distributed', 'build', 'graphs', 'geometry', 'shapes', 'mesh', 'mesh_components', 'mesh_surface', 'mesh_simplify', 'mesh_decimate', 'mesh_distance', 'mesh_texture', 'mesh_build', 'augment', 'step_tail', 'dataset', 'training_loop', 'instance_selection', 'images', 'data_tools'):
         import importlib
         return importlib.import_module(f'{__name__}.{name}')
     raise AttributeError(name)

@@ -117,7 +117,17 @@ _PROTOTYPES = {
     'tdgp_mesh_decimate_gather_workspace_bytes': (c_int64, [c_int64]),
     'tdgp_mesh_decimate_gather_count': (c_int, [P, c_int64, P, c_int64, P]),
     'tdgp_mesh_decimate_gather': (c_int, [P, P, c_int, P, c_int64, c_int64, P, c_int64, P, c_int64, P, P, P]),
-    'tdgp_atlas_points': (c_int, [P, c_int64, P, c_int64, c_int, c_int, c_int, c_int, P, P, P]),
+    'tdgp_mesh_distance_prepare': (c_int, [P, P, c_int64, c_int64, P, P, P, P]),
+    'tdgp_mesh_distance_grid_count': (c_int, [P, P, c_int64, POINTER(c_float), c_float, POINTER(c_int), P, P]),
+    'tdgp_mesh_distance_scan_workspace_bytes': (c_int64, [c_int64]),
+    'tdgp_mesh_distance_grid_emit': (c_int, [P, P, c_int64, POINTER(c_float), c_float, POINTER(c_int), P, c_int64, P, P, c_int64, P]),
+    'tdgp_mesh_distance_cell_start': (c_int, [P, c_int64, c_int64, P, P]),
+    'tdgp_mesh_distance_closest': (c_int, [P, c_int64, P, P, c_int64, c_int64, P, POINTER(c_float), c_float, POINTER(c_int), P, P, c_int64, c_int, P, P, P, P, P, P]),
+    'tdgp_mesh_distance_sample_count': (c_int, [P, P, c_int64, c_int64, P, c_float, P, P]),
+    'tdgp_mesh_distance_sample_emit': (c_int, [P, P, c_int64, c_int64, P, c_float, P, c_int64, P, P, P, c_int64, P]),
+    'tdgp_mesh_distance_reduce_workspace_bytes': (c_int64, [c_int64]),
+    'tdgp_mesh_distance_reduce': (c_int, [P, P, c_int64, P, c_int64, P]),
+    'tdgp_atlas_points':(c_int, [P, c_int64, P, c_int64, c_int, c_int, c_int, c_int, P, P, P]),
     'tdgp_atlas_texels': (c_int, [P, c_int64, P, c_int64, P, P, P]),
     'tdgp_mesh_sample_texture': (c_int, [P, P, P, P, P, c_int64, P, c_int64, P, c_int64, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     'tdgp_quantile_select_workspace_bytes': (c_int64, [c_int64]),

@@ -79,7 +79,7 @@ def decimate(vertices, triangles, target_triangles=None, max_error=None, max_rou
     rounds, stopped).  Edges are collapsed, cheapest first within every neighbourhood, until at most `target_triangles` are left ('target'), a
     round selects nothing ('exhausted') or `max_rounds` have run ('max_rounds'); rounds counts every round run, the empty last one included.
     max_error (in the units of `vertices`): a collapse is allowed only while the area-weighted RMS distance of the new vertex to the planes
-    accumulated in it stays within the bound (not a Hausdorff bound).  With both, a collapse satisfies the bound and the loop stops at the
+    accumulated in it stays within the bound (not a Hausdorff bound; `mesh_distance.mesh_distance` measures that).  With both, a collapse satisfies the bound and the loop stops at the
     target.  A vertex leaves only by being merged into another; survivors keep their order (a vertex no triangle names stays), and
     vertex_map[v] is the output index of the vertex v ended up in.  Surviving triangles keep their order; triangle_map[j] is the input index
     of output triangle j.  A triangle with an index outside [0, V) or a repeated index is dropped in front of round 0.  fix_boundary: the rim

@@ -870,7 +870,7 @@ int     tdgp_mesh_cluster_attribute(const float* attribute, int channels, int64_
  *   csrc/quadric_solve.h serves both) started from m = (p_a + p_b) * 0.5, and m itself if any x_c is not finite;
  *   Ax_c = (A_c0*x_0 + A_c1*x_1) + A_c2*x_2,  cost = (((x_0*Ax_0 + x_1*Ax_1) + x_2*Ax_2) + 2 * ((bv_0*x_0 + bv_1*x_1) + bv_2*x_2)) + Q_33;
  *   cost is not NaN, and below 0 it counts as 0;  with a bound, cost <= (max_error*max_error) * w: the area-weighted RMS distance to the
- *   accumulated planes, not the Hausdorff distance;  no flip: for every corner of a whose triangle does not name b (then of b, not naming a),
+ *   accumulated planes, not the Hausdorff distance (that one is measured by the mesh-distance block below);  no flip: for every corner of a whose triangle does not name b (then of b, not naming a),
  *   with p the triangle's positions in slot order and p' the same with that corner's slot moved to x,  n0 = cross(p1-p0, p2-p0),
  *   n1 = cross(p'1-p'0, p'2-p'0),  (n0_0*n1_0 + n0_1*n1_1) + n0_2*n1_2 > 0.
  *   Then key = (bits of (float)cost << 32) | mix(k), with mix(h): h ^= h >> 16; h *= 0x7feb352d; h ^= h >> 15; h *= 0x846ca68b; h ^= h >> 16
@@ -909,6 +909,83 @@ int     tdgp_mesh_decimate_gather_count(const int32_t* parent, int64_t V, void* 
 int     tdgp_mesh_decimate_gather(const double* position, const double* attribute, int channels, const int32_t* parent, int64_t V,
                                   int64_t max_hops, void* workspace, int64_t workspace_bytes, float* out_vertices, int64_t V_out,
                                   float* out_attribute, int32_t* vertex_map, tdgp_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Mesh distance (csrc/mesh_distance.hip; the reference's users measure a simplified mesh against its source in MeshLab / Metro): a uniform
+ * grid over the triangles, the closest point of a mesh per query point, surface samples, and the statistics of their distances -- the
+ * sampled two-sided surface distance (maximum = Hausdorff, area-weighted mean and RMS) that `max_error` above is NOT.
+ *   grid:    _prepare -> [bounds, count and area sum read back] -> per try: _grid_count -> [the pair total read back; too many cells or pairs:
+ *            the cell doubles] -> _grid_emit -> [a STABLE sort of the pairs by cell: plumbing] -> _cell_start
+ *   query:   _closest (the walk through the grid, or brute_force = 1: the scan over all triangles)
+ *   samples: _prepare -> _sample_count -> [the total read back] -> _sample_emit;   statistics: _closest -> _reduce -> [one read-back]
+ * Common: the rules of the mesh blocks above, unchanged (checked arguments, empty inputs, caller-owned workspaces sized by a query that
+ * answers -1 for sizes it refuses, no waiting between workgroups, no floating-point atomics, positions from scans only, every
+ * floating-point operation in DOUBLE on the fp32 inputs widened exactly, rounded once in the order written, `/` and sqrt correctly
+ * rounded).  T, V, N, P, S <= 2^31 - 1.  dot(x, y) = (x_0*y_0 + x_1*y_1) + x_2*y_2;  cross(x, y) = (x_1*y_2 - x_2*y_1, x_2*y_0 - x_0*y_2,
+ * x_0*y_1 - x_1*y_0).  A triangle is VALID when its three indices are distinct and inside [0, V) and its nine coordinates are finite; the
+ * others are never dereferenced and never listed.  Triangle ids always are indices into the input array.
+ *
+ * THE DISTANCE d2(p; a, b, c) and the closest point q:  ab = b - a, ac = c - a, ap = p - a, n = cross(ab, ac), nn = dot(n, n).
+ *   Face case, when nn > 0 and dot(cross(c - b, p - b), n) >= 0 and dot(cross(a - c, p - c), n) >= 0 and dot(cross(ab, ap), n) >= 0:
+ *   s = dot(ap, n), f = s / nn, q = p - n*f, d2 = s*s / nn.   Otherwise d2 = +inf and, for (x, y) = (a, b), (b, c), (c, a) in that order:
+ *   e = y - x, ee = dot(e, e), t = 0 when ee == 0 else dot(p - x, e) / ee clamped into [0, 1], r = x + t*e, dd = dot(p - r, p - r); dd < d2
+ *   replaces (d2, q) by (dd, r).  A collinear or point-like triangle has nn == 0 and is the union of its edges.  The closest triangle of a
+ *   point has the smallest d2, ties to the smallest id: any traversal that never skips it returns the bits of the scan over all triangles.
+ *
+ * tdgp_mesh_distance_prepare: valid uint8 [T];  box fp32 [T,6] = the minimum and the maximum of the three vertices per axis (zeros when not
+ *   valid);  area double [T] = 0.5 * sqrt(nn) (0 when not valid).
+ * THE GRID (lo fp32 [3], cell fp32 > 0, dims int [3], each >= 1, their product <= 2^24; host memory):  the cell of a coordinate x on axis k
+ *   is floor((x - lo_k) / cell) clamped into [0, dims_k - 1];  cell (cx, cy, cz) has the key (cz*dims_1 + cy)*dims_0 + cx.  The caller takes
+ *   lo / hi = the minimum / maximum of the boxes of valid triangles, dims_k = floor((hi_k - lo_k) / cell) + 1, and the default cell
+ *   (float)(2 * sqrt(area sum / valid count)) with the area summed by tdgp_mesh_distance_reduce.
+ * tdgp_mesh_distance_grid_count: counts int32 [T] = the number of cells the box of a valid triangle overlaps (the product of its three cell
+ *   ranges), 0 when not valid.
+ * tdgp_mesh_distance_grid_emit: pair_cell / pair_triangle int32 [P], P = the sum of the counts: triangle t writes its cells (z outermost, x
+ *   innermost) from the exclusive scan of the counts on.  Sorted by cell with a stable sort, every cell's list ascends in triangle id.
+ * tdgp_mesh_distance_cell_start: cell_start int32 [cells + 1] from the sorted keys: cell_start[c] = the number of pairs with a key < c.
+ * tdgp_mesh_distance_closest: one lane per point.  A point with a coordinate that is not finite: sqdist = distance = closest = NaN,
+ *   triangle = -1, nothing is walked.  Else the minimum of d2 over the valid triangles (brute_force) or over the walk:  c_k = the point's
+ *   cell, a_k = p_k - lo_k;  for r = 0, 1, ... max(dims) - 1: every cell at Chebyshev distance exactly r from c that lies in the grid has its
+ *   list evaluated;  then for every axis k, with g = (|a_k| + mc) * 2^-48:  if c_k - r > 0 the low side is open, mc = (c_k - r)*cell (an exact
+ *   product) and its distance is max(0, (a_k - mc) - g);  if c_k + r < dims_k - 1 the high side is open, mc = (c_k + r + 1)*cell and its
+ *   distance is max(0, (mc - a_k) - g).  No open side: stop.  lb = the smallest of them: stop when (lb*lb) * (1 - 2^-40) > the running
+ *   minimum.  (A triangle no visited cell lists lies wholly beyond one open side; g covers the rounding of the cell arithmetic, the factor
+ *   that of d2 itself on triangles that are not needles.)  The loop ends after max(dims) shells at the latest.
+ *   Outputs: sqdist double [N] = d2, distance fp32 [N] = (float)sqrt(d2), triangle int32 [N], closest fp32 [N,3] = q rounded once;  no valid
+ *   triangle (or P == 0 on the walk): +inf, +inf, -1, NaN.  evaluated int32 [N] or NULL: the number of d2 evaluations of the point.
+ * tdgp_mesh_distance_sample_count: counts int32 [T] = k*k + 3 for a valid triangle, k = ceil(sqrt(the largest of dot(e, e) over b - a, c - b,
+ *   a - c) / spacing) clamped into [1, 64];  0 when not valid.
+ * tdgp_mesh_distance_sample_emit: S = the sum of the counts.  From the exclusive scan of the counts on, triangle t writes: its three
+ *   vertices, weight 0;  then for i = 0 .. k-1, j = 0 .. k-1-i:  u = (i + 1/3) / k, v = (j + 1/3) / k (1/3 the double constant);  then for
+ *   i = 0 .. k-2, j = 0 .. k-2-i:  u = (i + 2/3) / k, v = (j + 2/3) / k;  the point (float)((a + u*ab) + v*ac) per axis, weight
+ *   (0.5 * sqrt(nn)) / (k*k), triangle t.
+ * tdgp_mesh_distance_reduce: weight double [N], distance fp32 [N] or NULL -> at the START of the workspace five 8-byte fields: the sums of w,
+ *   of w*d and of w*(d*d) (d widened; the last two 0 without distances), the maximum of d as a double, its index as int64 (the lowest index
+ *   among equals; NaN never is the maximum; -1 when there is none).  THE ORDER: block b of 256 holds elements 256 b .. 256 b + 255, zeros
+ *   past N, and slot i takes slot i + s for s = 128, 64, ... 1;  then ONE block: slot t adds the block results t, t + 256, ... in that
+ *   order, starting from 0, and the same tree follows.
+ * --------------------------------------------------------------------------------------------- */
+int     tdgp_mesh_distance_prepare(const float* vertices, const int32_t* triangles, int64_t T, int64_t V, uint8_t* valid, float* box,
+                                   double* area, tdgp_stream_t stream);
+int     tdgp_mesh_distance_grid_count(const float* box, const uint8_t* valid, int64_t T, const float* lo, float cell, const int* dims,
+                                      int32_t* counts, tdgp_stream_t stream);
+int64_t tdgp_mesh_distance_scan_workspace_bytes(int64_t T);
+int     tdgp_mesh_distance_grid_emit(const float* box, const int32_t* counts, int64_t T, const float* lo, float cell, const int* dims,
+                                     void* workspace, int64_t workspace_bytes, int32_t* pair_cell, int32_t* pair_triangle, int64_t P,
+                                     tdgp_stream_t stream);
+int     tdgp_mesh_distance_cell_start(const int32_t* sorted_cell, int64_t P, int64_t cells, int32_t* cell_start, tdgp_stream_t stream);
+int     tdgp_mesh_distance_closest(const float* points, int64_t N, const float* vertices, const int32_t* triangles, int64_t T, int64_t V,
+                                   const uint8_t* valid, const float* lo, float cell, const int* dims, const int32_t* cell_start,
+                                   const int32_t* pair_triangle, int64_t P, int brute_force, double* sqdist, float* distance,
+                                   int32_t* triangle, float* closest, int32_t* evaluated, tdgp_stream_t stream);
+int     tdgp_mesh_distance_sample_count(const float* vertices, const int32_t* triangles, int64_t T, int64_t V, const uint8_t* valid,
+                                        float spacing, int32_t* counts, tdgp_stream_t stream);
+int     tdgp_mesh_distance_sample_emit(const float* vertices, const int32_t* triangles, int64_t T, int64_t V, const int32_t* counts,
+                                       float spacing, void* workspace, int64_t workspace_bytes, float* points, double* weight,
+                                       int32_t* triangle, int64_t S, tdgp_stream_t stream);
+int64_t tdgp_mesh_distance_reduce_workspace_bytes(int64_t N);
+int     tdgp_mesh_distance_reduce(const double* weight, const float* distance, int64_t N, void* workspace, int64_t workspace_bytes,
+                                  tdgp_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Mesh textures (csrc/mesh_texture.hip; the reference's users bake a texture in MeshLab / Blender after decimating): a per-triangle atlas

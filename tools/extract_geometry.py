@@ -73,6 +73,9 @@ def build_parser():
     # and the texture (mesh_texture.py): a per-triangle atlas baked from the field on the final mesh, written next to the .obj
     p.add_argument('--texture-texels', type=int, default=argparse.SUPPRESS, metavar='N',
                    help='bake a texture of N texels per triangle leg (2..64) and write NAME.obj with vt lines, NAME.mtl and NAME.png (needs --save-obj; default: none)')
+    # and the distance report (mesh_distance.py): how far the simplified / decimated result is from the mesh it came from
+    p.add_argument('--distance-report', action='store_true', default=argparse.SUPPRESS,
+                   help='with simplification or decimation on: print the sampled two-sided surface distance (Hausdorff, mean, RMS) of the result to the unsimplified mesh')
     return p
 
 
@@ -204,6 +207,14 @@ def main(argv=None):
                     print(json.dumps(dict(name=name, decimate=decimate, vertices=counts[0][0], triangles=counts[0][1], triangles_before=counts[0].triangles_before,
                                           triangles_before_decimate=counts[0].decimate['triangles_before'], rounds=counts[0].decimate['rounds'],
                                           stopped=counts[0].decimate['stopped'])))
+                if getattr(args, 'distance_report', False) and (simplify is not None or decimate is not None):
+                    # one more extraction with everything but the simplification and the decimation: the mesh the result came from, same units
+                    full = geometry.extract_geometry(G, w, volume_res=args.volume_res, voxel_origin=args.voxel_origin, cube_size=args.cube_size,
+                                                     thresh_value=args.thresh_value, crop='reference', normalize=True, components=comp, smooth=smooth)[0]
+                    d = tdgp.mesh_distance.mesh_distance(shape.vertices, shape.triangles, full.vertices, full.triangles)
+                    print(json.dumps(dict(name=name, distance=dict(hausdorff=d.hausdorff, mean=d.mean, rms=d.rms, result_to_full_max=d.a_to_b.max,
+                                                                   full_to_result_max=d.b_to_a.max, samples=[d.a_to_b.samples, d.b_to_a.samples]),
+                                          triangles=int(shape.triangles.shape[0]), triangles_full=int(full.triangles.shape[0]))))
                 if texture is not None:
                     atlas = counts[0].atlas
                     print(json.dumps(dict(name=name, texture_texels=atlas.texels, atlas=[atlas.width, atlas.height], tiles_per_row=atlas.tiles_per_row,
