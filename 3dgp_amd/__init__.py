@@ -22,6 +22,7 @@ The directory name starts with a digit, so import it with ``importlib.import_mod
   mesh_simplify        vertex clustering of the extracted mesh with quadric placement: a tenth of the triangles, creases kept, on the device
   mesh_decimate        quadric edge collapse in rounds: N triangles or an error bound, the surface stays closed, oriented, of the same topology
   mesh_distance        how far one mesh is from another: triangle grid, closest points, sampled two-sided distance (Hausdorff, mean, RMS), error colours
+  mesh_rays            what a ray hits on a mesh: first hit / any hit through the triangle grid, segment visibility, ambient occlusion per point or vertex
   mesh_texture         a per-triangle texture atlas of the extracted mesh baked from the field: textured mesh frames, .obj with vt / .mtl / .png
   mesh_build           the mesh of one sample from its planes, every stage in order: the one build behind extract_geometry and the mesh frames
   augment              the ADA augmentation pipe: per-sample parameters, geometry, colour, noise and cutout on the device, with adjoints
@@ -38,7 +39,7 @@ from .config import GeneratorConfig  # noqa: F401
 
 def __getattr__(name):
     # torch-dependent submodules are imported on first use
-    if name in ('_lib', 'ops', 'renderer', 'generator', 'adaptors', 'metrics', 'inference', 'discriminator', 'training', 'compat', 'distributed', 'build', 'graphs', 'geometry', 'shapes', 'mesh', 'mesh_components', 'mesh_surface', 'mesh_simplify', 'mesh_decimate', 'mesh_distance', 'mesh_texture', 'mesh_build', 'augment', 'step_tail', 'dataset', 'training_loop', 'instance_selection', 'images', 'data_tools'):
+    if name in ('_lib', 'ops', 'renderer', 'generator', 'adaptors', 'metrics', 'inference', 'discriminator', 'training', 'compat', 'distributed', 'build', 'graphs', 'geometry', 'shapes', 'mesh', 'mesh_components', 'mesh_surface', 'mesh_simplify', 'mesh_decimate', 'mesh_distance', 'mesh_rays', 'mesh_texture', 'mesh_build', 'augment', 'step_tail', 'dataset', 'training_loop', 'instance_selection', 'images', 'data_tools'):
         import importlib
         return importlib.import_module(f'{__name__}.{name}')
     raise AttributeError(name)

@@ -127,6 +127,9 @@ _PROTOTYPES = {
     'tdgp_mesh_distance_sample_emit': (c_int, [P, P, c_int64, c_int64, P, c_float, P, c_int64, P, P, P, c_int64, P]),
     'tdgp_mesh_distance_reduce_workspace_bytes': (c_int64, [c_int64]),
     'tdgp_mesh_distance_reduce': (c_int, [P, P, c_int64, P, c_int64, P]),
+    'tdgp_mesh_rays_cast': (c_int, [P, P, c_int64, c_double, c_double, P, P, c_int64, c_int64, P, POINTER(c_float), c_float, POINTER(c_int), P, P, c_int64, c_int, c_int,
+                                    P, P, P, P, P, P, P, P]),
+    'tdgp_mesh_rays_ao': (c_int, [P, P, c_int64, P, c_int, c_int, c_float, c_float, P, P, c_int64, c_int64, POINTER(c_float), c_float, POINTER(c_int), P, P, c_int64, P, P]),
     'tdgp_atlas_points':(c_int, [P, c_int64, P, c_int64, c_int, c_int, c_int, c_int, P, P, P]),
     'tdgp_atlas_texels': (c_int, [P, c_int64, P, c_int64, P, P, P]),
     'tdgp_mesh_sample_texture': (c_int, [P, P, P, P, P, c_int64, P, c_int64, P, c_int64, P, c_int, c_int, c_int, c_int, c_int, P, P]),

@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(CSRC, 'libtdgp_hip.so')
-SOURCES = ['core.hip', 'bias_act.hip', 'upfirdn2d.hip', 'modconv.hip', 'conv_grad.hip', 'camera_rays.hip', 'frames_grid.hip', 'field.hip', 'field_deep.hip', 'sampling.hip', 'render_grad.hip', 'render_fused.hip', 'geometry.hip', 'iso_surface.hip', 'mesh_raster.hip', 'mesh_components.hip', 'mesh_surface.hip', 'mesh_simplify.hip', 'mesh_decimate.hip', 'mesh_distance.hip', 'mesh_texture.hip', 'metrics.hip', 'pair_dist.hip', 'gaussian.hip', 'augment.hip', 'step_tail.hip', 'resample.hip']
+SOURCES = ['core.hip', 'bias_act.hip', 'upfirdn2d.hip', 'modconv.hip', 'conv_grad.hip', 'camera_rays.hip', 'frames_grid.hip', 'field.hip', 'field_deep.hip', 'sampling.hip', 'render_grad.hip', 'render_fused.hip', 'geometry.hip', 'iso_surface.hip', 'mesh_raster.hip', 'mesh_components.hip', 'mesh_surface.hip', 'mesh_simplify.hip', 'mesh_decimate.hip', 'mesh_distance.hip', 'mesh_rays.hip', 'mesh_texture.hip', 'metrics.hip', 'pair_dist.hip', 'gaussian.hip', 'augment.hip', 'step_tail.hip', 'resample.hip']
 HEADERS = ['common.h', 'device_scan.h', 'shade.h', 'mesh_bary.h', 'mesh_hit.h', 'quadric_solve.h', 'modconv_bf16.inc', 'modconv_wino.inc', 'modconv_wino4.inc', 'modconv_wino4f.inc', 'modconv_host.inc', 'field_body.inc', 'field_grad.inc', 'field_walk2.inc', 'mc_table.inc', os.path.join('..', '..', 'include', 'tdgp.h')]
 # -ffp-contract=off: fp32 chains that decide integer rows must round like the reference's eager ops;
 # fused multiply-adds are written explicitly (fmaf_) where wanted.

@@ -21,6 +21,7 @@ from . import renderer as _renderer
 
 Shape = collections.namedtuple('Shape', ['vertices', 'triangles', 'sigma'])
 TexturedShape = collections.namedtuple('TexturedShape', ['vertices', 'triangles', 'sigma', 'texture'])
+OccludedShape = collections.namedtuple('OccludedShape', ['vertices', 'triangles', 'sigma', 'texture', 'occlusion'])
 
 
 class MeshCount(tuple):
@@ -175,7 +176,7 @@ def grid_to_world(vertices, volume_res, voxel_origin=(0.0, 0.0, 0.0), cube_size=
 @torch.no_grad()
 def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=0.3, thresh_value=25.0, crop='reference', normalize=True,
                      slab_points=2 ** 22, noise_mode='const', units='index', sheared=True, components=None, smooth=None, simplify=None,
-                     return_counts=False, texture=None, decimate=None):
+                     return_counts=False, texture=None, decimate=None, ao=None):
     """scripts/extract_geometry.py:26-42 per sample of `ws`: density grid -> crop -> marching cubes -> (optionally) scale.  Returns a list of
     Shape(vertices [V,3] fp32, triangles [T,3] int32, sigma [D,H,W] fp32 -- the cropped grid), all on the device.
     crop: 'reference' (extract_geometry.py:33), None, or three slices.  normalize: divide the vertices by the length of their bounding-box
@@ -185,11 +186,13 @@ def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_s
     components, smooth, simplify, decimate, texture: the stages of `mesh_build.check_stages`, run on the marching-cubes output BEFORE it is scaled
     (`normalize` divides by the diagonal of the finished mesh; vertex normals are the caller's: `mesh_surface.vertex_normals` of the final
     vertices).  With texture= every item is a TexturedShape(vertices, triangles, sigma, texture) whose `texture` is a `mesh_texture.Texture`,
-    baked on the `grid_to_world` vertices WHATEVER `units` returns.  return_counts=True: also a list of `MeshCount` per sample."""
+    baked on the `grid_to_world` vertices WHATEVER `units` returns.  return_counts=True: also a list of `MeshCount` per sample.
+    ao: dict(rays=32, radius=None, bias=None): every item is an OccludedShape(vertices, triangles, sigma, texture or None, occlusion) whose
+    `occlusion` is `mesh_rays.vertex_occlusion` of the finished mesh in world units (fp32 [V] in [0, 1]; `save_ply(colours=)` takes it as grey)."""
     if units not in ('index', 'world'):
         raise ValueError(f"units must be 'index' or 'world', got {units!r}")
     from . import mesh_build as _mesh_build          # the mesh modules behind it import this one
-    stages = _mesh_build.check_stages(components, smooth, simplify, texture, decimate)
+    stages = _mesh_build.check_stages(components, smooth, simplify, texture, decimate, ao)
     crop = _crop_slices(crop, volume_res)
     out, counts = [], []
     for b in range(ws.shape[0]):               # one sample's grid alive at a time, as the reference loops
@@ -206,6 +209,9 @@ def extract_geometry(G, ws, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_s
             if float(diag) > 0:
                 verts = verts / diag
         counts.append(m.count)
+        if m.occlusion is not None:
+            out.append(OccludedShape(verts, m.triangles, m.sigma, m.texture, m.occlusion))
+            continue
         out.append(Shape(verts, m.triangles, m.sigma) if m.texture is None else TexturedShape(verts, m.triangles, m.sigma, m.texture))
     return (out, counts) if return_counts else out
 

@@ -277,7 +277,7 @@ FIELDS = (('rgb', (3,), torch.float32), ('depth', (1,), torch.float32), ('normal
 @torch.no_grad()
 def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shaded', normals='face', cull='none', near=None, planes=None, G=None,
                       vertex_colours=None, light=None, ambient=0.2, albedo=(0.8, 0.8, 0.8), background=(1.0, 1.0, 1.0), max_rays_per_call=None,
-                      t_miss=None, step=None, vertex_normals=None, texture=None, texture_filter='bilinear', samples=1):
+                      t_miss=None, step=None, vertex_normals=None, texture=None, texture_filter='bilinear', samples=1, vertex_occlusion=None):
     """C frames of ONE mesh (vertices [V,3] fp32 in world units, triangles [T,3] int32, on the device) under C cameras (`camera_params`: angles,
     radius, look_at, fov as the renderer takes them) at `resolution` (a side, or (w, h)).
 
@@ -302,8 +302,14 @@ def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shad
     (tdgp_mesh_visibility_ms -> tdgp_mesh_resolve_ms, 8 bytes per sample between them): rgb is the mean of the sample colours over
     `background`, and the group gains coverage [C,R], the fraction of the pixel's samples the mesh covers (composite another background B as
     rgb + (1 - coverage) * (B - background)).  status is 1 where any sample hit; depth, tri and normal are those of the nearest hit sample.  The
-    frame stays on the pixel grid of the one-sample frame and of the renderer's frames of the same cameras.  The chunks shrink by `samples`."""
+    frame stays on the pixel grid of the one-sample frame and of the renderer's frames of the same cameras.  The chunks shrink by `samples`.
+    vertex_occlusion: None, or fp32 [V] in [0, 1] (`mesh_rays.vertex_occlusion`: 1 = open) that darkens the surface colour before it is lit.
+    mode='colour' with `vertex_colours`: the colours times it, one fp32 multiply; mode='shaded': the frame goes through the colour path with
+    albedo * occlusion as vertex colours.  With a texture, normals='field' or mode='normals' it is a ValueError."""
     _check_options(mode, normals, cull, max_rays_per_call, texture, texture_filter, samples)
+    if vertex_occlusion is not None and (texture is not None or normals == 'field' or mode == 'normals'):
+        raise ValueError(f"vertex_occlusion darkens vertex colours: it takes mode 'shaded' or 'colour' with face or vertex normals and no texture (got mode={mode!r}, "
+                         f"normals={normals!r}{', a texture' if texture is not None else ''})")
     # what those options need of this mesh: the field behind it, its colours, its normals
     if normals == 'field' and (planes is None or G is None):
         raise ValueError("normals='field' evaluates the field at the hits: it needs the generator G and the sample's planes (G.synthesis.tri_planes)")
@@ -319,6 +325,11 @@ def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shad
         # this mode is an option of a device mesh only (its corner table is built there): asking for it on a host mesh is a bad option value
         raise ValueError(f"normals='vertex' takes a mesh on the GPU (got {vertices.device}, {triangles.device}); the vertex normals have no CPU path")
     vertices, triangles = _check_mesh(vertices, triangles)
+    if vertex_occlusion is not None:
+        if not isinstance(vertex_occlusion, torch.Tensor) or vertex_occlusion.dtype != torch.float32 or tuple(vertex_occlusion.shape) != (int(vertices.shape[0]),) \
+                or vertex_occlusion.device != vertices.device:
+            raise ValueError(f'vertex_occlusion must be an fp32 [{int(vertices.shape[0])}] tensor on {vertices.device} (mesh_rays.vertex_occlusion), got '
+                             f'{getattr(vertex_occlusion, "dtype", type(vertex_occlusion).__name__)} {tuple(getattr(vertex_occlusion, "shape", ()))}')
     w, h = (int(resolution), int(resolution)) if np.isscalar(resolution) else (int(r) for r in resolution)
     if h < 2 or w < 2:
         raise ValueError(f'resolution must be at least 2 x 2, got {resolution!r}')
@@ -352,6 +363,10 @@ def render_mesh_views(vertices, triangles, camera_params, resolution, mode='shad
     vrgb = None
     if point_field is None and mode == 'colour' and texture is None:
         vrgb = vertex_colours if vertex_colours.dtype == torch.float32 else vertex_colours.float() / (255.0 if vertex_colours.dtype == torch.uint8 else 1.0)
+    if vertex_occlusion is not None:                # plumbing: the surface colour times the occlusion, then the colour path as it is
+        base = vrgb if mode == 'colour' else torch.tensor([float(a) for a in albedo], dtype=torch.float32, device=dev)[None, :]
+        vrgb = base * vertex_occlusion[:, None]
+        mode = 'colour'
     max_rays = 16 * R if max_rays_per_call is None else int(max_rays_per_call)
     cstep = max(1, min(max_rays, FIELD_POINTS_MAX // STENCIL) // (R * samples))
     shade = dict(mode=mode, light=light, ambient=ambient, albedo=albedo, background=background)
@@ -398,7 +413,7 @@ def _camera_slice(camera_params, device, c0, c1):
 @torch.no_grad()
 def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_origin=(0.0, 0.0, 0.0), cube_size=None, crop=None, sheared=True,
                        mode='shaded', normals='face', plane_batch=4, return_counts=False, components=None, smooth=None, simplify=None, texture=None, decimate=None,
-                       **kw):
+                       ao=None, **kw):
     """Mesh frames of every `ws` under its cameras (sample-major: camera n * V + v is view v of sample n).  Per sample: `mesh_build.build_mesh`
     -- the density grid at volume_res^3 over a cube of `cube_size` (default the whole field, 2 * cfg.cube_scale), marching cubes at `level`, the
     stages, `grid_to_world` -- then its V cameras through `render_mesh_views`.  The backbone runs once per plane batch; its planes feed the
@@ -406,6 +421,8 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
     -> TensorGroup(rgb [B*V,R,3], depth, normal, status, tri) as `render_mesh_views`; return_counts=True: also a `geometry.MeshCount` per sample.
     components, smooth, simplify, decimate, texture: the stages of `mesh_build.check_stages`.  Normals, vertex colours (mode 'colour') and counts are
     those of the finished mesh in world units; with a texture the frames take their colour from it (mode='colour', face or vertex normals).
+    ao: dict(rays=32, radius=None, bias=None): ambient occlusion per vertex of the finished mesh (`mesh_rays.vertex_occlusion`), handed to
+    `render_mesh_views(vertex_occlusion=)` -- mode 'shaded' or 'colour', face or vertex normals, no texture.
     kw: cull, near, light, ambient, albedo, background, max_rays_per_call, t_miss, step, samples of `render_mesh_views` (samples=4 | 16: multisampled
     frames, and the group gains `coverage`; the grids and strips below take it the same way)."""
     syn, cfg = G.synthesis, G.cfg
@@ -414,7 +431,9 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
     V = _renderer.views_per_sample(int(get('angles').shape[0]), num_samples, f'{num_samples} samples')
     if int(plane_batch) < 1:
         raise ValueError(f'plane_batch must be positive, got {plane_batch!r}')
-    stages = _mesh_build.check_stages(components, smooth, simplify, texture, decimate)
+    stages = _mesh_build.check_stages(components, smooth, simplify, texture, decimate, ao)
+    if stages.ao is not None and (texture is not None or normals == 'field' or mode == 'normals'):
+        raise ValueError(f"ao darkens vertex colours: it takes mode 'shaded' or 'colour' with face or vertex normals and no texture (got mode={mode!r}, normals={normals!r})")
     _check_options(mode, normals, kw.get('cull', 'none'), kw.get('max_rays_per_call'), texture, stages.texture_filter, kw.get('samples', 1))
     if syn.training:
         raise RuntimeError('render_mesh_frames is the inference route: call .eval() first (training mode renders patches with density noise)')
@@ -434,7 +453,8 @@ def render_mesh_frames(G, ws, camera_params, level=25.0, volume_res=256, voxel_o
             vc = vertex_colours(G, pb, m.world) if (mode == 'colour' and normals != 'field' and m.texture is None) else None
             cams = _camera_slice(camera_params, ws.device, (n0 + b) * V, (n0 + b + 1) * V)
             parts.append(render_mesh_views(m.world, m.triangles, cams, res, mode=mode, normals=normals, planes=pb if normals == 'field' else None, G=G,
-                                           vertex_colours=vc, **({} if m.texture is None else dict(texture=m.texture, texture_filter=stages.texture_filter)), **kw))
+                                           vertex_colours=vc, **({} if m.texture is None else dict(texture=m.texture, texture_filter=stages.texture_filter)),
+                                           **({} if m.occlusion is None else dict(vertex_occlusion=m.occlusion)), **kw))
     frames = parts[0] if len(parts) == 1 else TensorGroup.cat(parts, dim=0)
     return (frames, counts) if return_counts else frames
 

@@ -988,6 +988,81 @@ int     tdgp_mesh_distance_reduce(const double* weight, const float* distance, i
                                   tdgp_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Mesh rays (csrc/mesh_rays.hip; the reference's users cast rays and bake ambient occlusion in MeshLab / Blender): what a ray hits on a
+ * mesh, over THE GRID of the block above exactly as its entry points fill it (vertices, triangles, valid, lo, cell, dims, cell_start,
+ * pair_triangle: the members of one grid; a grid of more than one cell needs a finite cell).
+ *   tdgp_mesh_rays_cast  first hit or any hit of N rays, by the walk through the grid or (brute_force = 1) by the scan over all triangles
+ *   tdgp_mesh_rays_ao    ambient occlusion of N points: R rays per point in any-hit mode, the unoccluded ones counted
+ * Common: the rules of the block above, unchanged (checked arguments, N == 0 launches nothing, no workspace, no atomics, every
+ * floating-point operation in DOUBLE, rounded once in the order written, `/` and sqrt correctly rounded, comparisons ordered).
+ *
+ * THE RAY AND THE TRIANGLE, hit(o, d; a, b, c; t_min, t_max) with o, d doubles and the corners fp32 widened exactly (the translate / shear /
+ * scale form of Woop, Benthin and Wald, "Watertight Ray/Triangle Intersection", JCGT 2013):
+ *   per ray:  kz = the axis of the largest |d_k|, ties to the lowest index;  kx = (kz + 1) mod 3, ky = (kx + 1) mod 3, the two swapped when
+ *     d[kz] < 0;  Sx = d[kx] / d[kz],  Sy = d[ky] / d[kz],  Sz = 1 / d[kz].
+ *   per corner p of (a, b, c):  P = p - o per axis;  Px = P[kx] - Sx*P[kz],  Py = P[ky] - Sy*P[kz],  Pz = Sz*P[kz].
+ *   U = Cx*By - Cy*Bx,  V = Ax*Cy - Ay*Cx,  W = Bx*Ay - By*Ax.   A miss when one of U, V, W is < 0 and one is > 0 (zeros are inside).
+ *   det = (U + V) + W;  a miss when det == 0.   t = ((U*Az + V*Bz) + W*Cz) / det.   Accepted iff t_min <= t <= t_max.
+ *   Reported per hit: t;  bary = ((float)(V / det), (float)(W / det)), the weights of corners b and c (the convention of csrc/mesh_bary.h);
+ *   side = +1 when det > 0, else -1.  The map into the ray's frame keeps orientation (an even permutation and Sz > 0, or an odd one and
+ *   Sz < 0) and sends d to +z, and det = -(the z component of cross(B - A, C - A) in that frame): det > 0 iff the normal of the stored
+ *   winding, cross(b - a, c - a), points against d -- the ray meets the side that normal points to.
+ *   WATERTIGHT: (Px, Py) depends on p and the ray alone, never on the triangle.  For an edge (p, q) shared by two triangles, one holds it
+ *   as Qx*Py - Qy*Px and the other as Px*Qy - Py*Qx: products commute and x - y = -(y - x) exactly, so the two edge functions are the same
+ *   bits up to sign.  A ray for which one is < 0 finds the other > 0, and zeros are inside: no ray passes between two triangles that share
+ *   an edge.  (Plain Moeller-Trumbore, which forms its edges per triangle, does not have this property.)
+ *   THE HIT of a ray is the accepted VALID triangle with the smallest t, ties to the smallest index: independent of the visiting order, so
+ *   any traversal that never skips the minimiser returns the bits of the scan over all valid triangles (brute_force = 1, the yardstick).
+ *   A triangle whose projected area is at the rounding level of its edge functions (a needle seen end-on, a ray through the line of a
+ *   collinear triangle) can be accepted at a t that leaves its own box; only for such a hit may walk and scan differ.
+ *
+ * THE WALK (one lane per ray, one-wave blocks).  P == 0: nothing is hit.  A grid of ONE cell: its list is tested, nothing else is computed.
+ *   Else the axes are taken in the ray's order (x, y, z) = (kx, ky, kz), z the major one:  a_k = o_k - lo_k,  top_k = dims_k * cell,
+ *   mag = the sum over x, y, z in that order of ((|o_k| + |lo_k|) + top_k),  slack = mag * 2^-48  (everything the walk computes on any axis
+ *   is below mag, its roundings below 2^-50 mag).  floorcell(v, n) = floor(v / cell) clamped into [0, n - 1]: the very division and floor
+ *   that listed the triangles, so it is monotone against them.
+ *   1. The window:  t0 = t_min, t1 = t_max;  per axis x, y, z with the planes p0 = -slack, p1 = top_k + slack:  d_k == 0: nothing is hit
+ *      unless p0 <= a_k <= p1;  else ta = (p0 - a_k) / d_k, tb = (p1 - a_k) / d_k, t0 = max(t0, min(ta, tb)), t1 = min(t1, max(ta, tb)).
+ *      Nothing is hit unless t0 <= t1.
+ *   2. z0 = a_z + t0*d_z, z1 = a_z + t1*d_z;  up = d_z > 0;  s = floorcell(up ? z0 - slack : z0 + slack, dims_z), the last slab
+ *      floorcell(up ? z1 + slack : z1 - slack, dims_z).  At most dims_z slabs are taken, s moving by +1 (up) or -1:
+ *      ta = ((s*cell - slack) - a_z) * Sz,  tb = (((s + 1)*cell + slack) - a_z) * Sz  (s*cell is an exact product),
+ *      te = max(min(ta, tb), t0),  tx = min(max(ta, tb), t1).   STOP when te > the running minimum of t (any-hit: never).
+ *      When te <= tx:  xa = a_x + te*d_x, xb = a_x + tx*d_x, columns floorcell(min(xa, xb) - slack, dims_x) .. floorcell(max(xa, xb) + slack,
+ *      dims_x), rows likewise on y; the list of every cell of that rectangle in slab s is tested (y outer, x inner, the list in order).
+ *      STOP after the last slab.
+ *   Conservative: a hit at parameter t lies in its triangle's fp32 box, so some cell (cx, cy, cz) that lists the triangle has
+ *   cz*cell - g <= a_z + t*d_z <= (cz + 1)*cell + g with g far below slack; slab cz therefore is among those taken, its [te, tx] holds t,
+ *   and because |d_x|, |d_y| <= |d_z| the rectangle, grown by slack and mapped through the monotone floorcell, meets the triangle's
+ *   column and row ranges.  A triangle not yet tested has t >= te of every slab not yet taken (te never decreases), which is why the stop
+ *   is sound.  A triangle listed in several visited cells is tested again: the minimum cannot depend on it, and no "seen" set is kept.
+ *   Any-hit mode leaves at the first accepted triangle and reports only the flag.
+ *
+ * tdgp_mesh_rays_cast: origins, directions fp32 [N,3], widened exactly;  t_min finite, t_min <= t_max (t_max may be +inf; else
+ *   TDGP_EINVAL);  brute_force, any_hit in {0, 1}.  any_hit == 0 -> t double [N], depth fp32 [N] = (float)t, triangle int32 [N], bary fp32
+ *   [N,2], side int8 [N] (hit may be NULL);  a ray with a component that is not finite or with d == (0, 0, 0): NaN, NaN, -1, NaN, 0;  a
+ *   miss: +inf, +inf, -1, NaN, 0.  any_hit == 1 -> hit uint8 [N] only (the other five may be NULL): 1 iff some valid triangle is accepted
+ *   (0 for a bad ray), which is triangle >= 0 of the first-hit mode.  evaluated int32 [N] or NULL: the triangle tests of the ray.
+ * tdgp_mesh_rays_ao: points, normals fp32 [N,3];  tables fp32 [K,R,3] (unit directions round +z; the caller builds them), R in {16, 32, 64},
+ *   K a power of two <= 64;  bias fp32 >= 0 finite, radius fp32 > 0 (+inf allowed), both widened.  One lane per (point i, direction k), a
+ *   wave holds 64 / R points.  A point or a normal with a component that is not finite, or the normal (0, 0, 0): NaN.  Else
+ *   j = 0 when K == 1, else ((uint32)i * 2654435761u) >> (32 - log2 K);  (x, y, z) = tables[j][k] widened;
+ *   len = sqrt((n0*n0 + n1*n1) + n2*n2), N = (n0 / len, n1 / len, n2 / len);  the frame of Duff et al. ("Building an Orthonormal Basis,
+ *   Revisited", JCGT 2017):  sg = Nz >= 0 ? 1 : -1,  a = -1 / (sg + Nz),  b = (Nx*Ny) * a,
+ *   T = (1 + ((sg*Nx)*Nx)*a,  sg*b,  (-sg)*Nx),   B = (b,  sg + (Ny*Ny)*a,  -Ny);
+ *   d_c = (x*T_c + y*B_c) + z*N_c,   o_c = p_c + bias*N_c;   the ray (o, d) is cast by THE WALK in any-hit mode over [0, radius] (a ray that
+ *   is not finite or has d == 0 counts as unoccluded).  occlusion fp32 [N] = (float)(the number of unoccluded rays of the point) /
+ *   (float)R: one 64-bit ballot and a population count over the point's R lanes -- an integer, whatever the order; P == 0 gives 1.
+ * --------------------------------------------------------------------------------------------- */
+int     tdgp_mesh_rays_cast(const float* origins, const float* directions, int64_t N, double t_min, double t_max, const float* vertices,
+                            const int32_t* triangles, int64_t T, int64_t V, const uint8_t* valid, const float* lo, float cell, const int* dims,
+                            const int32_t* cell_start, const int32_t* pair_triangle, int64_t P, int brute_force, int any_hit, double* t,
+                            float* depth, int32_t* triangle, float* bary, int8_t* side, uint8_t* hit, int32_t* evaluated, tdgp_stream_t stream);
+int     tdgp_mesh_rays_ao(const float* points, const float* normals, int64_t N, const float* tables, int K, int R, float bias, float radius,
+                          const float* vertices, const int32_t* triangles, int64_t T, int64_t V, const float* lo, float cell, const int* dims,
+                          const int32_t* cell_start, const int32_t* pair_triangle, int64_t P, float* occlusion, tdgp_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Mesh textures (csrc/mesh_texture.hip; the reference's users bake a texture in MeshLab / Blender after decimating): a per-triangle atlas
  * whose layout is a pure function of the triangle count, filled from the field, and fetched at the hits of a mesh frame.
  *   tdgp_atlas_points -> [the field's colour at the points: the caller's] -> tdgp_atlas_texels

@@ -76,6 +76,9 @@ def build_parser():
     # and the distance report (mesh_distance.py): how far the simplified / decimated result is from the mesh it came from
     p.add_argument('--distance-report', action='store_true', default=argparse.SUPPRESS,
                    help='with simplification or decimation on: print the sampled two-sided surface distance (Hausdorff, mean, RMS) of the result to the unsimplified mesh')
+    # and ambient occlusion (mesh_rays.py): per vertex of the finished mesh, as grey vertex colours of the .ply
+    p.add_argument('--ao-rays', type=int, choices=[16, 32, 64], default=argparse.SUPPRESS, metavar='N',
+                   help='cast N (16, 32 or 64) cosine-weighted rays per vertex of the finished mesh and write the unoccluded share as grey vertex colours (needs --save-ply; default: none)')
     return p
 
 
@@ -131,9 +134,17 @@ def texture_options(args):
     return None if texels is None else dict(texels=texels)
 
 
+def ao_options(args):
+    """The `ao` argument of geometry.extract_geometry from the command line: None unless --ao-rays asks for it."""
+    rays = getattr(args, 'ao_rays', None)
+    return None if rays is None else dict(rays=rays)
+
+
 def parse_args(argv=None):
     p = build_parser()
     args = p.parse_args(argv)
+    if hasattr(args, 'ao_rays') and not args.save_ply:
+        p.error('--ao-rays writes the occlusion as vertex colours of the .ply: it needs --save-ply (the .obj carries no vertex colours)')
     if hasattr(args, 'texture_texels'):
         if not 2 <= args.texture_texels <= 64:
             p.error(f'--texture-texels takes an integer in [2, 64], got {args.texture_texels}')
@@ -182,13 +193,13 @@ def main(argv=None):
     os.makedirs(args.output_dir, exist_ok=True)
     need_mesh = args.save_obj or args.save_ply
     comp, smooth, with_normals = component_options(args), smooth_options(args), getattr(args, 'vertex_normals', False)
-    simplify, texture, decimate = simplify_options(args), texture_options(args), decimate_options(args)
+    simplify, texture, decimate, ao = simplify_options(args), texture_options(args), decimate_options(args), ao_options(args)
     for name, w in zip(names, ws.split(1, dim=0)):
         if need_mesh:
             shapes, counts = geometry.extract_geometry(G, w, volume_res=args.volume_res, voxel_origin=args.voxel_origin, cube_size=args.cube_size,
                                                        thresh_value=args.thresh_value, crop='reference', normalize=True, components=comp, smooth=smooth,
                                                        simplify=simplify, return_counts=True, **({} if texture is None else dict(texture=texture)),
-                                                       **({} if decimate is None else dict(decimate=decimate)))
+                                                       **({} if decimate is None else dict(decimate=decimate)), **({} if ao is None else dict(ao=ao)))
             shape = shapes[0]
             sigma = shape.sigma
             normals = tdgp.mesh_surface.vertex_normals(shape.vertices, shape.triangles) if with_normals else None
@@ -198,7 +209,8 @@ def main(argv=None):
                 else:
                     geometry.save_obj(os.path.join(args.output_dir, f'{name}.obj'), shape.vertices, shape.triangles, normals=normals)
             if args.save_ply:
-                geometry.save_ply(os.path.join(args.output_dir, f'{name}.ply'), shape.vertices, shape.triangles, normals=normals)
+                grey = {} if ao is None else dict(colours=shape.occlusion[:, None].expand(-1, 3))
+                geometry.save_ply(os.path.join(args.output_dir, f'{name}.ply'), shape.vertices, shape.triangles, normals=normals, **grey)
             if args.verbose:
                 print(f'{name}: {shape.vertices.shape[0]} vertices, {shape.triangles.shape[0]} triangles')
                 if simplify is not None:
@@ -215,6 +227,10 @@ def main(argv=None):
                     print(json.dumps(dict(name=name, distance=dict(hausdorff=d.hausdorff, mean=d.mean, rms=d.rms, result_to_full_max=d.a_to_b.max,
                                                                    full_to_result_max=d.b_to_a.max, samples=[d.a_to_b.samples, d.b_to_a.samples]),
                                           triangles=int(shape.triangles.shape[0]), triangles_full=int(full.triangles.shape[0]))))
+                if ao is not None:
+                    occ = shape.occlusion
+                    print(json.dumps(dict(name=name, ao_rays=ao['rays'], vertices=int(occ.shape[0]), occlusion_mean=float(occ.mean()) if occ.numel() else None,
+                                          occlusion_min=float(occ.min()) if occ.numel() else None)))
                 if texture is not None:
                     atlas = counts[0].atlas
                     print(json.dumps(dict(name=name, texture_texels=atlas.texels, atlas=[atlas.width, atlas.height], tiles_per_row=atlas.tiles_per_row,

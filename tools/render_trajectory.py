@@ -13,7 +13,7 @@ the rays and shaded (`--shape-mode shaded | normals | colour`, `--num-refine`, `
 `--vis mesh_grid` / `--vis mesh_strips`: the same layouts of MESH frames -- the surface extracted once per sample (`--volume-res`, `--cube-size`,
 marching cubes at `--level`) and rasterised for every frame; `--mesh-normals face` shades the flat facets, `vertex` interpolates the mesh's own vertex normals, `field` takes the normals from the field;
 `--mesh-smooth-iters N` Taubin-smooths every mesh on the device before it is drawn; `--mesh-simplify-cell X` then clusters its vertices in cells of
-X voxels (quadric placement) and draws the simplified mesh; `--mesh-decimate-triangles N` collapses edges until at most N triangles are left
+X voxels (quadric placement) and draws the simplified mesh; `--mesh-ao-rays N [--mesh-ao-radius R]` darkens each mesh by its per-vertex ambient occlusion (N rays per vertex); `--mesh-decimate-triangles N` collapses edges until at most N triangles are left
 (the surface stays closed and of the same topology); `--mesh-texture-texels N` bakes a texture of N texels per triangle leg from the field
 on every final mesh and draws the frames in colour mode from it (`--mesh-texture-filter nearest | bilinear`); `--mesh-samples 4 | 16` draws the
 frames with 4 or 16 coverage samples per pixel (anti-aliased silhouettes; face or vertex normals).
@@ -91,6 +91,15 @@ class _Parser(argparse.ArgumentParser):
                 self.error('--mesh-samples 4 | 16 draws with face or vertex normals (--mesh-normals field is evaluated once per pixel)')
         if a.mesh_smooth_iters < 0:
             self.error(f'--mesh-smooth-iters takes a non-negative integer, got {a.mesh_smooth_iters}')
+        if a.mesh_ao_rays is not None or a.mesh_ao_radius is not None:
+            if not a.vis.startswith('mesh_'):
+                self.error('--mesh-ao-rays and --mesh-ao-radius need --vis mesh_grid or mesh_strips')
+            if a.mesh_ao_rays is None:
+                self.error('--mesh-ao-radius needs --mesh-ao-rays')
+            if a.mesh_ao_radius is not None and not a.mesh_ao_radius > 0:
+                self.error(f'--mesh-ao-radius takes a positive number, got {a.mesh_ao_radius}')
+            if a.mesh_normals == 'field' or a.mesh_texture_texels is not None or a.shape_mode == 'normals':
+                self.error('--mesh-ao-rays darkens the shaded or coloured surface: it draws with face or vertex normals, without a texture, in --shape-mode shaded or colour')
         return a
 
 
@@ -137,6 +146,9 @@ def build_parser():
     p.add_argument('--mesh-texture-filter', choices=['nearest', 'bilinear'], default=None, help='mesh frames: how the texture is fetched (default bilinear)')
     p.add_argument('--mesh-samples', type=int, choices=[1, 4, 16], default=None, metavar='S',
                    help='mesh frames: coverage samples per pixel, 1 | 4 | 16 (default 1: one point sample at the pixel centre)')
+    p.add_argument('--mesh-ao-rays', type=int, choices=[16, 32, 64], default=None, metavar='N',
+                   help='mesh frames: ambient occlusion per vertex of each final mesh from N (16, 32 or 64) rays, multiplied into the surface colour (default: none)')
+    p.add_argument('--mesh-ao-radius', type=float, default=None, metavar='R', help='mesh frames: how far an occluder counts, in world units (default: any distance)')
     p.add_argument('--keep-components', type=parse_keep, default=None, metavar='K',
                    help="mesh frames: draw only the K largest connected components of each mesh ('all': no limit; default: the raw level set)")
     p.add_argument('--component-by', choices=['triangles', 'area'], default='triangles', help='mesh frames: what "largest" measures')
@@ -181,7 +193,8 @@ def mesh_options(args):
                 smooth=dict(iterations=args.mesh_smooth_iters) if args.mesh_smooth_iters > 0 else None,
                 simplify=dict(cell=args.mesh_simplify_cell) if args.mesh_simplify_cell is not None else None, **({'texture': texture} if texture else {}),
                 **({'decimate': dict(target_triangles=args.mesh_decimate_triangles)} if args.mesh_decimate_triangles is not None else {}),
-                **({'samples': args.mesh_samples} if (args.mesh_samples or 1) > 1 else {}))
+                **({'samples': args.mesh_samples} if (args.mesh_samples or 1) > 1 else {}),
+                **({'ao': dict(rays=args.mesh_ao_rays, radius=args.mesh_ao_radius)} if args.mesh_ao_rays is not None else {}))
 
 
 def main(argv=None):
@@ -234,6 +247,8 @@ def main(argv=None):
         if args.mesh_decimate_triangles is not None:
             line.update(mesh_decimate_triangles=args.mesh_decimate_triangles, decimate_rounds=[c.decimate['rounds'] for c in counts],
                         decimate_stopped=[c.decimate['stopped'] for c in counts])
+        if args.mesh_ao_rays is not None:
+            line.update(ao_rays=args.mesh_ao_rays, ao_radius=args.mesh_ao_radius)
         if args.mesh_texture_texels is not None:
             line.update(shape_mode='colour', mesh_texture_texels=args.mesh_texture_texels, mesh_texture_filter=args.mesh_texture_filter or 'bilinear',
                         atlas=[[c.atlas.width, c.atlas.height] for c in counts])
